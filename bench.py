@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/sec of the MI355X-native SPH step (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dam_break_1m]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dam_break_1m] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed warm-up steps, times exactly K steps and prints the result line (`value`, `ms_per_step`
+= the wall clock of one timed step, the iteration counts of the timed steps).  --dump-outputs DIR then also writes what the last
+timed step computed (position, velocity, density, pressure in global particle order, and that step's dt / time / iteration
+counts) as DIR/<name>.npy; the inputs are the same from run to run, so two builds can be compared output for output.
+Everything below -- the instrumented repeat, roofline, kernels, the other configs, transports, forced counts, the CPU
+baseline -- runs only with --full.
 
 A "step" is one `sph_step` (= single_step_without_adaptivity, simulation.rs:1980-2730) over the whole
 particle set, inputs resident in HBM.  Every N runs BASELINE.json configs[1] (2D dam-break, 1 048 576
@@ -12,7 +19,7 @@ STRONG scaling, the experiment north_star names ("N=1M at 1, 2, 4 and 8 GPUs"). 
 reported under "strong_8m" at every N (at N=1: the whole scene on one GPU).  --scaling weak keeps last
 round's ~1M-particles-per-GPU series as a side experiment.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   roofline      dominant neighbour sweep by time share: algorithmic bytes / HIP-event launch time vs 8 TB/s HBM
                 (HIP events of an instrumented pass right after the timed region -- see the comment in main())
   roofline_density  the same for the density kernel (north_star's named target kernel)
@@ -144,7 +151,39 @@ def parse_args():
     ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other single-GPU BASELINE configs")
     ap.add_argument("--no-8m", action="store_true", help="skip the strong-scaling leg on configs[3] (8.4M particles)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: instrumented repeat, roofline, other configs, transports, CPU baseline")
     return ap.parse_args()
+
+
+DUMP_FIELDS = ("position", "velocity", "density", "pressure")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, fields, extra, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """Write the per-particle arrays `fields` (equal first dimension, global particle order) and the small arrays `extra` as
+    out_dir/<name>.npy, float32 kept and everything else as float64.  If they would take more than `limit_bytes`, the per-particle
+    arrays are replaced by the same fixed, seeded sample of particles, whose indices are written as sample_index.npy."""
+    def as_float(a):
+        a = np.asarray(a)
+        return np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+
+    fields = {k: as_float(v) for k, v in fields.items()}
+    extra = {k: as_float(v) for k, v in extra.items()}
+    n = len(next(iter(fields.values())))
+    per_particle = sum(a.nbytes // max(n, 1) for a in fields.values())
+    small = sum(a.nbytes for a in extra.values())
+    if n and small + per_particle * n > limit_bytes:
+        m = max(0, (limit_bytes - small) // (per_particle + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+        fields = {k: v[idx] for k, v in fields.items()}
+        extra = dict(extra, sample_index=idx.astype(np.float64))
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in {**fields, **extra}.items():
+        np.save(out_dir / f"{k}.npy", v)
 
 
 def short_run(plib, name, steps=40, warmup=10, math_policy=None, list_forms=False, **param_overrides):
@@ -373,7 +412,7 @@ def main():
         return c, len(mass)
 
     def timed_run(c, p, warmup, steps):
-        """W untimed warm-up steps, then EXACTLY K steps between barriers; the MAX over ranks of the elapsed time."""
+        """W untimed warm-up steps, then EXACTLY K steps between barriers; the MAX over ranks of the elapsed time (and the last step's stats)."""
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         t_w0 = time.perf_counter()
@@ -381,7 +420,7 @@ def main():
             c.step(p)
         warm = time.perf_counter() - t_w0
         c.dist_get_stats(reset=True)
-        div_it, dens_it = [], []
+        div_it, dens_it, st = [], [], None
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -394,7 +433,7 @@ def main():
             tt = torch.tensor([el], device="cuda" if transport == "rccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        return el, warm, div_it, dens_it, c.dist_get_stats()
+        return el, warm, div_it, dens_it, c.dist_get_stats(), st
 
     def comm_record(stats, steps):
         """what this rank put on the wire per step (sph_dist_get_stats): latency-bound messages, so count and size both matter"""
@@ -415,9 +454,25 @@ def main():
     # step here -- measured -- so the per-kernel HIP-event timings below come from an instrumented pass that continues the same
     # workload right after the timed region; `value` is never taken from it.)
     leg(f"timed region: {wl}, {args.warmup} + {args.steps} steps")
-    elapsed, warmup_elapsed, div_iters, dens_iters, comm_stats = timed_run(ctx, p, args.warmup, args.steps)
+    elapsed, warmup_elapsed, div_iters, dens_iters, comm_stats, last_stats = timed_run(ctx, p, args.warmup, args.steps)
 
     n_local = ctx.n
+
+    if args.dump_outputs:
+        # what the last timed step computed, in global particle order (slab ranks: reassembled by particle id on rank 0)
+        leg(f"writing the last step's outputs to {args.dump_outputs}")
+        fields = {f: ctx.download(f) for f in DUMP_FIELDS}
+        if distributed:
+            parts = [None] * world
+            dist.all_gather_object(parts, (ctx.download("particle_id"), fields))
+            fields = {f: np.zeros((n_total,) + a.shape[1:], dtype=a.dtype) for f, a in fields.items()}
+            for ids, part in parts:
+                for f in fields:
+                    fields[f][ids] = part[f]
+        if rank == 0:
+            st = last_stats
+            step_stats = [] if st is None else [st.dt, st.time, st.div_solver.iters, st.density_solver.iters]
+            write_outputs(args.dump_outputs, fields, {"step_stats": np.array(step_stats, dtype=np.float64)})
 
     # ---- instrumented pass: THE SAME WINDOW again -- a fresh context, the same upload, the same W warm-up steps unprofiled, then the
     # same K steps with HIP events (timing-enabled markers on the library's own stream) around every kernel.  The step is
@@ -429,7 +484,7 @@ def main():
     # rocprofv3 reports as 10.44 us, profiles/r4_event_calibration.md), bracketed like every other kernel -- and subtracted.
     prof_all, prof_work, ev_overhead_us, marker_excess_us = {}, {}, 0.0, 0.0
     prof_window = None
-    if args.profile_steps != 0:
+    if args.full and args.profile_steps != 0:
         leg("instrumented repeat of the timed window")
         ctx.close()
         ctx, _ = make_context(scene, params)
@@ -459,8 +514,10 @@ def main():
                        "calibration_spin10_dispatch_us": (cal_d[1] * 1e3 / cal_d[0]) if cal_d and cal_d[0] else None,
                        "calibration_spin10_rocprofv3_us": SPIN10_ROCPROF_US}
         args.profile_steps = k_prof
-    leg("copy kernel")
-    copy_gbs = ctx.profile_copy_bandwidth_gbs(1 << 30) if rank == 0 else 0.0   # achievable HBM rate of this device, same run
+    copy_gbs = 0.0
+    if args.full and rank == 0:
+        leg("copy kernel")
+        copy_gbs = ctx.profile_copy_bandwidth_gbs(1 << 30)   # achievable HBM rate of this device, same run
     ctx.close()
 
     # ---- every transport this launch can run, side by side: the headline and configs[3] again over the peer-mapped
@@ -478,7 +535,7 @@ def main():
         try:
             leg(f"{label} over {tname}")
             c, n_ = make_context(scn, P, tname)
-            el_, _, di_, de_, st_ = timed_run(c, P.to_ffi(), args.warmup, args.steps)
+            el_, _, di_, de_, st_, _ = timed_run(c, P.to_ffi(), args.warmup, args.steps)
             rec.update({"ms_per_step": el_ * 1e3 / args.steps, "value": n_ * args.steps / el_, "unit": "particle-steps/s", "particles": n_,
                         "mean_div_iterations": float(np.mean(di_)), "mean_density_iterations": float(np.mean(de_)), "comm_rank0": comm_record(st_, args.steps)})
             leg(f"{label} over {tname}: exchange cost")
@@ -504,7 +561,7 @@ def main():
         return rec
 
     other_transports = [t for t in (["ipc"] if distributed and not os.environ.get("BENCH_ONE_TRANSPORT") else []) if t != transport]
-    if distributed and wl == "dam_break_1m":
+    if args.full and distributed and wl == "dam_break_1m":
         transports = {transport: {"ms_per_step": elapsed * 1e3 / args.steps, "value": n_total * args.steps / elapsed, "unit": "particle-steps/s",
                                   "comm_rank0": comm_record(comm_stats, args.steps), "primary": True}}
         for t in other_transports:
@@ -512,7 +569,7 @@ def main():
 
     # ---- north_star's second strong-scaling target: configs[3], 8.4M particles, same K / W, same protocol -------------------
     strong_8m = None
-    if not args.no_8m and wl == "dam_break_1m":
+    if args.full and not args.no_8m and wl == "dam_break_1m":
         s8, p8f, d8 = WORKLOADS["dam_break_8m"]
         P8 = p8f()
 
@@ -526,7 +583,7 @@ def main():
             sN, pNf, dN = WORKLOADS[name]
             PN = pNf()
             c8, n8 = make_context(sN(), PN)
-            el8, _, di8, de8, st8 = timed_run(c8, PN.to_ffi(), args.warmup, args.steps)
+            el8, _, di8, de8, st8, _ = timed_run(c8, PN.to_ffi(), args.warmup, args.steps)
             c8.close()
             os.environ.pop("SPH_OVERLAP", None)
             return {"workload": f"{name}: {dN}", "particles": n8, "value": n8 * args.steps / el8, "unit": "particle-steps/s",
@@ -548,7 +605,7 @@ def main():
     # strong-scaling case) with max_dt 0.00025, the largest of the three probed values at which it does not blow up
     # (profiles/r5_config3_divergence.md); same K / W, same protocol, at every N
     strong_8m_spec = None
-    if not args.no_8m and wl == "dam_break_1m":
+    if args.full and not args.no_8m and wl == "dam_break_1m":
         leg("SURVEY's configs[3] geometry: dam_break_8m_spec")
         strong_8m_spec = run_8m(None, "dam_break_8m_spec")
         strong_8m_spec["max_dt"] = 0.00025
@@ -559,7 +616,7 @@ def main():
     # the iterations is what ONE Jacobi iteration costs end to end (both sweeps, and on slabs: pack, exchange, unpack, totals) -- per
     # transport, comparable across N.  Never part of `value`.
     forced_count = None
-    if wl == "dam_break_1m":
+    if args.full and wl == "dam_break_1m":
         FORCED = dict(hybrid_dfsph_max_avg_density_error=0.0, hybrid_dfsph_max_avg_divergence_error=0.0)
         K_LO, K_HI, W_F, S_F = 6, 18, 2, 6
 
@@ -571,7 +628,7 @@ def main():
                 try:
                     PF = pFf(max_iters=K, **FORCED)
                     c, nF = make_context(sF(), PF, tname)
-                    elF, _, diF, deF, _ = timed_run(c, PF.to_ffi(), W_F, S_F)
+                    elF, _, diF, deF, _, _ = timed_run(c, PF.to_ffi(), W_F, S_F)
                     rec[K] = (elF * 1e3 / S_F, float(np.mean(diF)) - 1 + float(np.mean(deF)) - 1, nF)
                 except (ffi.SphError, RuntimeError) as e:
                     return {"failed": str(e)[:300]}
@@ -598,7 +655,7 @@ def main():
     # and the lists, merge_partner / merge_counter broadcast, every rank applies to its own slab; the particles never leave their GPU).
     # The ghost layer of a cut is as wide as the largest smoothing length NEAR it asks for, so the fine block's slices stand on 8 ranks.
     config4 = None
-    if distributed and not args.no_8m and wl == "dam_break_1m":
+    if args.full and distributed and not args.no_8m and wl == "dam_break_1m":
         from adaptive_sph_amd.distributed import rank_single_step_adaptivity_on_slabs
         s4, p4f, d4 = WORKLOADS["ratio_stress_4m"]
         r_fine = float(np.sqrt(np.float32(0.0004385) ** 2 * 0.93 / np.pi))
@@ -611,7 +668,7 @@ def main():
             scn4 = s4()
             c4, n4 = make_context(scn4, P4)
             k4 = max(2, min(args.steps, 10))
-            el4, _, _, de4, st4 = timed_run(c4, P4.to_ffi(), 2, k4)
+            el4, _, _, de4, st4, _ = timed_run(c4, P4.to_ffi(), 2, k4)
             config4.update({"particles": n4, "steps": k4, "ms_per_step": el4 * 1e3 / k4, "particle_steps_per_s": n4 * k4 / el4,
                             "mean_density_iterations": float(np.mean(de4)), "comm_rank0": comm_record(st4, k4)})
             from adaptive_sph_amd.adaptivity import SplitPatterns
@@ -778,17 +835,20 @@ def main():
         "config": {"workload": f"{wl}: {desc}", "particles": n_total, "solver": params.pressure_solver_method,
                    "mean_div_iterations": float(np.mean(div_iters)), "mean_density_iterations": float(np.mean(dens_iters)),
                    "parallelism": (f"x-slabs x{world}" + ("" if transport == "rccl" else f", {transport} transport (more ranks than GPUs: functional run)")) if distributed else "single GPU"},
-        "roofline": roofline,
-        "roofline_density": roofline_density,
-        "kernels": kernels,
-        "strong_8m": strong_8m,
-        "strong_8m_spec": strong_8m_spec,
-        "transports": transports,
-        "forced_count": forced_count,
-        "config4_ratio_stress_4m": config4,
-        "comm_rank0": comm_record(comm_stats, args.steps) if distributed else {"host_waits_per_step": comm_stats["host_waits"] / max(args.steps, 1)},
     }
-    if distributed:   # time inside RCCL per step, from the instrumented pass (HIP events around the grouped send/recv and the all-reduces)
+    if args.full:
+        out.update({
+            "roofline": roofline,
+            "roofline_density": roofline_density,
+            "kernels": kernels,
+            "strong_8m": strong_8m,
+            "strong_8m_spec": strong_8m_spec,
+            "transports": transports,
+            "forced_count": forced_count,
+            "config4_ratio_stress_4m": config4,
+        })
+    out["comm_rank0"] = comm_record(comm_stats, args.steps) if distributed else {"host_waits_per_step": comm_stats["host_waits"] / max(args.steps, 1)}
+    if args.full and distributed:   # time inside RCCL per step, from the instrumented pass (HIP events around the grouped send/recv and the all-reduces)
         out["comm_rank0"]["rccl_us_per_step_instrumented"] = {
             k: prof_all[k][1] * 1e3 / max(args.profile_steps, 1) for k in ("rccl_sendrecv", "rccl_allreduce") if k in prof_all}
     # whole-step algorithmic bytes B_step = 388 + 100 (n_div + n_dens) B per particle-step with the
@@ -814,7 +874,7 @@ def main():
         "steps_from_rest": {"steps": args.warmup, "ms_per_step": warmup_elapsed * 1e3 / max(args.warmup, 1),
                             "note": "steps 0..warmup-1 (rest lattice, first launches included); rank 0's clock, not part of `value`"},
     }
-    if not args.no_extra and not distributed and wl == "dam_break_1m":
+    if args.full and not args.no_extra and not distributed and wl == "dam_break_1m":
         out["other_configs"] = []
         leg("other configs: dam_break_1m_adaptive")
         out["other_configs"].append(short_run(plib, "dam_break_1m_adaptive"))                                    # configs[2]: 4:1 radius ratio
@@ -851,7 +911,7 @@ def main():
                 out["other_configs"].append(ad)
         except Exception as e:   # (a refusal of the adaptive step is a result, not a reason to lose the line)
             out["other_configs"].append({"workload": "ratio_stress_4m WITH adaptivity", "refused": str(e)[:300]})
-    if not args.no_cpu_baseline and not distributed:
+    if args.full and not args.no_cpu_baseline and not distributed:
         leg("cpu baseline (oracle)")
         out["cpu_baseline"] = cpu_baseline(scene, params, args.cpu_seconds)
     wd["off"] = True

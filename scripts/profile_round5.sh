@@ -9,6 +9,7 @@
 #   + the other configs (profile_configs.sh: configs[2], [3] -- whose traffic decides roofline.bound --, [4]'s scene, configs[1] + level estimation)
 # then: python scripts/summarize_profile.py gpurun_out/r5p profiles/r5p ; python scripts/pmc_table.py gpurun_out/r5p/sq > profiles/r5_sq_counters.txt
 R=$1
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 bash $GRAFT_REPO_ROOT/scripts/profile_round.sh $R
 bash $GRAFT_REPO_ROOT/scripts/pmc_run2.sh $R/sq "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_BUSY_CYCLES" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SMEM" \
      "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS" \
@@ -16,6 +17,6 @@ bash $GRAFT_REPO_ROOT/scripts/pmc_run2.sh $R/sq "SQ_WAVES SQ_INSTS_VALU SQ_INSTS
      "TCC_HIT TCC_MISS TCC_REQ" "TA_TA_BUSY TA_ADDR_STALLED_BY_TC_CYCLES TA_DATA_STALLED_BY_TC_CYCLES TA_FLAT_LOAD_WAVEFRONTS"
 OUT=$GRAFT_REPO_ROOT/$R
 cd /tmp; export TMPDIR=/tmp
-timeout -k 5 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt2 -o kt -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-8m > $OUT/kt2_bench.json 2> $OUT/kt2.err; echo "two-pass trace rc=$?"
+timeout -k 5 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt2 -o kt -- python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra --no-8m > $OUT/kt2_bench.json 2> $OUT/kt2.err; echo "two-pass trace rc=$?"
 cd $GRAFT_REPO_ROOT; python scripts/kt_two_passes.py $R/kt2 $R/kt2_bench.json | tee $R/two_passes.txt; rm -rf $OUT/kt2
 bash $GRAFT_REPO_ROOT/scripts/profile_configs.sh $R

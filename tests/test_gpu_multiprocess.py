@@ -64,7 +64,7 @@ def test_bench_starts_its_own_ranks_and_prints_the_schema():
         env = _env()
         env.update(extra_env)
         r = subprocess.run([sys.executable, str(REPO / "bench.py")] + cmd + ["--steps", "4", "--warmup", "2", "--workload", "dam_break_64k", "--no-8m",
-                                                                           "--profile-steps", "2", "--no-cpu-baseline"],
+                                                                           "--profile-steps", "2", "--no-cpu-baseline", "--full"],
                            capture_output=True, text=True, timeout=900, env=env, cwd=str(REPO))
         assert r.returncode == 0, r.stderr[-4000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
