@@ -42,6 +42,12 @@ def build_parser() -> argparse.ArgumentParser:
     # the reference's VtkExporter is compiled in but switched off (main_loop.rs:253 `export_vtk_data = false`); same writer here
     run.add_argument("--vtk", default=None, metavar="FOLDER", help="write FOLDER/my-sph-NNNNN.vtk + my-sph.vtk.series (one snapshot per step)")
     run.add_argument("--vtk-every", type=int, default=1, help="snapshot every N-th step")
+    img = sub.add_parser("image", help="Render images (and video frames) as described by export recipes")
+    img.add_argument("RECIPE", nargs="+", help="ImageExportConfig list (YAML); paths inside are relative to its directory")
+    img.add_argument("--split-patterns", default=None,
+                     help="SplitPatterns file for recipes that split; default ./split-patterns.yaml, like the reference")
+    img.add_argument("--supersample", type=int, default=1, choices=[1, 2, 3, 4], help="S x S samples per pixel (1: the reference's pixel grid)")
+    img.add_argument("--device", type=int, default=0)
     return ap
 
 
@@ -104,6 +110,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "run":
         run(args)
+    elif args.command == "image":
+        from .image_export import main_image
+        main_image(args)
     return 0
 
 

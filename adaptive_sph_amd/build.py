@@ -42,7 +42,7 @@ def build_hip(force: bool = False, verbose: bool = False, out_name: str = "libsp
     from concurrent.futures import ThreadPoolExecutor
     out = CSRC / out_name   # (variants are built HERE, next to the product library, and selected with SPH_HIP_LIBRARY: ffi.py)
     srcs = sorted(CSRC.glob("*.hip"))
-    headers = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + [REPO / "include" / "sph_ffi.h"]
+    headers = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + sorted((REPO / "include").glob("*.h"))
     extra = os.environ.get("SPH_EXTRA_HIPCC_FLAGS", "").split() + list(extra_flags)
     # -fno-slp-vectorize: the SLP vectoriser turns pairs of scalar f32 operations into v_pk_* instructions and pays for each with register
     # moves (73 v_mov in sweep B's hot path); without it the same arithmetic is 1-5 % faster per sweep (profiles/r5_variants.md section 3)

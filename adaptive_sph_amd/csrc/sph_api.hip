@@ -693,7 +693,8 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
-                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx};
+                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
+                     &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
     for (auto b : all) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);
@@ -767,6 +768,7 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->have_reduced = false;
     c->lists_after = false;
     c->hdr_ahead = false;
+    c->rnd_have_prev = false;   // a render snapshot (sph_render.hip) belongs to the particle set it was taken from
     if (n == 0) return SPH_OK;
     // stage host arrays through scratch buffers: mass -> key[1], pos -> scratch, vel -> vel_tmp
     HIPCHK(c, hipMemcpyAsync(c->key[1].p, mass, n * sizeof(float), hipMemcpyHostToDevice, s));

@@ -241,6 +241,11 @@ struct sph_ctx {
     uint32_t last_div_iters = 2, last_dens_iters = 2;
     uint32_t prev_dens_iters = 0;
     uint32_t prev_div_iters = 0;   // the step before: the solves are chained only while the divergence solve's count repeats
+    // frames (sph_render.hip): the colour records by reference index, the sample keys, the output staging, the pressure maximum, the
+    // positions kept for an interpolated frame (sph_render_snapshot) -- allocated on first use, kept across frames, freed by sph_destroy
+    DevBuf rnd_rec, rnd_keys, rnd_out, rnd_max, rnd_prev;
+    uint64_t rnd_prev_n = 0;
+    bool rnd_have_prev = false;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)

@@ -152,6 +152,19 @@ class SphError(RuntimeError):
 # every symbol include/sph_ffi.h declares (checked by tests/test_abi.py)
 MATH_POLICIES = {"fast": 0, "exact": 1}   # enum sph_math_policy
 
+# include/sph_render.h: frames drawn on the device (product only; not part of sph_ffi.h, the oracle draws nothing)
+RENDER_SYMBOLS = ["render", "render_colors", "render_snapshot"]
+RENDER_MAX_STOPS = 16
+RENDER_SHOW_SURFACE, RENDER_SHOW_NEIGHBORHOOD_REDUCED, RENDER_FROM_STASH, RENDER_INTERPOLATE = 1, 2, 4, 8
+
+
+class SphRenderParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("supersample", C.c_int32), ("zoom_out", C.c_float),
+                ("attribute", C.c_int32), ("flags", C.c_uint32), ("alpha", C.c_float), ("n_stops", C.c_int32),
+                ("stops", (C.c_float * 4) * RENDER_MAX_STOPS), ("n_segments", C.c_int32), ("segments", C.POINTER(C.c_float)),
+                ("line_width", C.c_float)]
+
+
 ABI_SYMBOLS = [
     "create", "destroy", "upload", "upload_field", "download", "download_neighbors", "num_particles", "time",
     "set_time", "step", "classify", "share_particles", "merge_particles", "set_split_patterns", "split_particles", "host_find_partners", "last_error", "grid", "set_boundary_polygon", "set_math_policy", "get_math_policy", "apply_edits", "profile_enable", "profile_reset", "profile_get", "profile_event_overhead", "profile_dispatch_bracket", "profile_copy_bandwidth", "profile_list_forms", "set_sweep_variant",
@@ -265,6 +278,10 @@ class SphLibrary:
         self.dist_set_rebalance = sig("dist_set_rebalance", i32, [vp, i32], required=False)
         self.dist_get_cuts = sig("dist_get_cuts", i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)], required=False)
         self.dist_get_stats = sig("dist_get_stats", i32, [vp, C.POINTER(SphDistStats), i32], required=False)
+        rpp = C.POINTER(SphRenderParams)
+        self.render = sig("render", i32, [vp, C.POINTER(SphParams), rpp, vp, u64], required=False)
+        self.render_colors = sig("render_colors", i32, [vp, C.POINTER(SphParams), rpp, vp, u64], required=False)
+        self.render_snapshot = sig("render_snapshot", i32, [vp], required=False)
 
 
 _PRODUCT = None
@@ -457,6 +474,29 @@ class Context:
 
     def split_particles(self, params: SphParams, ap: "SphAdaptParams") -> None:
         self._check(self.lib.split_particles(self.handle, C.byref(params), C.byref(ap)))
+
+    # ---- frames (include/sph_render.h; adaptive_sph_amd/render.py builds the parameters) ----
+    def _render_lib(self):
+        if self.lib.render is None:
+            raise SphError(30, f"{self.lib.path.name} has no renderer (sph_render.h is implemented by the product library only)")
+        return self.lib
+
+    def render_frame(self, params: SphParams, rp: "SphRenderParams") -> np.ndarray:
+        """sph_render: the frame as uint8[height, width, 3], top row first."""
+        out = np.empty((int(rp.height), int(rp.width), 3), np.uint8)
+        self._check(self._render_lib().render(self.handle, C.byref(params), C.byref(rp), out.ctypes.data, out.nbytes))
+        return out
+
+    def render_colors(self, params: SphParams, rp: "SphRenderParams") -> np.ndarray:
+        """sph_render_colors: uint8[n, 3], reference (host) order."""
+        out = np.empty((self.n, 3), np.uint8)
+        self._check(self._render_lib().render_colors(self.handle, C.byref(params), C.byref(rp), out.ctypes.data if out.size else None,
+                                                     out.nbytes))
+        return out
+
+    def render_snapshot(self) -> None:
+        """sph_render_snapshot: keep the current positions for the next interpolated frame."""
+        self._check(self._render_lib().render_snapshot(self.handle))
 
     def grid(self) -> SphGridInfo:
         g = SphGridInfo()
