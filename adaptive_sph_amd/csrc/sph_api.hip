@@ -555,13 +555,15 @@ Options options_from_env()
     o.slab_records = num("SPH_SLAB_RECORDS", 1) != 0 ? 1 : 0;
     o.side_cus = num("SPH_SIDE_CUS", 0);
     o.main_exclude = num("SPH_MAIN_EXCLUDE", 0) != 0 ? 1 : 0;
+    o.ipc_fuse_max_bytes = std::max(num("SPH_IPC_FUSE_MAX_BYTES", 64 << 10), 0);
+    o.ipc_copy_min_bytes = std::max(num("SPH_IPC_COPY_MIN_BYTES", 256 << 10), 0);
 #else
     // the product ignores the laboratory's switches -- and says so, once per process (advisor r5: a bisect script that sets them against
     // libsph_hip.so would otherwise run the defaults in every row and report nothing)
     static const char* const lab_only[] = {"SPH_PACED", "SPH_PACE_LEAD", "SPH_PACE_PRED", "SPH_CHAIN", "SPH_ACCEL_GENERIC", "SPH_JACOBI_GENERIC", "SPH_SOURCE_GENERIC",
                                            "SPH_SLAB_GENERAL", "SPH_SLAB_LEVEL_PLAIN", "SPH_LEVEL_SERIAL", "SPH_LEVEL_BATCH8", "SPH_LEVEL_QUEUE", "SPH_OFFSET_LISTS",
                                            "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
-                                           "SPH_SIDE_CUS", "SPH_MAIN_EXCLUDE"};
+                                           "SPH_SIDE_CUS", "SPH_MAIN_EXCLUDE", "SPH_IPC_FUSE_MAX_BYTES", "SPH_IPC_COPY_MIN_BYTES"};
     static bool warned = false;
     if (!warned)
         for (const char* name : lab_only)

@@ -81,6 +81,8 @@ struct Options {
     int hip_trace = 0;          // SPH_HIP_TRACE=1          host-side timeline of the step
     int side_cus = 0;           // SPH_SIDE_CUS=<k>         (lab) the side stream (level-set propagation) owns k CUs of every XCD through a CU mask (0: no mask)
     int main_exclude = 0;       // SPH_MAIN_EXCLUDE=1       (lab) ... and the main stream is masked OFF those CUs
+    int ipc_fuse_max_bytes = 64 << 10;   // SPH_IPC_FUSE_MAX_BYTES=<b>  push transport: a Jacobi iteration's exchange is fused (Comm::exchange_fused) while its largest message is <= b (0: never)
+    int ipc_copy_min_bytes = 256 << 10;  // SPH_IPC_COPY_MIN_BYTES=<b>  push transport: a message above b bytes is copied by k_ipc_copy, the push kernel only signals
 };
 Options options_from_env();   // sph_api.hip
 

@@ -1894,8 +1894,54 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     return SPH_OK;
 }
 
-static int group_step(Group& G, const sph_params* p, sph_step_stats* outs)
+// Step-start agreement of a slab decomposition: every rank passes its own sph_params and holds its own math policy
+// (sph_set_math_policy is per context).  Ranks that differ would exchange ghost values of different arithmetic, size buffers for
+// one policy and index them under the other, or leave a solve while a neighbour waits in its next collective.  A loopback group
+// compares its members on the host (one sph_params for all of them); a per-rank transport min-reduces ONE row: a 64-bit digest of
+// the parameters' bytes and the policy, in 16-bit pieces (exact as floats) and their negations (min of -v = -max v).  A rank whose
+// piece is not both the minimum and the maximum differs from another rank -- and then EVERY rank sees min != max.  Refused before
+// anything is launched: nothing to poison, every rank returns the same status (`together`: the transport stays usable).
+static int agree_step_inputs(Group& G, const sph_params* p, bool* together)
 {
+    static_assert(sizeof(sph_params) % 4 == 0, "sph_params: 4-byte fields, no padding (the digest hashes its bytes)");
+    sph_ctx* c0 = G.m[0];
+    bool policy_differs = false, params_differ = false;
+    if (G.m.size() > 1) {
+        for (auto c : G.m) policy_differs |= c->exact != c0->exact;
+    } else {
+        uint64_t h = 1469598103934665603ull;   // FNV-1a over the bytes of sph_params
+        const uint8_t* b = (const uint8_t*)p;
+        for (size_t k = 0; k < sizeof(sph_params); k++) h = (h ^ b[k]) * 1099511628211ull;
+        std::vector<std::vector<float>> row(1, std::vector<float>(10));
+        for (int k = 0; k < 4; k++) row[0][k] = (float)((h >> (16 * k)) & 0xffffu);
+        row[0][4] = (float)c0->exact;
+        for (int k = 0; k < 5; k++) row[0][5 + k] = -row[0][k];
+        const std::vector<float> mine = row[0];
+        if (int rc = G.comm->allreduce_min_f32(G, row)) return rc;
+        for (int k = 0; k < 10; k++)
+            if (row[0][k] != mine[k]) (k % 5 == 4 ? policy_differs : params_differ) = true;
+    }
+    if (!policy_differs && !params_differ) return SPH_OK;
+    *together = true;
+    for (auto c : G.m) {
+        if (policy_differs)
+            (void)c->fail(SPH_ERR_INVALID_ARGUMENT, "the ranks of the slab decomposition differ in their math policy (sph_set_math_policy; rank %d: %s); nothing was launched",
+                          c->dist.rank, c->exact ? "EXACT" : "FAST");
+        else
+            (void)c->fail(SPH_ERR_INVALID_ARGUMENT, "the ranks of the slab decomposition differ in their sph_params (rank %d passed its own to sph_step); nothing was launched", c->dist.rank);
+    }
+    return SPH_ERR_INVALID_ARGUMENT;
+}
+
+static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool* refused_together = nullptr)
+{
+    if (G.multi()) {
+        bool together = false;
+        if (int rc = agree_step_inputs(G, p, &together)) {
+            if (refused_together) *refused_together = together;
+            return rc;
+        }
+    }
     bool started = false;
     const int rc = group_step_inner(G, p, outs, &started);
     if (rc && started)
@@ -1920,8 +1966,9 @@ extern "C" int sph_step(sph_ctx* c, const sph_params* p, sph_step_stats* out)
     G.m.push_back(c);
     int rc = comm_for_rank(c, &G.comm);
     if (rc) return rc;
-    rc = group_step(G, p, out);
-    if (rc) comm_abandon(c);   // (thread / shared-memory transports: the other ranks' next collective reports it instead of waiting)
+    bool refused_together = false;   // every rank refused the step in the same collective: the transport stays usable
+    rc = group_step(G, p, out, &refused_together);
+    if (rc && !refused_together) comm_abandon(c);   // (thread / shared-memory transports: the other ranks' next collective reports it instead of waiting)
     return rc;
 }
 

@@ -1336,7 +1336,12 @@ __global__ __launch_bounds__(1024) void k_ipc_wait_unpack(IpcFusedWait f)
 
 struct IpcComm : ShmComm {
     static IpcState* st(sph_ctx* c) { return (IpcState*)c->dist.ipc; }
-    bool can_fuse_iteration(Group& G, size_t bytes) override { return G.m.size() == 1 && st(G.m[0]) && bytes <= st(G.m[0])->bytes_per_side && bytes <= (64u << 10); }
+    // (rank-local inputs: a rank may fuse while its x-neighbour does not -- the two forms share the sequence counters, the inbox layout and
+    //  the totals table; tests/test_gpu_multiprocess.py mixes them through the laboratory's Options::ipc_fuse_max_bytes)
+    bool can_fuse_iteration(Group& G, size_t bytes) override
+    {
+        return G.m.size() == 1 && st(G.m[0]) && bytes <= st(G.m[0])->bytes_per_side && bytes <= (size_t)G.m[0]->opt.ipc_fuse_max_bytes;
+    }
     int exchange_fused(Group& G, const FusedField& f, int slot) override
     {
         sph_ctx* c = G.m[0];
@@ -1437,7 +1442,8 @@ struct IpcComm : ShmComm {
             const int oside = side ^ 1;   // I am my left neighbour's right side
             const uint32_t gran = (uint32_t)((xf.send_bytes[side] + 15) / 16);
             uint4* dst = (uint4*)IpcState::inbox(I->peer[nb], I->bytes_per_side, oside, parity);
-            if (gran > 16384u) {   // > 256 KB: many workgroups copy, the push kernel only signals
+            if ((size_t)gran * 16 > (size_t)c->opt.ipc_copy_min_bytes) {   // > 256 KB: many workgroups copy, the push kernel only signals
+                ProfScope pc(&c->prof, "ipc_copy", c->stream);
                 hipLaunchKernelGGL(k_ipc_copy, dim3(std::min(1024u, (gran + 255u) / 256u)), dim3(256), 0, c->stream, (const uint4*)xf.send[side], dst, gran);
                 ps.granules[side] = 0;
             } else {

@@ -62,14 +62,16 @@ def pick_transport(world: int) -> str:
 _SHM_SERIAL = [0]
 
 
-def make_slab_context(lib: ffi.SphLibrary, pos, mass, vel, planes, rank: int, world: int, local_rank: int, transport: str = None) -> ffi.Context:
+def make_slab_context(lib: ffi.SphLibrary, pos, mass, vel, planes, rank: int, world: int, local_rank: int, transport: str = None,
+                      cuts: Sequence[float] = None) -> ffi.Context:
     """This rank's slab context of a `torch.distributed` launch (one process per rank): configured, communicator attached, particles
-    uploaded.  torch.distributed only carries the RCCL unique id (or the shared-memory segment's name) and a barrier."""
+    uploaded.  torch.distributed only carries the RCCL unique id (or the shared-memory segment's name) and a barrier.  `cuts`: the
+    world + 1 static cuts (default: slab_cuts, equal counts)."""
     import os
     import torch.distributed as dist
     import torch
     transport = transport or pick_transport(world)
-    cuts = slab_cuts(pos[:, 0], world)
+    cuts = list(cuts) if cuts is not None else slab_cuts(pos[:, 0], world)
     mine = partition(pos[:, 0], cuts)[rank]
     cap = _slab_capacity(len(mass), world)
     ctx = ffi.Context(lib, cap, planes, device_id=local_rank)
@@ -130,8 +132,8 @@ def make_slab_context(lib: ffi.SphLibrary, pos, mass, vel, planes, rank: int, wo
     return ctx
 
 
-def make_loopback_group(lib: ffi.SphLibrary, pos, mass, vel, planes, n_ranks: int, device_id: int = 0) -> List[ffi.Context]:
-    cuts = slab_cuts(pos[:, 0], n_ranks)
+def make_loopback_group(lib: ffi.SphLibrary, pos, mass, vel, planes, n_ranks: int, device_id: int = 0, cuts: Sequence[float] = None) -> List[ffi.Context]:
+    cuts = list(cuts) if cuts is not None else slab_cuts(pos[:, 0], n_ranks)
     parts = partition(pos[:, 0], cuts)
     ctxs = []
     for r in range(n_ranks):

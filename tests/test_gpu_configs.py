@@ -85,7 +85,7 @@ def test_config3_dam_break_8m_eight_slabs_against_the_single_context(product_lib
     single.upload(mass, pos, vel)
     grp = D.make_loopback_group(product_lib, pos, mass, vel, planes, 8)
     assert sum(c.n for c in grp) == len(mass) == n_expected and min(c.n for c in grp) > 1000000
-    for s in range(3):
+    for s in range(steps):
         st1 = single.step(p)
         sts = ffi.group_step(grp, p)
         assert all(st.dt == st1.dt for st in sts)
@@ -96,6 +96,10 @@ def test_config3_dam_break_8m_eight_slabs_against_the_single_context(product_lib
     assert np.array_equal(D.gather_by_id(grp, "neighbor_count", n), single.download("neighbor_count"))
     for f, tol in (("position", 1e-5), ("velocity", 1e-4), ("density", 1e-5), ("mass", 0.0)):
         assert rel_err(D.gather_by_id(grp, f, n), single.download(f)) <= tol, f
+    # (a position bar of 1e-5 of max|x| is ~100 ulp of a coordinate: more than the first steps move a particle -- the displacement
+    #  from the uploaded positions is the bar that can fail)
+    ok, rep = displacement_bars(D.gather_by_id(grp, "position", n), single.download("position"), pos)
+    assert ok, rep
     st = grp[3].dist_get_stats()
     assert st["n_ghost"][0] > 0 and st["n_ghost"][1] > 0 and st["exchanges"] > 0    # an inner slab has two neighbours
     # the slabs' neighbour lists (global ids, ghosts included) are the single context's ENTRY BY ENTRY (this test

@@ -8,6 +8,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -132,3 +133,59 @@ print("CLEAN", flush=True)
     build.build_lab()   # (SPH_AHEAD_BUILD is a laboratory switch: both runs on libsph_lab.so, whose default IS the product's path)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, SPH_HIP_LIBRARY="libsph_lab.so"))
     assert r.returncode == 0 and "CLEAN" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-2500:])
+
+
+# ---- rows of the push transport whose ranks take different forms (tests/mp_slab_check.py: MP_RANK_ENV, MP_CUTS, MP_FORMS) ---------------
+# A Jacobi iteration's exchange is fused into two launches where IpcComm::can_fuse_iteration says so, and that is decided per rank from
+# rank-local inputs (its own largest halo / ghost count, whether it holds any particle).  The fused form and the plain one share the
+# sequence counters, the inbox layout and the totals table: every row below mixes them, asserts from each rank's profile that it was
+# mixed (fused: ipc_pack_push), and ends bit for bit the loopback group of the same cuts (the check mp_slab_check.py always makes).
+
+def _mp_run(world, port, extra_env, timeout=600):
+    env = _env()
+    env.update(extra_env)
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
+                        "--master-port", str(port), str(REPO / "tests" / "mp_slab_check.py")],
+                       capture_output=True, text=True, timeout=timeout, env=env, cwd=str(REPO))
+    assert r.returncode == 0 and f"MP_CHECK OK world={world}" in r.stdout, r.stdout[-3000:] + r.stderr[-4000:]
+    forms = [l for l in r.stdout.splitlines() if l.startswith("MP_FORMS")]
+    print("\n".join(forms))
+    return r.stdout
+
+
+@pytest.mark.parametrize("world,unfused", [(3, (1,)), (4, (1, 3))], ids=["middle-rank-unfused", "alternating"])
+def test_push_transport_rows_with_fused_and_unfused_ranks(lab_lib, world, unfused):
+    """Laboratory switch SPH_IPC_FUSE_MAX_BYTES=0 on some ranks only (the threshold is the rank-local input of the fuse decision): world 3
+    with the middle rank never fusing between two fusing ranks, world 4 alternating.  Each rank's profile shows the form it ran."""
+    out = _mp_run(world, 29680 + world, {"SPH_TRANSPORT": "ipc", "SPH_HIP_LIBRARY": "libsph_lab.so", "MP_FORMS": "1",
+                                         "MP_RANK_ENV": ";".join(f"{r}:SPH_IPC_FUSE_MAX_BYTES=0" for r in unfused),
+                                         "MP_EXPECT_FORMS": ",".join("U" if r in unfused else "F" for r in range(world))})
+    assert "transport=ipc" in out and out.count("MP_FORMS") == world
+
+
+def test_push_transport_rank_that_starts_empty(product_lib):
+    """The natural mixed row, on the PRODUCT library: static cuts leave the last of three ranks without a particle and out of reach of
+    the column's ghost layer, so it takes part in every Jacobi iteration's totals through the plain push while its neighbours fuse.
+    The column reaches it within the run: it receives ghosts, fuses from then on, and owns particles at the end."""
+    from adaptive_sph_amd import scene as sc
+    pos = sc.init_particles(sc.dam_break_small(128, 64, 1 / 64))[0]
+    inner = [float(np.float32(np.median(pos[:, 0]))), float(np.float32(pos[:, 0].max() + 0.075))]
+    _mp_run(3, 29690, {"SPH_TRANSPORT": "ipc", "MP_FORMS": "1", "MP_STEPS": "36", "MP_CUTS": ",".join(repr(c) for c in inner),
+                       "MP_EXPECT_FORMS": "F,F,UF"})
+
+
+def test_push_transport_large_messages_take_the_copy_path(lab_lib):
+    """IpcComm::round copies a message above SPH_IPC_COPY_MIN_BYTES (256 KB in the product) with the multi-workgroup k_ipc_copy and lets
+    the push kernel only signal.  With the laboratory threshold at 2 KB the per-step ghost / record messages and the plain field
+    refreshes take that path on both ranks: the copy launches show in the profile, more bytes than the threshold left each rank in
+    one step, and the result is the loopback group's bit for bit."""
+    _mp_run(2, 29693, {"SPH_TRANSPORT": "ipc", "SPH_HIP_LIBRARY": "libsph_lab.so", "MP_FORMS": "1", "SPH_IPC_COPY_MIN_BYTES": "2048",
+                       "MP_EXPECT_FORMS": "C,C"})
+
+
+def test_ranks_as_processes_refuse_a_step_with_different_parameters_together(product_lib):
+    """Two processes over the shared-memory transport; at step 2 rank 1 passes a max_iters one higher.  The step-start agreement refuses
+    that step on both ranks (status 1, the message names sph_params) before anything is launched; the transport stays usable and the
+    run goes on to end bit for bit the loopback group that never saw the refusal."""
+    out = _mp_run(2, 29695, {"SPH_TRANSPORT": "shm", "MP_REFUSE_AT": "2"})
+    assert "MP_REFUSED every rank" in out

@@ -1,6 +1,8 @@
 """Slab decomposition (the multi-GPU algorithm) verified on ONE GPU: k contexts of this process act as ranks
 0..k-1 with the loopback transport (sph_group_step); the same driver code runs with the RCCL transport when
 every rank is its own process.  Results must match a single context on the same scene."""
+import os
+
 import numpy as np
 import pytest
 
@@ -962,3 +964,269 @@ def test_rccl_single_rank_roundtrip(product_lib):
     c.upload(mass, pos, vel)
     c.step(dam_break_params().to_ffi())
     assert np.all(np.isfinite(c.download("position")))
+
+
+# ---- rows whose ranks decide differently, and the step-start agreement on sph_params / the math policy -----------------------------
+# A loopback group takes every decision once for the whole row (member 0's options, its policy); ranks on threads -- what every
+# process of a multi-GPU run executes -- decide some things alone: the form of sweep A (SPH_OVERLAP, by slab size), and they hold
+# their own math policy and pass their own sph_params.  The mixed rows below are compared BIT FOR BIT with the loopback group of the
+# same cuts (the reference for slab arithmetic), and each asserts from the ranks' profiles that the row really was mixed.
+
+def _column(side_x=96, side_y=48):
+    scn = sc.dam_break_small(side_x, side_y, 1 / 48)
+    pos, mass, vel = sc.init_particles(scn)
+    vel = vel.copy()
+    vel[:, 0] = 0.8                               # particles cross the cuts
+    return pos, mass, vel, sc.boundary_planes(scn.boundary)
+
+
+def _set_policy(c, policy):
+    if policy is not None:
+        c.set_math_policy(policy)
+
+
+class _Ranks:
+    """k slab contexts stepped like D.ThreadedGroup (one thread and one sph_step per rank), but with a per-rank environment set
+    before each ffi.Context (the options are read at sph_create) and a math policy set before or after sph_dist_configure.
+    step() takes one sph_params or one per rank and returns per rank the stats or the SphError."""
+
+    def __init__(self, lib, pos, mass, vel, planes, k, monkeypatch, env=None, policy=None, policy_first=True):
+        import ctypes as C
+        from concurrent.futures import ThreadPoolExecutor
+        self.lib = lib
+        self.group = C.c_void_p()
+        assert lib.thread_group_create(k, C.byref(self.group)) == 0
+        cuts = D.slab_cuts(pos[:, 0], k)
+        parts = D.partition(pos[:, 0], cuts)
+        self.contexts = []
+        try:
+            for r in range(k):
+                saved = {}
+                for name, val in ((env or {}).get(r) or {}).items():
+                    saved[name] = os.environ.get(name)
+                    monkeypatch.setenv(name, val)
+                c = ffi.Context(lib, D._slab_capacity(len(mass), k), planes)
+                for name, val in saved.items():
+                    if val is None:
+                        monkeypatch.delenv(name)
+                    else:
+                        monkeypatch.setenv(name, val)
+                self.contexts.append(c)
+                pol = policy[r] if isinstance(policy, (list, tuple)) else policy
+                if policy_first:
+                    _set_policy(c, pol)
+                c.dist_configure(r, k, cuts[r], cuts[r + 1])
+                c.comm_init_threads(self.group, r, k)
+                c.upload(mass[parts[r]], pos[parts[r]], vel[parts[r]])
+                c.upload_field("particle_id", parts[r].astype(np.uint32))
+                if not policy_first:
+                    _set_policy(c, pol)
+        except BaseException:
+            self.close()
+            raise
+        self.pool = ThreadPoolExecutor(k)
+
+    def step_each(self, p):
+        ps = p if isinstance(p, (list, tuple)) else [p] * len(self.contexts)
+        futs = [self.pool.submit(c.step, q) for c, q in zip(self.contexts, ps)]
+        out = []
+        for f in futs:
+            try:
+                out.append(f.result())
+            except ffi.SphError as e:
+                out.append(e)
+        return out
+
+    def step(self, p):
+        out = self.step_each(p)
+        errs = [e for e in out if isinstance(e, ffi.SphError)]
+        if errs:
+            raise errs[0]
+        return out
+
+    def close(self):
+        if getattr(self, "pool", None):
+            self.pool.shutdown(wait=True)
+        for c in self.contexts:
+            c.close()
+        self.contexts = []
+        if self.group:
+            self.lib.thread_group_destroy(self.group)
+            self.group = None
+
+
+def _loopback(lib, pos, mass, vel, planes, k, policy=None, policy_first=True):
+    cuts = D.slab_cuts(pos[:, 0], k)
+    parts = D.partition(pos[:, 0], cuts)
+    ctxs = []
+    for r in range(k):
+        c = ffi.Context(lib, D._slab_capacity(len(mass), k), planes)
+        pol = policy[r] if isinstance(policy, (list, tuple)) else policy
+        if policy_first:
+            _set_policy(c, pol)
+        c.dist_configure(r, k, cuts[r], cuts[r + 1])
+        c.upload(mass[parts[r]], pos[parts[r]], vel[parts[r]])
+        c.upload_field("particle_id", parts[r].astype(np.uint32))
+        if not policy_first:
+            _set_policy(c, pol)
+        ctxs.append(c)
+    return ctxs
+
+
+SLAB_FIELDS = ("particle_id", "position", "velocity", "density", "pressure", "neighbor_count")
+
+
+def _its(stats):
+    return [(float(x.dt), int(x.div_solver.iters), int(x.density_solver.iters)) for x in stats]
+
+
+def _assert_bitwise(got, ref):
+    for r, (a, b) in enumerate(zip(got, ref)):
+        assert a.n == b.n, r
+        for f in SLAB_FIELDS:
+            assert np.array_equal(a.download(f), b.download(f)), (r, f)
+
+
+@pytest.mark.parametrize("pattern", ["101", "010"])
+@pytest.mark.parametrize("solver", ["HybridDFSPH", "IISPH"])
+def test_ranks_that_split_sweep_a_differently_match_the_loopback_group(product_lib, monkeypatch, solver, pattern):
+    """split_sweep_a decides PER RANK (by slab size, or SPH_OVERLAP read at sph_create): slab counts that straddle
+    SPLIT_MIN_PARTICLES make a row in which some ranks run sweep A as interior + edge launches around the exchange and their
+    neighbours run the one-launch form.  The two forms must make the same collectives and the same arithmetic: ranks on threads
+    with SPH_OVERLAP set per context (pattern: 1 = split) against the loopback group, every field bit for bit; each rank's profile
+    shows the form it ran."""
+    monkeypatch.delenv("SPH_OVERLAP", raising=False)
+    pos, mass, vel, planes = _column()
+    p = dam_break_params(pressure_solver_method=solver).to_ffi()
+    split = [ch == "1" for ch in pattern]
+    loop = _loopback(product_lib, pos, mass, vel, planes, 3)
+    thr = _Ranks(product_lib, pos, mass, vel, planes, 3, monkeypatch, env={r: {"SPH_OVERLAP": "1" if s else "0"} for r, s in enumerate(split)})
+    try:
+        for c in thr.contexts:
+            c.profile_enable(1)
+        for s in range(12):
+            a, b = ffi.group_step(loop, p), thr.step(p)
+            assert _its(a) == _its(b), s
+        forms = []
+        for r, c in enumerate(thr.contexts):
+            prof = c.profile_get()
+            forms.append("split" if "pressure_accel_edge" in prof else "one launch")
+            assert ("pressure_accel_edge" in prof) == split[r] and "ghost_pack" in prof, (r, sorted(prof))
+        print(f"sweep A per rank: {forms}")
+        _assert_bitwise(thr.contexts, loop)
+    finally:
+        thr.close()
+        for c in loop:
+            c.close()
+
+
+@pytest.mark.parametrize("policy_first", [True, False], ids=["policy-then-configure", "configure-then-policy"])
+def test_exact_math_policy_on_slabs(product_lib, monkeypatch, policy_first):
+    """EXACT on a slab decomposition, with the policy set before and after sph_dist_configure: ranks on threads and the loopback group
+    all EXACT, bit for bit each other; the EXACT loopback group against an EXACT single context within the bars
+    test_loopback_group_matches_single_context holds FAST to; and the EXACT slab result differs from the FAST one -- the policy
+    reached every rank."""
+    monkeypatch.delenv("SPH_HIP_EXACT", raising=False)
+    pos, mass, vel, planes = _column()
+    p = forced(max_iters=4).to_ffi()
+    k = 3
+    single = ffi.Context(product_lib, len(mass), planes)
+    single.set_math_policy("exact")
+    single.upload(mass, pos, vel)
+    loop = _loopback(product_lib, pos, mass, vel, planes, k, "exact", policy_first)
+    fast = _loopback(product_lib, pos, mass, vel, planes, k, "fast", policy_first)
+    thr = _Ranks(product_lib, pos, mass, vel, planes, k, monkeypatch, policy="exact", policy_first=policy_first)
+    try:
+        assert all(c.math_policy() == "exact" for c in loop + thr.contexts)
+        for s in range(25):
+            st1 = single.step(p)
+            a, b = ffi.group_step(loop, p), thr.step(p)
+            ffi.group_step(fast, p)
+            assert _its(a) == _its(b), s
+            assert all(st.dt == st1.dt and st.div_solver.iters == st1.div_solver.iters for st in a), s
+            assert abs(int(a[0].div_solver.normal_count) - int(st1.div_solver.normal_count)) <= 8
+        _assert_bitwise(thr.contexts, loop)
+        n = len(mass)
+        for f, tol in (("position", 1e-5), ("velocity", 1e-4), ("density", 1e-5), ("mass", 0.0)):
+            assert rel_err(D.gather_by_id(loop, f, n), single.download(f)) <= tol, f
+        assert np.array_equal(D.gather_by_id(loop, "neighbor_count", n), single.download("neighbor_count"))
+        differ = [not np.array_equal(a.download("density"), b.download("density")) for a, b in zip(loop, fast)]
+        assert all(differ), differ                     # every rank computed under EXACT
+        assert all(c.math_policy() == "exact" for c in loop + thr.contexts)
+    finally:
+        thr.close()
+        for c in loop + fast:
+            c.close()
+        single.close()
+
+
+def _nudged(p, **kw):
+    """a copy of the sph_params struct `p` with some fields changed"""
+    q = type(p).from_buffer_copy(p)
+    for name, val in kw.items():
+        setattr(q, name, val)
+    return q
+
+
+def test_loopback_group_with_one_exact_member_is_refused(product_lib, monkeypatch):
+    """One member of a loopback group on the EXACT policy (sph_set_math_policy is per context): the group step is refused before
+    anything is launched -- status SPH_ERR_INVALID_ARGUMENT, the message names the math policy -- and nothing is poisoned: with the
+    member set back, the group steps and matches a group that never saw the refusal, bit for bit."""
+    monkeypatch.delenv("SPH_HIP_EXACT", raising=False)
+    pos, mass, vel, planes = _column()
+    p = dam_break_params().to_ffi()
+    grp = _loopback(product_lib, pos, mass, vel, planes, 3, ["fast", "exact", "fast"])
+    ref = _loopback(product_lib, pos, mass, vel, planes, 3)
+    try:
+        with pytest.raises(ffi.SphError) as e:
+            ffi.group_step(grp, p)
+        assert e.value.status == 1 and "math policy" in str(e.value), str(e.value)
+        grp[1].set_math_policy("fast")                 # (a poisoned context would refuse this)
+        for s in range(8):
+            assert _its(ffi.group_step(grp, p)) == _its(ffi.group_step(ref, p)), s
+        _assert_bitwise(grp, ref)
+    finally:
+        for c in grp + ref:
+            c.close()
+
+
+@pytest.mark.parametrize("case", ["max_iters", "max_dt one ulp", "math policy"])
+def test_ranks_on_threads_that_step_with_different_inputs_are_refused_together(product_lib, monkeypatch, case):
+    """Every rank passes its own sph_params and holds its own math policy.  A rank whose max_iters differs could leave a solve while its
+    neighbours wait in the next collective; one max_dt one ulp off or one EXACT rank would exchange ghost values of other arithmetic.
+    The step-start agreement refuses such a step on EVERY rank (status 1, the message names the input) before anything is launched;
+    nothing is poisoned, the transport stays usable: with the inputs agreed again the ranks step on and match a loopback group that
+    never saw the refusal, bit for bit."""
+    monkeypatch.delenv("SPH_HIP_EXACT", raising=False)
+    pos, mass, vel, planes = _column()
+    P = dam_break_params()
+    p = P.to_ffi()
+    ref = _loopback(product_lib, pos, mass, vel, planes, 3)
+    thr = _Ranks(product_lib, pos, mass, vel, planes, 3, monkeypatch)
+    try:
+        for s in range(3):
+            assert _its(thr.step(p)) == _its(ffi.group_step(ref, p)), s
+        ps = [p, p, p]
+        if case == "max_iters":
+            ps[1] = _nudged(p, max_iters=p.max_iters + 1)
+        elif case == "max_dt one ulp":
+            ps[2] = _nudged(p, max_dt=float(np.nextafter(np.float32(p.max_dt), np.float32(1))))
+            assert ps[2].max_dt != p.max_dt
+        else:
+            thr.contexts[0].set_math_policy("exact")
+        import time
+        t0 = time.perf_counter()
+        out = thr.step_each(ps)
+        assert time.perf_counter() - t0 < 30.0           # refused in the agreement, nobody waited out a collective
+        assert all(isinstance(o, ffi.SphError) and o.status == 1 for o in out), out
+        word = "math policy" if case == "math policy" else "sph_params"
+        assert all(word in str(o) for o in out), [str(o) for o in out]
+        if case == "math policy":
+            thr.contexts[0].set_math_policy("fast")      # (a poisoned context would refuse this)
+        for s in range(6):
+            assert _its(thr.step(p)) == _its(ffi.group_step(ref, p)), s
+        _assert_bitwise(thr.contexts, ref)
+    finally:
+        thr.close()
+        for c in ref:
+            c.close()
