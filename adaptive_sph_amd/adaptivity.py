@@ -149,6 +149,41 @@ def find_merge_partner_sequential(size_class, mass, level, position, h2, offsets
     return _find_partners("merge", size_class, mass, level, position, h2, offsets, indices, P, dt)
 
 
+def partner_candidates_reference(kind: str, size_class, mass, position, h2, offsets, indices, P: SimulationParams) -> Tuple[np.ndarray, np.ndarray]:
+    """The contract of sph_download_partner_candidates (include/sph_candidates.h) in numpy float32 on a full CSR: row i is empty
+    unless i is a donor of `kind` (share: Large, merge: TooSmall); a donor row keeps, in list order, every j != i that passes the two
+    tests of `_find_partners` that read nothing the loop writes -- the class test (particle_sharing.rs:50-58, particle_merging.rs:57-69)
+    and the distance test (particle_sharing.rs:61-65, particle_merging.rs:72-76), each f32 operation in the reference's order.
+    `_find_partners` on the result takes the decisions it takes on the full lists: both tests are idempotent, the rows keep their order."""
+    share = kind == "share"
+    size_class = np.asarray(size_class)
+    mass = np.asarray(mass, np.float32)
+    position = np.asarray(position, np.float32).reshape(-1, 2)
+    h2 = np.asarray(h2, np.float32)
+    offsets = np.asarray(offsets, np.int64)
+    indices = np.asarray(indices, np.uint32)
+    n = len(mass)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(offsets))
+    sel = np.nonzero(size_class[rows] == (LARGE if share else TOO_SMALL))[0]   # entries of donor rows
+    i, j = rows[sel], indices[sel].astype(np.int64)
+    keep = i != j
+    cj = size_class[j]
+    if share:
+        can = (cj == SMALL) | ((cj == TOO_SMALL) & bool(P.allow_share_with_too_small_particle)) | \
+              ((cj == OPTIMAL) & bool(P.allow_share_with_optimal_particle))
+    else:
+        can = (cj == SMALL) | (cj == TOO_SMALL) | ((cj == OPTIMAL) & bool(P.allow_merge_with_optimal_particle))
+        if P.allow_merge_on_size_difference:
+            can = can | (mass[j] > f32(5.0) * mass[i])
+    keep &= can
+    dx, dy = position[i, 0] - position[j, 0], position[i, 1] - position[j, 1]
+    max_dist = ((h2[i] + h2[j]) * f32(0.5)) * f32(P.max_share_distance if share else P.max_merge_distance)
+    keep &= ~(dx * dx + dy * dy > max_dist * max_dist)
+    out_off = np.zeros(n + 1, np.uint32)
+    out_off[1:] = np.cumsum(np.bincount(i[keep], minlength=n))
+    return out_off, np.ascontiguousarray(indices[sel][keep])
+
+
 def validate_partners(kind: str, size_class, merge_partner, merge_counter, offsets, indices) -> int:
     """validate_share_partners (particle_sharing.rs:119-150) / validate_merge_partners (particle_merging.rs:226-268)."""
     n = len(merge_counter)
@@ -206,14 +241,27 @@ class AdaptivityDriver:
     every step, merging on even step numbers, splitting on odd ones (`step_number` is FluidSimulation.step_number AFTER the step,
     :2725); mass is conserved to 0.005 (asserted like the reference).  The step's neighbour lists are read once and kept on the
     host across the passes, as the reference's NeighborhoodCache is: share_particles does not touch it, and the merge decision
-    that follows still iterates the lists of the step."""
+    that follows still iterates the lists of the step.
 
-    def __init__(self, ctx: ffi.Context, split_patterns: SplitPatterns = None, log=None):
+    `export`: what the host reads of the lists.  "lists" (default): every neighbour list, once per step (download_neighbors).
+    "candidates": per partner search, only the donors' neighbours that pass the search's class and distance tests, filtered on the
+    device (download_partner_candidates, include/sph_candidates.h); the same search then takes the same decisions on those rows, and
+    the two mass sums of the conservation check are reduced on the device (sum_mass)."""
+
+    EXPORTS = ("lists", "candidates")
+
+    def __init__(self, ctx: ffi.Context, split_patterns: SplitPatterns = None, log=None, export: str = "lists"):
+        if export not in self.EXPORTS:
+            raise ValueError(f"export must be one of {self.EXPORTS}, not {export!r}")
         self.ctx = ctx
         self.log = log
+        self.export = export
         self.host = ffi.HostBuffers()   # the exports land in the same host memory every step (round 6: the 26 ms "download" of configs[4]'s adaptive step were mostly page faults of fresh arrays)
         if ctx.n:
-            self.host.reserve(ctx.n)
+            if export == "candidates":
+                self.host.reserve(ctx.n, export="candidates")
+            else:
+                self.host.reserve(ctx.n)
         if split_patterns is not None:
             ctx.set_split_patterns(split_patterns.patterns)
 
@@ -222,8 +270,11 @@ class AdaptivityDriver:
         exports assembled in global index order, distributed.group_single_step_adaptivity)."""
         import time as _t
         ctx, log = self.ctx, self.log
+        candidates = self.export == "candidates"
+        if candidates and lists is not None:
+            raise ValueError("export=\"candidates\" filters the lists that live in the context: it cannot be combined with lists= (slab assembly)")
         p, ap = P.to_ffi(), adapt_params(P, dt)
-        info = {"n_before": ctx.n, "shares": 0, "merges": 0, "splits": 0}
+        info = {"n_before": ctx.n, "shares": 0, "merges": 0, "splits": 0, "export": self.export, "exported_indices": 0}
         # what the adaptive half of a step costs, by phase (bench.py reports it): device -> host of the lists and the five fields a
         # decision reads, the sequential partner searches on the host, the apply calls on the device
         tm = info["seconds"] = {"download": 0.0, "host_decide": 0.0, "apply": 0.0, "mass_check": 0.0}
@@ -235,20 +286,30 @@ class AdaptivityDriver:
         seq_sum = lambda a: float(np.sum(a, dtype=np.float64))   # noqa: E731
         t0 = _t.perf_counter()
         host = self.host
-        m1 = ctx.download("mass", host)
-        off, idx = lists if lists is not None else ctx.download_neighbors(host)   # the lists single_step_without_adaptivity left behind (self.neighs)
-        t1 = _t.perf_counter()
-        tm["download"] += t1 - t0
-        total_mass1 = seq_sum(m1)   # (before the next download of the masses overwrites the persistent buffer)
-        tm["mass_check"] += _t.perf_counter() - t1
+        off = idx = None
+        if candidates:
+            total_mass1 = ctx.sum_mass()
+            tm["mass_check"] += _t.perf_counter() - t0
+        else:
+            m1 = ctx.download("mass", host)
+            off, idx = lists if lists is not None else ctx.download_neighbors(host)   # the lists single_step_without_adaptivity left behind (self.neighs)
+            info["exported_indices"] += len(idx)
+            t1 = _t.perf_counter()
+            tm["download"] += t1 - t0
+            total_mass1 = seq_sum(m1)   # (before the next download of the masses overwrites the persistent buffer)
+            tm["mass_check"] += _t.perf_counter() - t1
 
         def decide(kind):
+            nonlocal off, idx
             ta = _t.perf_counter()
             ctx.classify(p)
             t0 = _t.perf_counter()
             tm["apply"] += t0 - ta   # (classify_particles on the device: the apply side's device work)
             cls = ctx.download("particle_size_class", host)
             fields = (cls, ctx.download("mass", host), ctx.download("level_estimation", host), ctx.download("position", host), ctx.download("h2", host))
+            if candidates:   # this search's rows: the step's lists (kept on the device across share_particles), the fields as they are now
+                off, idx = ctx.download_partner_candidates(kind, p, ap, host)
+                info["exported_indices"] += len(idx)
             t1 = _t.perf_counter()
             tm["download"] += t1 - t0
             try:
@@ -283,11 +344,15 @@ class AdaptivityDriver:
             apply(lambda: (ctx.classify(p), ctx.split_particles(p, ap)))
             info["splits"] = ctx.n - n0
         t0 = _t.perf_counter()
-        m2 = ctx.download("mass", host)
-        t1 = _t.perf_counter()
-        tm["download"] += t1 - t0
-        total_mass2 = seq_sum(m2)
-        tm["mass_check"] += _t.perf_counter() - t1
+        if candidates:
+            total_mass2 = ctx.sum_mass()
+            tm["mass_check"] += _t.perf_counter() - t0
+        else:
+            m2 = ctx.download("mass", host)
+            t1 = _t.perf_counter()
+            tm["download"] += t1 - t0
+            total_mass2 = seq_sum(m2)
+            tm["mass_check"] += _t.perf_counter() - t1
         if not abs(total_mass1 - total_mass2) <= 0.005:             # assert_ft_approx_eq(total_mass1, total_mass2, 0.005, "mass sum")
             raise AssertionError(f"mass sum: {total_mass1} vs {total_mass2}")
         info["n_after"] = ctx.n

@@ -412,6 +412,7 @@ extern "C" int sph_share_particles(sph_ctx* c, const sph_params* p, const sph_ad
 extern "C" int sph_merge_particles(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter)
 {
     ADAPT_CHECK(c, 1, partner, counter);
+    c->export_valid = false;   // (the candidate export's lists index the vector before the deletions: sph_candidates.hip)
     return transfer(c, p, ap, partner, counter, 1);
 }
 
@@ -431,6 +432,7 @@ extern "C" int sph_set_split_patterns(sph_ctx* c, uint32_t n_patterns, const flo
 extern "C" int sph_split_particles(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap)
 {
     ADAPT_CHECK(c, 2, nullptr, nullptr);
+    c->export_valid = false;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t n = (uint32_t)c->n;
     if (n == 0) return SPH_OK;

@@ -696,7 +696,7 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
-                     &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
+                     &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
     for (auto b : all) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);
@@ -740,6 +740,7 @@ extern "C" int sph_set_math_policy(sph_ctx* c, int policy)
         HIPCHK(c, c->wall_cnt.ensure(n));
     }
     c->grid_valid = false;
+    c->export_valid = false;
     c->ahead.valid = false;
     c->hdr_ahead = false;
     c->lists_after = false;
@@ -766,6 +767,8 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->inc_count_valid = false;   // ... and so does the incremental sort's last mover count (advisor r4)
     c->export_d_off.release();   // (the CSR export's device buffers: a host that re-uploads is not exporting every step)
     c->export_d_idx.release();
+    c->export_valid = false;
+    for (DevBuf* b : {&c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan}) b->release();
     c->have_level = false;
     c->have_reduced = false;
     c->lists_after = false;
@@ -986,6 +989,7 @@ extern "C" int sph_apply_edits(sph_ctx* c, const sph_edit_op* ops, uint64_t n_op
     if (!c || (n_ops && !ops)) return SPH_ERR_INVALID_ARGUMENT;
     if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
     HIPCHK(c, hipSetDevice(c->device));
+    c->export_valid = false;
     const uint32_t n_old = (uint32_t)c->n;
     // ---- resolve the script: which object sits at which index, and the last value written to each field of an object
     std::vector<uint32_t> at(n_old);
@@ -1098,6 +1102,7 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     c->dist.have_flags = false;   // (slab context: owned particles only, in row order; the next step selects new ghosts)
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
     c->grid_valid = false;   // lists, cell indices and per-step outputs belong to the vector before this call
+    c->export_valid = false;
     if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
     c->inc_count_valid = false;   // ... and so does the incremental sort's last mover count (advisor r4)
     c->have_level = false;
@@ -1119,6 +1124,7 @@ extern "C" int sph_upload_field(sph_ctx* c, int field, const void* src, uint64_t
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d cannot be uploaded", field);
     const uint32_t n = (uint32_t)c->n;
     c->hdr_ahead = false;   // the header computed at the end of the last step no longer describes the state
+    if (field == SPH_F_POSITION || field == SPH_F_MASS) c->export_valid = false;   // (the candidate export's lists: sph_candidates.hip)
     if (bytes != (uint64_t)n * r.elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d: size mismatch", field);
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
@@ -1520,6 +1526,45 @@ extern "C" int sph_download_neighbors(sph_ctx* c, uint32_t* offsets, uint32_t* i
                            c->lists_after_k, (const uint32_t*)nullptr);
     HIPCHK(c, hipMemcpyAsync(indices, d_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    c->export_valid = true;   // (sph_candidates.hip filters this CSR in place of building its own)
+    c->export_tot = tot;
+    return SPH_OK;
+}
+
+// The same CSR without the host: counts in host order, prefix sum on the device, fill.  Only the total crosses the bus.
+int export_lists_on_device(sph_ctx* c)
+{
+    const uint32_t n = (uint32_t)c->n;
+    hipStream_t s = c->stream;
+    DevBuf &d_off = c->export_d_off, &d_idx = c->export_d_idx;
+    c->export_valid = false;
+    HIPCHK(c, d_off.ensure(((size_t)n + 1) * 4));
+    HIPCHK(c, c->scratch.ensure((size_t)n * 4 + 4));
+    HIPCHK(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+    const bool ext = c->lists_after;
+    const dim3 grid((n + 255) / 256), blk(256);
+    if (n) {
+        if (!ext) hipLaunchKernelGGL(k_to_host_order, grid, blk, 0, s, n, (int)G_U32, c->orig[c->cur].as<uint32_t>(), (const void*)c->ncount.p, c->scratch.p);
+        else hipLaunchKernelGGL(k_ext_counts, grid, blk, 0, s, n, c->nl_ext.as<uint4>(), c->orig[c->cur].as<uint32_t>(), c->scratch.as<uint32_t>());
+    }
+    device_exclusive_scan_u32(s, c->scratch.as<uint32_t>(), d_off.as<uint32_t>(), n, c->cand_scan.as<uint32_t>(), d_off.as<uint32_t>() + n);
+    uint32_t tot = 0;
+    HIPCHK(c, hipMemcpyAsync(&tot, d_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, d_idx.ensure((size_t)tot * 4));
+    if (n && tot) {
+        if (!ext)
+            hipLaunchKernelGGL(k_fill_neighbors, grid, blk, 0, s, n, c->fgrid, TileP{c->tile_ts, c->tile_tsx, c->tile_tsy, c->tile_h.as<uint32_t>(), 0.f},
+                               c->cell_start.as<uint32_t>(), c->cxy.as<uint32_t>(), c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur ^ 1].as<float4>(),
+                               d_off.as<uint32_t>(), d_idx.as<uint32_t>(), 2.f, (const uint32_t*)nullptr);
+        else
+            hipLaunchKernelGGL(k_fill_neighbors, grid, blk, 0, s, n, c->fgrid,
+                               TileP{c->tile_ts, c->tile_tsx, c->tile_tsy, c->tile_h_ext.as<uint32_t>(), c->lists_after_slack}, c->cell_start.as<uint32_t>(),
+                               c->cxy.as<uint32_t>(), c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(), d_off.as<uint32_t>(), d_idx.as<uint32_t>(),
+                               c->lists_after_k, (const uint32_t*)nullptr);
+    }
+    c->export_valid = true;
+    c->export_tot = tot;
     return SPH_OK;
 }
 

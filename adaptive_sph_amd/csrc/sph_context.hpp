@@ -106,6 +106,13 @@ struct sph_ctx {
     std::vector<uint32_t> export_cnt, export_off;   // sph_download_neighbors: host staging of the counts / offsets, kept across calls
     DevBuf export_d_off, export_d_idx;              // ... and its device-side CSR (a 200 MB hipMalloc + hipFree per call otherwise); freed by sph_destroy and by sph_upload
 
+    // sph_candidates.hip: export_d_off / export_d_idx hold the CSR of the LAST STEP's lists (export_tot entries).  Set when either export
+    // built it, kept by sph_share_particles (it renumbers nothing: the merge search that follows still iterates the step's lists),
+    // cleared by whatever replaces the lists or the vector they index (step, upload, position / mass upload, edits, merge, split, policy)
+    bool export_valid = false;
+    uint64_t export_tot = 0;
+    DevBuf cand_rec, cand_cls, cand_cnt, cand_off, cand_idx, cand_scan, cand_red;   // host-order records / classes, counts, offsets, indices, scan and reduction scratch
+
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];
     int cur = 0;   // which of the (vel, orig, lvl, lvlold) ping-pong set is live
@@ -279,4 +286,7 @@ void launch_header(sph_ctx* c, uint32_t n, float rest_density, int from_mass, He
 void launch_publish(sph_ctx* c);
 void launch_profile_calibration(sph_ctx* c);   // Profiler mode 1: one spin kernel of known duration per step (sph_api.hip)
 void launch_check_neighborhood(sph_ctx* c, const SweepArgs& a);
+// The CSR of the last step's lists (the rows of sph_download_neighbors) into export_d_off / export_d_idx without a host copy of the
+// counts or the indices; sets export_valid / export_tot.  One context, grid_valid (sph_candidates.hip checks both).
+int export_lists_on_device(sph_ctx* c);
 void dist_release(sph_ctx* c);  // sph_step.hip

@@ -1943,6 +1943,7 @@ static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool*
         }
     }
     bool started = false;
+    for (auto c : G.m) c->export_valid = false;   // (sph_candidates.hip: the exported CSR holds the lists of the step before this one)
     const int rc = group_step_inner(G, p, outs, &started);
     if (rc && started)
         for (auto c : G.m) {

@@ -158,6 +158,10 @@ RENDER_MAX_STOPS = 16
 RENDER_SHOW_SURFACE, RENDER_SHOW_NEIGHBORHOOD_REDUCED, RENDER_FROM_STASH, RENDER_INTERPOLATE = 1, 2, 4, 8
 
 
+# include/sph_candidates.h: the partner searches' candidates filtered on the device + the device mass sum (product only)
+CANDIDATE_SYMBOLS = ["download_partner_candidates", "sum_mass"]
+
+
 class SphRenderParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("supersample", C.c_int32), ("zoom_out", C.c_float),
                 ("attribute", C.c_int32), ("flags", C.c_uint32), ("alpha", C.c_float), ("n_stops", C.c_int32),
@@ -192,14 +196,19 @@ class HostBuffers:
             self._bufs[key] = b
         return b[:need].view(dtype)
 
-    def reserve(self, n: int, neighbours_per_particle: int = 16):
+    def reserve(self, n: int, neighbours_per_particle: int = 16, export: str = "lists"):
         """Touch the buffers an adaptive step of `n` particles exports into (the five decision fields, the CSR lists, the partner arrays)
-        ahead of the first step -- what a host whose vectors exist from the start has anyway."""
+        ahead of the first step -- what a host whose vectors exist from the start has anyway.  `export="candidates"`: the filtered CSR of
+        Context.download_partner_candidates instead of the full lists (its indices: room for 4 per particle instead of 16, grown on demand)."""
         for name in ("particle_size_class", "mass", "level_estimation", "position", "h2"):
             fid, dt, w = FIELDS[name]
             self.view("field:" + name, dt, n * w)
-        self.view("csr:offsets", np.uint32, n + 1)
-        self.view("csr:indices", np.uint32, neighbours_per_particle * n)
+        if export == "candidates":
+            self.view("cand:offsets", np.uint32, n + 1)
+            self.view("cand:indices", np.uint32, 4 * n)
+        else:
+            self.view("csr:offsets", np.uint32, n + 1)
+            self.view("csr:indices", np.uint32, neighbours_per_particle * n)
         self.view("merge_partner", np.uint32, n)
         self.view("merge_counter", np.uint16, n)
 
@@ -282,6 +291,9 @@ class SphLibrary:
         self.render = sig("render", i32, [vp, C.POINTER(SphParams), rpp, vp, u64], required=False)
         self.render_colors = sig("render_colors", i32, [vp, C.POINTER(SphParams), rpp, vp, u64], required=False)
         self.render_snapshot = sig("render_snapshot", i32, [vp], required=False)
+        self.download_partner_candidates = sig("download_partner_candidates", i32, [vp, i32, C.POINTER(SphParams), ap, vp, vp, u64, C.POINTER(u64)],
+                                               required=False)
+        self.sum_mass = sig("sum_mass", i32, [vp, C.POINTER(C.c_double)], required=False)
 
 
 _PRODUCT = None
@@ -474,6 +486,46 @@ class Context:
 
     def split_particles(self, params: SphParams, ap: "SphAdaptParams") -> None:
         self._check(self.lib.split_particles(self.handle, C.byref(params), C.byref(ap)))
+
+    # ---- candidate export (include/sph_candidates.h) ----
+    def _candidate_lib(self):
+        if self.lib.download_partner_candidates is None or self.lib.sum_mass is None:
+            raise SphError(30, f"{self.lib.path.name} has no candidate export (sph_candidates.h is implemented by the product library only)")
+        return self.lib
+
+    def download_partner_candidates(self, kind, params: SphParams, ap: "SphAdaptParams", host: "HostBuffers" = None):
+        """sph_download_partner_candidates: CSR (offsets[n+1], indices) over all particles in host order whose donor rows hold the
+        neighbours that pass the class and the distance test of the `kind` ("share" / 0, "merge" / 1) search, in list order -- what
+        adaptivity.partner_candidates_reference computes from the full lists.  `host`: as in download_neighbors (persistent buffers
+        "cand:offsets" / "cand:indices", one library call unless the candidates outgrew them)."""
+        lib = self._candidate_lib()
+        kind = {"share": 0, "merge": 1}.get(kind, kind)
+        n = self.n
+        total = C.c_uint64(0)
+        pp = C.byref(params) if params is not None else None
+        app = C.byref(ap) if ap is not None else None
+        if host is None:
+            offsets = np.empty(n + 1, dtype=np.uint32)
+            self._check(lib.download_partner_candidates(self.handle, int(kind), pp, app, offsets.ctypes.data, None, 0, C.byref(total)))
+            indices = np.empty(int(total.value), dtype=np.uint32)
+            self._check(lib.download_partner_candidates(self.handle, int(kind), pp, app, offsets.ctypes.data, indices.ctypes.data if indices.size else None,
+                                                        indices.size, C.byref(total)))
+            return offsets, indices
+        offsets = host.view("cand:offsets", np.uint32, n + 1)
+        cap = max(host.capacity("cand:indices", np.uint32), 4 * n)
+        indices = host.view("cand:indices", np.uint32, cap)
+        rc = lib.download_partner_candidates(self.handle, int(kind), pp, app, offsets.ctypes.data, indices.ctypes.data, indices.size, C.byref(total))
+        if rc != 0 and int(total.value) > indices.size:   # the candidates outgrew the buffer: the total is known now
+            indices = host.view("cand:indices", np.uint32, int(total.value) + int(total.value) // 8)
+            rc = lib.download_partner_candidates(self.handle, int(kind), pp, app, offsets.ctypes.data, indices.ctypes.data, indices.size, C.byref(total))
+        self._check(rc)
+        return offsets, indices[: int(total.value)]
+
+    def sum_mass(self) -> float:
+        """sph_sum_mass: the f64 sum of the masses, reduced on the device in a fixed order."""
+        v = C.c_double(0.0)
+        self._check(self._candidate_lib().sum_mass(self.handle, C.byref(v)))
+        return float(v.value)
 
     # ---- frames (include/sph_render.h; adaptive_sph_amd/render.py builds the parameters) ----
     def _render_lib(self):

@@ -104,7 +104,11 @@ class FluidSimulation:
     """Drop-in for ``FluidSimulation<DimensionUtils2d, 2>`` on the step path."""
 
     def __init__(self, position, velocity, mass, planes, counters_enabled: bool = False,
-                 lib: Optional[ffi.SphLibrary] = None, device_id: int = 0, n_capacity: Optional[int] = None, split_patterns=None):
+                 lib: Optional[ffi.SphLibrary] = None, device_id: int = 0, n_capacity: Optional[int] = None, split_patterns=None,
+                 adaptivity_export: str = "lists"):
+        if adaptivity_export not in ("lists", "candidates"):
+            raise ValueError(f"adaptivity_export must be 'lists' or 'candidates', not {adaptivity_export!r}")
+        self.adaptivity_export = adaptivity_export   # what single_step_adaptivity reads of the neighbour lists (adaptivity.AdaptivityDriver)
         self.lib = lib if lib is not None else ffi.load_product()
         mass = np.ascontiguousarray(mass, dtype=np.float32)
         n = mass.shape[0]
@@ -168,7 +172,7 @@ class FluidSimulation:
             from .adaptivity import AdaptivityDriver
             if P.splitting and self.split_patterns is None:
                 raise RuntimeError("splitting needs split patterns: FluidSimulation(..., split_patterns=SplitPatterns.load_from_file('split-patterns.yaml'))")
-            self._adaptivity = AdaptivityDriver(self.ctx, self.split_patterns)
+            self._adaptivity = AdaptivityDriver(self.ctx, self.split_patterns, export=self.adaptivity_export)
         t0 = _time.perf_counter()
         info = self._adaptivity.single_step_adaptivity(P, dt, self.step_number)
         if self.counters_enabled:
@@ -222,13 +226,13 @@ def init_simulation_params(simulation_params: SimulationParams, scene_config: Sc
 
 def init_fluid_sim(simulation_params: SimulationParams, scene_config: SceneConfig, counters_enabled: bool = False,
                    lib: Optional[ffi.SphLibrary] = None, device_id: int = 0, split_patterns=None,
-                   n_capacity: Optional[int] = None) -> FluidSimulation:
+                   n_capacity: Optional[int] = None, adaptivity_export: str = "lists") -> FluidSimulation:
     """simulation.rs:3074-3231.  `n_capacity`: room for the particles splitting will add (the reference's Vecs grow on demand;
-    the device arrays are sized once)."""
+    the device arrays are sized once).  `adaptivity_export`: "lists" or "candidates" (adaptivity.AdaptivityDriver)."""
     pos, mass, vel = init_particles(scene_config)
     planes = boundary_planes(scene_config.boundary, simulation_params.init_boundary_handler)
     return FluidSimulation(pos, vel, mass, planes, counters_enabled, lib=lib, device_id=device_id, split_patterns=split_patterns,
-                           n_capacity=n_capacity)
+                           n_capacity=n_capacity, adaptivity_export=adaptivity_export)
 
 
 def run_until(fluid_simulation: FluidSimulation, simulation_params: SimulationParams, max_seconds: float,

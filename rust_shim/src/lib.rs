@@ -8,6 +8,8 @@
 //! `From<&SimulationParams>` a maintainer drops into the reference crate.
 #![allow(non_camel_case_types)]
 
+pub mod candidates;   // include/sph_candidates.h: the partner searches' candidates filtered on the device
+
 pub mod ffi {
     use std::os::raw::{c_char, c_int, c_void};
 
