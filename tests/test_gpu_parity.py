@@ -300,6 +300,7 @@ def test_replaying_step_lists_needs_recorded_lists(product_lib):
     P.use_extended_range_for_level_estimation = True
     g2.step(P.to_ffi())
     assert g2.download("neighbor_count").max() > 32
+    assert g2.profile_list_forms()["n_walk"] > 0      # the premise: lanes without a recorded list, which walk their candidates
 
 
 def test_center_diff_detector_after_advection(product_lib, oracle_lib):
@@ -555,7 +556,7 @@ def test_against_committed_fixtures(product_lib, name):
         assert rel_err(g.download(f), z[f]) < TOL.get(f, REL_TOL_FIELDS), f
 
 
-def test_error_codes_match_reference_guards(product_lib):
+def test_error_codes_match_reference_guards(product_lib, oracle_lib):
     scn = sc.dam_break_small(16, 16, 1 / 16)
     pos, mass, vel = sc.init_particles(scn)
     planes = sc.boundary_planes(scn.boundary)
@@ -565,7 +566,12 @@ def test_error_codes_match_reference_guards(product_lib):
     g.upload(mass, pos, bad)
     with pytest.raises(ffi.SphError) as e:
         g.step(dam_break_params().to_ffi())
-    assert e.value.status in (14, 15, 17, 18, 19)      # a NaN velocity trips one of the is_finite guards
+    assert e.value.status in (14, 15, 17, 18, 19)      # a NaN velocity trips one of the is_finite guards ...
+    o = ffi.Context(oracle_lib, len(mass), planes)
+    o.upload(mass, pos, bad)
+    with pytest.raises(ffi.SphError) as eo:
+        o.step(dam_break_params().to_ffi())
+    assert e.value.status == eo.value.status, (e.value, eo.value)   # ... the one the reference's step reaches first
     g.upload(mass, pos, vel)
     with pytest.raises(ffi.SphError) as e:
         g.step(dam_break_params(viscosity_type="XSPH").to_ffi())
