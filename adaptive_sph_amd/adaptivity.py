@@ -184,6 +184,44 @@ def partner_candidates_reference(kind: str, size_class, mass, position, h2, offs
     return out_off, np.ascontiguousarray(indices[sel][keep])
 
 
+def partner_problem_reference(kind: str, size_class, mass, level, position, h2, offsets, indices, P: SimulationParams):
+    """The contract of sph_download_partner_problem (include/sph_partner_problem.h) in numpy on a full CSR and the full fields: the
+    candidate rows of `partner_candidates_reference`, restricted to their PARTICIPANTS -- every donor whose row is not empty and every
+    j that occurs in a row -- and renumbered by rank in ascending host index.  Returns (ids, size_class, mass, level, position, h2,
+    offsets, indices): ids[K] the host indices, the five fields at ids, offsets[K + 1] / indices the participants' rows in compact
+    ids (rows and entries in their order; a participant that is no donor has an empty row).  `_find_partners` with n = K on it takes
+    the decisions it takes on the full lists: the renumbering is monotone, and everything the loop reads or writes belongs to a
+    participant (`expand_partner_decisions` maps them back)."""
+    coff, cidx = partner_candidates_reference(kind, size_class, mass, position, h2, offsets, indices, P)
+    n = len(coff) - 1
+    flag = np.zeros(n, bool)
+    flag[np.diff(coff.astype(np.int64)) > 0] = True
+    flag[cidx] = True
+    ids = np.nonzero(flag)[0].astype(np.uint32)
+    rank = np.cumsum(flag, dtype=np.int64) - flag          # exclusive scan of the flags
+    off_c = np.append(coff[ids], np.uint32(len(cidx))).astype(np.uint32)   # every row between two participants is empty
+    idx_c = rank[cidx].astype(np.uint32)
+    position = np.asarray(position, np.float32).reshape(-1, 2)
+    return (ids, np.asarray(size_class)[ids], np.asarray(mass, np.float32)[ids], np.asarray(level, np.float32)[ids], position[ids],
+            np.asarray(h2, np.float32)[ids], off_c, idx_c)
+
+
+def expand_partner_decisions(n: int, ids, mp_c, mc_c) -> Tuple[np.ndarray, np.ndarray]:
+    """The numpy twin of the expand kernel (sph_share_particles_compact / sph_merge_particles_compact): merge_partner / merge_counter of
+    the whole vector from the decisions on a compact problem -- AVAILABLE / 0 for everything that is no participant, a compact partner
+    id mapped through `ids`, the two sentinels left alone."""
+    ids = np.asarray(ids, np.int64)
+    mp_c = np.asarray(mp_c, np.uint32)
+    merge_partner = np.full(n, MERGE_PARTNER_AVAILABLE, np.uint32)
+    merge_counter = np.zeros(n, np.uint16)
+    sentinel = (mp_c == MERGE_PARTNER_AVAILABLE) | (mp_c == MERGE_PARTNER_DELETE)
+    mapped = mp_c.copy()
+    mapped[~sentinel] = ids[mp_c[~sentinel].astype(np.int64)]
+    merge_partner[ids] = mapped
+    merge_counter[ids] = np.asarray(mc_c, np.uint16)
+    return merge_partner, merge_counter
+
+
 def validate_partners(kind: str, size_class, merge_partner, merge_counter, offsets, indices) -> int:
     """validate_share_partners (particle_sharing.rs:119-150) / validate_merge_partners (particle_merging.rs:226-268)."""
     n = len(merge_counter)
@@ -246,9 +284,18 @@ class AdaptivityDriver:
     `export`: what the host reads of the lists.  "lists" (default): every neighbour list, once per step (download_neighbors).
     "candidates": per partner search, only the donors' neighbours that pass the search's class and distance tests, filtered on the
     device (download_partner_candidates, include/sph_candidates.h); the same search then takes the same decisions on those rows, and
-    the two mass sums of the conservation check are reduced on the device (sum_mass)."""
+    the two mass sums of the conservation check are reduced on the device (sum_mass).
+    "compact": per partner search, the problem of its K participants only -- the donors that have a candidate and the candidates,
+    renumbered 0..K-1 on the device with their five fields and their rows (download_partner_problem, include/sph_partner_problem.h);
+    the same search runs with n = K and its K decisions go back through share_particles_compact / merge_particles_compact.  No full
+    field and no list crosses the bus in this mode.
 
-    EXPORTS = ("lists", "candidates")
+    The returned info counts what crossed it: "exported_indices" (list or candidate entries), "participants" (the sum of K over the
+    passes; compact mode only, else 0), "bytes_down" / "bytes_up" (the payload arrays of the step's exports and applies, computed
+    from the counts: 4 B per index and offset, 21 B per particle or participant for the five fields, 6 B for the two partner
+    arrays, 8 B per device mass sum)."""
+
+    EXPORTS = ("lists", "candidates", "compact")
 
     def __init__(self, ctx: ffi.Context, split_patterns: SplitPatterns = None, log=None, export: str = "lists"):
         if export not in self.EXPORTS:
@@ -258,8 +305,8 @@ class AdaptivityDriver:
         self.export = export
         self.host = ffi.HostBuffers()   # the exports land in the same host memory every step (round 6: the 26 ms "download" of configs[4]'s adaptive step were mostly page faults of fresh arrays)
         if ctx.n:
-            if export == "candidates":
-                self.host.reserve(ctx.n, export="candidates")
+            if export in ("candidates", "compact"):
+                self.host.reserve(ctx.n, export=export)
             else:
                 self.host.reserve(ctx.n)
         if split_patterns is not None:
@@ -271,10 +318,12 @@ class AdaptivityDriver:
         import time as _t
         ctx, log = self.ctx, self.log
         candidates = self.export == "candidates"
-        if candidates and lists is not None:
-            raise ValueError("export=\"candidates\" filters the lists that live in the context: it cannot be combined with lists= (slab assembly)")
+        compact = self.export == "compact"
+        if (candidates or compact) and lists is not None:
+            raise ValueError(f"export=\"{self.export}\" filters the lists that live in the context: it cannot be combined with lists= (slab assembly)")
         p, ap = P.to_ffi(), adapt_params(P, dt)
-        info = {"n_before": ctx.n, "shares": 0, "merges": 0, "splits": 0, "export": self.export, "exported_indices": 0}
+        info = {"n_before": ctx.n, "shares": 0, "merges": 0, "splits": 0, "export": self.export, "exported_indices": 0, "participants": 0,
+                "bytes_down": 0, "bytes_up": 0}
         # what the adaptive half of a step costs, by phase (bench.py reports it): device -> host of the lists and the five fields a
         # decision reads, the sequential partner searches on the host, the apply calls on the device
         tm = info["seconds"] = {"download": 0.0, "host_decide": 0.0, "apply": 0.0, "mass_check": 0.0}
@@ -287,13 +336,15 @@ class AdaptivityDriver:
         t0 = _t.perf_counter()
         host = self.host
         off = idx = None
-        if candidates:
+        if candidates or compact:
             total_mass1 = ctx.sum_mass()
+            info["bytes_down"] += 8
             tm["mass_check"] += _t.perf_counter() - t0
         else:
             m1 = ctx.download("mass", host)
             off, idx = lists if lists is not None else ctx.download_neighbors(host)   # the lists single_step_without_adaptivity left behind (self.neighs)
             info["exported_indices"] += len(idx)
+            info["bytes_down"] += 4 * len(m1) + (0 if lists is not None else 4 * (len(off) + len(idx)))
             t1 = _t.perf_counter()
             tm["download"] += t1 - t0
             total_mass1 = seq_sum(m1)   # (before the next download of the masses overwrites the persistent buffer)
@@ -305,11 +356,22 @@ class AdaptivityDriver:
             ctx.classify(p)
             t0 = _t.perf_counter()
             tm["apply"] += t0 - ta   # (classify_particles on the device: the apply side's device work)
-            cls = ctx.download("particle_size_class", host)
-            fields = (cls, ctx.download("mass", host), ctx.download("level_estimation", host), ctx.download("position", host), ctx.download("h2", host))
+            if compact:   # this search's participants only: their fields as they are now, their rows of the step's lists in compact ids
+                _, *fields, off, idx = ctx.download_partner_problem(kind, p, ap, host)
+                cls = fields[0]
+                info["participants"] += len(cls)
+                info["exported_indices"] += len(idx)
+                info["bytes_down"] += 21 * len(cls) + 4 * (len(off) + len(idx))
+                info["bytes_up"] += 6 * len(cls)
+            else:
+                cls = ctx.download("particle_size_class", host)
+                fields = (cls, ctx.download("mass", host), ctx.download("level_estimation", host), ctx.download("position", host), ctx.download("h2", host))
+                info["bytes_down"] += 21 * len(cls)
+                info["bytes_up"] += 6 * len(cls)
             if candidates:   # this search's rows: the step's lists (kept on the device across share_particles), the fields as they are now
                 off, idx = ctx.download_partner_candidates(kind, p, ap, host)
                 info["exported_indices"] += len(idx)
+                info["bytes_down"] += 4 * (len(off) + len(idx))
             t1 = _t.perf_counter()
             tm["download"] += t1 - t0
             try:
@@ -326,29 +388,37 @@ class AdaptivityDriver:
             f(*a)
             tm["apply"] += _t.perf_counter() - t0
 
-        if P.sharing:
-            mp, mc = decide("share")
-            info["shares"] = int(mc.sum())
+        info["passes"] = []   # per partner search: its kind, n, what it moved and its share of the `seconds` buckets
+
+        def run_pass(kind, apply_f):
+            keys = ("participants", "exported_indices", "bytes_down", "bytes_up")
+            c0, t0, n0 = {k: info[k] for k in keys}, dict(tm), ctx.n
+            mp, mc = decide(kind)
+            events = int(mc.sum())
             if log:
-                log(f"SEQUENTIAL SHARE {info['shares']} shares")
-            apply(ctx.share_particles, p, ap, mp, mc)
+                log(f"SEQUENTIAL {kind.upper()} {events} {kind}s")
+            apply(apply_f, p, ap, mp, mc)
+            info["passes"].append({"kind": kind, "n": n0, "events": events, **{k: info[k] - c0[k] for k in keys},
+                                   "seconds": {k: tm[k] - t0[k] for k in ("download", "host_decide", "apply")}})
+            return events
+
+        if P.sharing:
+            info["shares"] = run_pass("share", ctx.share_particles_compact if compact else ctx.share_particles)
         if step_number % 2 == 0:
             if P.merging:
-                mp, mc = decide("merge")
-                info["merges"] = int(mc.sum())
-                if log:
-                    log(f"SEQUENTIAL MERGE {info['merges']} merges")
-                apply(ctx.merge_particles, p, ap, mp, mc)
+                info["merges"] = run_pass("merge", ctx.merge_particles_compact if compact else ctx.merge_particles)
         elif P.splitting:
             n0 = ctx.n
             apply(lambda: (ctx.classify(p), ctx.split_particles(p, ap)))
             info["splits"] = ctx.n - n0
         t0 = _t.perf_counter()
-        if candidates:
+        if candidates or compact:
             total_mass2 = ctx.sum_mass()
+            info["bytes_down"] += 8
             tm["mass_check"] += _t.perf_counter() - t0
         else:
             m2 = ctx.download("mass", host)
+            info["bytes_down"] += 4 * len(m2)
             t1 = _t.perf_counter()
             tm["download"] += t1 - t0
             total_mass2 = seq_sum(m2)

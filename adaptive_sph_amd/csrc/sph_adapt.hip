@@ -331,18 +331,30 @@ static int transfer(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap,
         if (partner[i] >= n && partner[i] != SPH_MERGE_PARTNER_AVAILABLE && partner[i] != SPH_MERGE_PARTNER_DELETE)
             return c->fail(SPH_ERR_INVALID_ARGUMENT, "merge_partner holds an index outside the particle vector (particle i=%u: %u)", i, partner[i]);
     hipStream_t s = c->stream;
+    TmpBuf d_partner, d_counter;
+    if (d_partner.ensure((size_t)n * 4) != hipSuccess || d_counter.ensure((size_t)n * 2) != hipSuccess) return c->fail(SPH_ERR_DEVICE, "out of device memory");
+    HIPCHK(c, hipMemcpyAsync(d_partner.p, partner, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_counter.p, counter, (size_t)n * 2, hipMemcpyHostToDevice, s));
+    return transfer_on_device(c, p, ap, d_partner.as<uint32_t>(), d_counter.as<uint16_t>(), merging);
+}
+
+// The receive / donate / delete path on merge_partner / merge_counter arrays that are on the device already (n > 0 entries each, queued
+// on the context's stream): what transfer() runs behind its two uploads, and what the compact apply of sph_partner_problem.hip runs
+// behind its expansion.  Returns after the stream has drained (check_status), so the caller may free the two arrays.
+int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, const uint32_t* d_partner_p, const uint16_t* d_counter_p, int merging)
+{
+    const uint32_t n = (uint32_t)c->n;
+    hipStream_t s = c->stream;
     const int k = c->cur;
-    TmpBuf d_partner, d_counter, d_slot, d_del, d_before, d_scratch, d_holes, d_src, d_sets;
+    TmpBuf d_slot, d_del, d_before, d_scratch, d_holes, d_src, d_sets;
     auto release = [&] {
-        for (TmpBuf* b : {&d_partner, &d_counter, &d_slot, &d_del, &d_before, &d_scratch, &d_holes, &d_src, &d_sets}) b->release();
+        for (TmpBuf* b : {&d_slot, &d_del, &d_before, &d_scratch, &d_holes, &d_src, &d_sets}) b->release();
     };
     auto guard = [&](hipError_t e) { return e == hipSuccess; };
-    if (!guard(d_partner.ensure((size_t)n * 4)) || !guard(d_counter.ensure((size_t)n * 2)) || !guard(d_slot.ensure((size_t)n * 4))) {
+    if (!guard(d_slot.ensure((size_t)n * 4))) {
         release();
         return c->fail(SPH_ERR_DEVICE, "out of device memory");
     }
-    HIPCHK(c, hipMemcpyAsync(d_partner.p, partner, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_counter.p, counter, (size_t)n * 2, hipMemcpyHostToDevice, s));
     const dim3 grid((n + 255) / 256), blk(256);
     const TargetP tp = target_params(p);
     const uint32_t min_partners = merging ? ap->minimum_merge_partners : ap->minimum_share_partners;
@@ -354,10 +366,10 @@ static int transfer(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap,
         }
     }
     hipLaunchKernelGGL(k_slot_of, grid, blk, 0, s, n, c->orig[k].as<uint32_t>(), d_slot.as<uint32_t>());
-    hipLaunchKernelGGL(k_transfer_receive, grid, blk, 0, s, n, merging, c->orig[k].as<uint32_t>(), d_slot.as<uint32_t>(), d_partner.as<uint32_t>(),
-                       d_counter.as<uint16_t>(), min_partners, ap->dt, ap->max_mass_transfer_sharing, tp, c->pm[c->pcur].as<float4>(), c->vel[k].as<float2>(),
+    hipLaunchKernelGGL(k_transfer_receive, grid, blk, 0, s, n, merging, c->orig[k].as<uint32_t>(), d_slot.as<uint32_t>(), d_partner_p,
+                       d_counter_p, min_partners, ap->dt, ap->max_mass_transfer_sharing, tp, c->pm[c->pcur].as<float4>(), c->vel[k].as<float2>(),
                        c->lvl[k].as<float>(), c->h2n[k].as<float>(), c->status.as<DeviceStatus>());
-    hipLaunchKernelGGL(k_transfer_donate, grid, blk, 0, s, n, merging, c->orig[k].as<uint32_t>(), d_partner.as<uint32_t>(), d_counter.as<uint16_t>(), min_partners,
+    hipLaunchKernelGGL(k_transfer_donate, grid, blk, 0, s, n, merging, c->orig[k].as<uint32_t>(), d_partner_p, d_counter_p, min_partners,
                        ap->dt, ap->max_mass_transfer_sharing, tp, c->pm[c->pcur].as<float4>(), c->lvl[k].as<float>(), c->h2n[k].as<float>(),
                        merging ? d_del.as<uint32_t>() : nullptr);
     int rc = check_status(c, "merge_partner holds an index outside the particle vector");

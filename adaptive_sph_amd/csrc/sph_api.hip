@@ -696,7 +696,8 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
-                     &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
+                     &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos,
+                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
     for (auto b : all) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);
@@ -769,6 +770,10 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->export_d_idx.release();
     c->export_valid = false;
     for (DevBuf* b : {&c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan}) b->release();
+    for (DevBuf* b : {&c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos, &c->prob_h2, &c->prob_off,
+                      &c->prob_idx})
+        b->release();
+    c->prob_open = false;
     c->have_level = false;
     c->have_reduced = false;
     c->lists_after = false;
@@ -1526,6 +1531,7 @@ extern "C" int sph_download_neighbors(sph_ctx* c, uint32_t* offsets, uint32_t* i
                            c->lists_after_k, (const uint32_t*)nullptr);
     HIPCHK(c, hipMemcpyAsync(indices, d_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    if (!c->export_valid) c->export_epoch++;   // (sph_partner_problem.hip: an open problem belongs to the lists it was made from)
     c->export_valid = true;   // (sph_candidates.hip filters this CSR in place of building its own)
     c->export_tot = tot;
     return SPH_OK;
@@ -1563,6 +1569,7 @@ int export_lists_on_device(sph_ctx* c)
                                c->cxy.as<uint32_t>(), c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(), d_off.as<uint32_t>(), d_idx.as<uint32_t>(),
                                c->lists_after_k, (const uint32_t*)nullptr);
     }
+    c->export_epoch++;
     c->export_valid = true;
     c->export_tot = tot;
     return SPH_OK;

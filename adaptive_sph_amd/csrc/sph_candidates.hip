@@ -21,16 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sph_candidates.h"
-#include "sph_context.hpp"
-
-struct CandP {
-    int share;             // kind == 0
-    uint32_t donor_class;  // Large (3) when sharing, TooSmall (0) when merging
-    float max_dist_factor;
-    int allow_optimal;     // allow_{share,merge}_with_optimal_particle
-    int allow_too_small;   // allow_share_with_too_small_particle
-    int allow_size_diff;   // allow_merge_on_size_difference
-};
+#include "sph_candidates.hpp"
 
 __global__ __launch_bounds__(256) void k_cand_gather(uint32_t n, const uint32_t* __restrict__ orig, const float4* __restrict__ pm,
                                                       const uint8_t* __restrict__ szc, float4* __restrict__ rec, uint8_t* __restrict__ cls)
@@ -89,11 +80,66 @@ __global__ __launch_bounds__(256) void k_cand_rows(uint32_t n, CandP q, const ui
     if (!FILL) cnt[i] = c;
 }
 
-static int refuse_common(sph_ctx* c, const char* what)
+int cand_refuse_common(sph_ctx* c, const char* what)
 {
     if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
     if (c->dist.on)
         return c->fail(SPH_ERR_UNSUPPORTED, "%s: a slab context holds a slab of the particles (assemble the full lists: sph_download_neighbors per rank)", what);
+    return SPH_OK;
+}
+
+CandP cand_params(int kind, const sph_adapt_params* ap)
+{
+    return CandP{kind == 0,
+                 kind == 0 ? 3u : 0u,
+                 kind == 0 ? ap->max_share_distance : ap->max_merge_distance,
+                 kind == 0 ? ap->allow_share_with_optimal_particle : ap->allow_merge_with_optimal_particle,
+                 ap->allow_share_with_too_small_particle,
+                 ap->allow_merge_on_size_difference};
+}
+
+int cand_need_lists(sph_ctx* c)
+{
+    if (c->export_valid) return SPH_OK;
+    if (!c->grid_valid) return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists of a step on the device: run a step first");
+    return export_lists_on_device(c);
+}
+
+int cand_count_rows(sph_ctx* c, const CandP& q, uint32_t* offsets_host, uint32_t* tot)
+{
+    const uint32_t n = (uint32_t)c->n;
+    hipStream_t s = c->stream;
+    HIPCHK(c, c->cand_rec.ensure((size_t)n * sizeof(float4)));
+    HIPCHK(c, c->cand_cls.ensure((size_t)n));
+    HIPCHK(c, c->cand_cnt.ensure((size_t)n * 4));
+    HIPCHK(c, c->cand_off.ensure(((size_t)n + 1) * 4));
+    HIPCHK(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+    const dim3 grid((n + 255) / 256), blk(256);
+    uint32_t* out_off = c->cand_off.as<uint32_t>();
+    {
+        ProfScope ps(&c->prof, "candidates_count", s);
+        hipLaunchKernelGGL(k_cand_gather, grid, blk, 0, s, n, c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(), c->szc[c->cur].as<uint8_t>(),
+                           c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>());
+        hipLaunchKernelGGL(k_cand_rows<false>, grid, blk, 0, s, n, q, c->export_d_off.as<uint32_t>(), c->export_d_idx.as<uint32_t>(), c->export_tot,
+                           c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>(), c->cand_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        device_exclusive_scan_u32(s, c->cand_cnt.as<uint32_t>(), out_off, n, c->cand_scan.as<uint32_t>(), out_off + n);
+    }
+    *tot = 0;
+    HIPCHK(c, hipMemcpyAsync(tot, out_off + n, 4, hipMemcpyDeviceToHost, s));
+    if (offsets_host) HIPCHK(c, hipMemcpyAsync(offsets_host, out_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return SPH_OK;
+}
+
+int cand_fill_rows(sph_ctx* c, const CandP& q, uint32_t tot)
+{
+    const uint32_t n = (uint32_t)c->n;
+    hipStream_t s = c->stream;
+    HIPCHK(c, c->cand_idx.ensure((size_t)tot * 4));
+    ProfScope ps(&c->prof, "candidates_fill", s);
+    hipLaunchKernelGGL(k_cand_rows<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, q, c->export_d_off.as<uint32_t>(), c->export_d_idx.as<uint32_t>(), c->export_tot,
+                       c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>(), (uint32_t*)nullptr, (const uint32_t*)c->cand_off.as<uint32_t>(),
+                       c->cand_idx.as<uint32_t>());
     return SPH_OK;
 }
 
@@ -104,57 +150,23 @@ extern "C" int sph_download_partner_candidates(sph_ctx* c, int kind, const sph_p
     if (n_indices) *n_indices = 0;
     if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_candidates: params and ap must be given");
     if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_candidates: kind %d is neither 0 (share) nor 1 (merge)", kind);
-    if (int rc = refuse_common(c, "sph_download_partner_candidates")) return rc;
+    if (int rc = cand_refuse_common(c, "sph_download_partner_candidates")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->export_valid) {
-        if (!c->grid_valid) return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists of a step on the device: run a step first");
-        if (int rc = export_lists_on_device(c)) return rc;
-    }
-    const uint32_t n = (uint32_t)c->n;
-    hipStream_t s = c->stream;
-    if (n == 0) {
+    if (int rc = cand_need_lists(c)) return rc;
+    if (c->n == 0) {
         if (offsets) offsets[0] = 0;
         return SPH_OK;
     }
-    HIPCHK(c, c->cand_rec.ensure((size_t)n * sizeof(float4)));
-    HIPCHK(c, c->cand_cls.ensure((size_t)n));
-    HIPCHK(c, c->cand_cnt.ensure((size_t)n * 4));
-    HIPCHK(c, c->cand_off.ensure(((size_t)n + 1) * 4));
-    HIPCHK(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
-    const CandP q{kind == 0,
-                  kind == 0 ? 3u : 0u,
-                  kind == 0 ? ap->max_share_distance : ap->max_merge_distance,
-                  kind == 0 ? ap->allow_share_with_optimal_particle : ap->allow_merge_with_optimal_particle,
-                  ap->allow_share_with_too_small_particle,
-                  ap->allow_merge_on_size_difference};
-    const dim3 grid((n + 255) / 256), blk(256);
-    const uint32_t* d_off = c->export_d_off.as<uint32_t>();
-    const uint32_t* d_idx = c->export_d_idx.as<uint32_t>();
-    uint32_t* out_off = c->cand_off.as<uint32_t>();
-    {
-        ProfScope ps(&c->prof, "candidates_count", s);
-        hipLaunchKernelGGL(k_cand_gather, grid, blk, 0, s, n, c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(), c->szc[c->cur].as<uint8_t>(),
-                           c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>());
-        hipLaunchKernelGGL(k_cand_rows<false>, grid, blk, 0, s, n, q, d_off, d_idx, c->export_tot, c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>(),
-                           c->cand_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        device_exclusive_scan_u32(s, c->cand_cnt.as<uint32_t>(), out_off, n, c->cand_scan.as<uint32_t>(), out_off + n);
-    }
+    const CandP q = cand_params(kind, ap);
     uint32_t tot = 0;
-    HIPCHK(c, hipMemcpyAsync(&tot, out_off + n, 4, hipMemcpyDeviceToHost, s));
-    if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, out_off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (int rc = cand_count_rows(c, q, offsets, &tot)) return rc;
     if (n_indices) *n_indices = tot;
     if (!indices) return SPH_OK;
     if (cap < tot) return c->fail(SPH_ERR_INVALID_ARGUMENT, "indices buffer too small");
     if (tot == 0) return SPH_OK;
-    HIPCHK(c, c->cand_idx.ensure((size_t)tot * 4));
-    {
-        ProfScope ps(&c->prof, "candidates_fill", s);
-        hipLaunchKernelGGL(k_cand_rows<true>, grid, blk, 0, s, n, q, d_off, d_idx, c->export_tot, c->cand_rec.as<float4>(), c->cand_cls.as<uint8_t>(),
-                           (uint32_t*)nullptr, (const uint32_t*)out_off, c->cand_idx.as<uint32_t>());
-    }
-    HIPCHK(c, hipMemcpyAsync(indices, c->cand_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    if (int rc = cand_fill_rows(c, q, tot)) return rc;
+    HIPCHK(c, hipMemcpyAsync(indices, c->cand_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
@@ -193,7 +205,7 @@ extern "C" int sph_sum_mass(sph_ctx* c, double* total)
 {
     if (!c || !total) return SPH_ERR_INVALID_ARGUMENT;
     *total = 0.0;
-    if (int rc = refuse_common(c, "sph_sum_mass")) return rc;
+    if (int rc = cand_refuse_common(c, "sph_sum_mass")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t n = (uint32_t)c->n;
     if (n == 0) return SPH_OK;

@@ -112,6 +112,14 @@ struct sph_ctx {
     bool export_valid = false;
     uint64_t export_tot = 0;
     DevBuf cand_rec, cand_cls, cand_cnt, cand_off, cand_idx, cand_scan, cand_red;   // host-order records / classes, counts, offsets, indices, scan and reduction scratch
+    // sph_partner_problem.hip: the compact partner problem.  export_epoch counts the times export_valid went from false to true, so
+    // "the lists are still those the problem was made from" is export_valid && prob_epoch == export_epoch without a hook in every
+    // call that drops the lists.  prob_ids[prob_k] (host indices, ascending) and prob_kind are the OPEN problem (prob_open).
+    uint64_t export_epoch = 0, prob_epoch = 0;
+    bool prob_open = false;
+    int prob_kind = 0;
+    uint32_t prob_k = 0;
+    DevBuf prob_flag, prob_rank, prob_lvl, prob_ids, prob_cls, prob_mass, prob_level, prob_pos, prob_h2, prob_off, prob_idx;
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];

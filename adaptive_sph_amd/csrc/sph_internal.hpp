@@ -345,3 +345,6 @@ struct sph_ctx;
 int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const EditSet* d_sets);
 // out[i] = sum of in[0 .. i) ; *total (device word) = sum of all.  scratch: >= (n / 2048 + 2) words
 void device_exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* scratch, uint32_t* total);
+// sph_adapt.hip: share (merging = 0) / merge (1) applied from partner / counter arrays that are on the device (sph_partner_problem.hip)
+int transfer_on_device(struct sph_ctx* c, const struct sph_params* p, const struct sph_adapt_params* ap, const uint32_t* d_partner, const uint16_t* d_counter,
+                       int merging);

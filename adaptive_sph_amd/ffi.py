@@ -161,6 +161,10 @@ RENDER_SHOW_SURFACE, RENDER_SHOW_NEIGHBORHOOD_REDUCED, RENDER_FROM_STASH, RENDER
 # include/sph_candidates.h: the partner searches' candidates filtered on the device + the device mass sum (product only)
 CANDIDATE_SYMBOLS = ["download_partner_candidates", "sum_mass"]
 
+# include/sph_partner_problem.h: the partner search as a compact problem of the donors and their candidates (product only)
+PROBLEM_SYMBOLS = ["download_partner_problem", "share_particles_compact", "merge_particles_compact"]
+PROBLEM_FIELDS = ("particle_size_class", "mass", "level_estimation", "position", "h2")   # the five decision fields, in the call's order
+
 
 class SphRenderParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("supersample", C.c_int32), ("zoom_out", C.c_float),
@@ -199,7 +203,14 @@ class HostBuffers:
     def reserve(self, n: int, neighbours_per_particle: int = 16, export: str = "lists"):
         """Touch the buffers an adaptive step of `n` particles exports into (the five decision fields, the CSR lists, the partner arrays)
         ahead of the first step -- what a host whose vectors exist from the start has anyway.  `export="candidates"`: the filtered CSR of
-        Context.download_partner_candidates instead of the full lists (its indices: room for 4 per particle instead of 16, grown on demand)."""
+        Context.download_partner_candidates instead of the full lists (its indices: room for 4 per particle instead of 16, grown on demand).
+        `export="compact"`: the "prob:*" buffers of Context.download_partner_problem only, sized for n participants and 4 n candidates --
+        the most a pass can need of the former (a cold first merge touches nearly every particle), grown on demand for the latter."""
+        if export == "compact":
+            self.reserve_problem(n, 4 * n)
+            self.view("merge_partner", np.uint32, n)
+            self.view("merge_counter", np.uint16, n)
+            return
         for name in ("particle_size_class", "mass", "level_estimation", "position", "h2"):
             fid, dt, w = FIELDS[name]
             self.view("field:" + name, dt, n * w)
@@ -211,6 +222,17 @@ class HostBuffers:
             self.view("csr:indices", np.uint32, neighbours_per_particle * n)
         self.view("merge_partner", np.uint32, n)
         self.view("merge_counter", np.uint16, n)
+
+
+    def reserve_problem(self, k: int, n_indices: int):
+        """The views Context.download_partner_problem fills for k participants and n_indices candidates (persistent, grown on demand)."""
+        out = {"ids": self.view("prob:ids", np.uint32, k)}
+        for name in PROBLEM_FIELDS:
+            fid, dt, w = FIELDS[name]
+            out[name] = self.view("prob:" + name, dt, k * w)
+        out["offsets"] = self.view("prob:offsets", np.uint32, k + 1)
+        out["indices"] = self.view("prob:indices", np.uint32, n_indices)
+        return out
 
 
 class SphLibrary:
@@ -294,6 +316,10 @@ class SphLibrary:
         self.download_partner_candidates = sig("download_partner_candidates", i32, [vp, i32, C.POINTER(SphParams), ap, vp, vp, u64, C.POINTER(u64)],
                                                required=False)
         self.sum_mass = sig("sum_mass", i32, [vp, C.POINTER(C.c_double)], required=False)
+        self.download_partner_problem = sig("download_partner_problem", i32, [vp, i32, C.POINTER(SphParams), ap, vp, vp, vp, vp, vp, vp, vp, u64, vp, u64,
+                                                                             C.POINTER(u64), C.POINTER(u64)], required=False)
+        self.share_particles_compact = sig("share_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
+        self.merge_particles_compact = sig("merge_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
 
 
 _PRODUCT = None
@@ -526,6 +552,68 @@ class Context:
         v = C.c_double(0.0)
         self._check(self._candidate_lib().sum_mass(self.handle, C.byref(v)))
         return float(v.value)
+
+    # ---- compact partner problem (include/sph_partner_problem.h) ----
+    def _problem_lib(self):
+        if any(getattr(self.lib, s, None) is None for s in PROBLEM_SYMBOLS):
+            raise SphError(30, f"{self.lib.path.name} has no compact partner problem (sph_partner_problem.h is implemented by the product library only)")
+        return self.lib
+
+    def download_partner_problem(self, kind, params: SphParams, ap: "SphAdaptParams", host: "HostBuffers" = None, want_ids: bool = False):
+        """sph_download_partner_problem: the `kind` ("share" / 0, "merge" / 1) search restricted to its K participants -- the donors with
+        a candidate and the candidates -- numbered in ascending host index: what adaptivity.partner_problem_reference computes from the
+        full lists and fields.  Returns (ids, size_class, mass, level_estimation, position, h2, offsets, indices) with K entries per field,
+        offsets[K + 1] and the indices in compact ids; ids (the host indices) is None unless `want_ids`.  The library keeps the problem
+        open for share_particles_compact / merge_particles_compact.  `host`: persistent "prob:*" buffers (views, overwritten by the next
+        call); one library call unless the problem outgrew them.  Without it: a sizing call, then the filling one."""
+        lib = self._problem_lib()
+        kind = int({"share": 0, "merge": 1}.get(kind, kind))
+        pp = C.byref(params) if params is not None else None
+        app = C.byref(ap) if ap is not None else None
+        k, tot = C.c_uint64(0), C.c_uint64(0)
+
+        def call(v, kcap):
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None   # noqa: E731
+            return lib.download_partner_problem(self.handle, kind, pp, app, ptr(v["ids"]) if want_ids else None, *[ptr(v[f]) for f in PROBLEM_FIELDS],
+                                                v["offsets"].ctypes.data, kcap, ptr(v["indices"]), v["indices"].size, C.byref(k), C.byref(tot))
+
+        if host is None:
+            self._check(lib.download_partner_problem(self.handle, kind, pp, app, None, None, None, None, None, None, None, 0, None, 0, C.byref(k), C.byref(tot)))
+            K, T = int(k.value), int(tot.value)
+            v = {"ids": np.empty(K, np.uint32), "offsets": np.empty(K + 1, np.uint32), "indices": np.empty(T, np.uint32)}
+            for name in PROBLEM_FIELDS:
+                fid, dt, w = FIELDS[name]
+                v[name] = np.empty(K * w, dt)
+            self._check(call(v, K))
+        else:
+            kcap = max(host.capacity("prob:ids", np.uint32), 1024)
+            v = host.reserve_problem(kcap, max(host.capacity("prob:indices", np.uint32), 4096))
+            rc = call(v, kcap)
+            if rc != 0 and (int(k.value) > kcap or int(tot.value) > v["indices"].size):   # the problem outgrew the buffers: both counts are known now
+                kcap = max(kcap, int(k.value) + int(k.value) // 8)
+                v = host.reserve_problem(kcap, max(v["indices"].size, int(tot.value) + int(tot.value) // 8))
+                rc = call(v, kcap)
+            self._check(rc)
+            K, T = int(k.value), int(tot.value)
+        return (v["ids"][:K] if want_ids else None, v["particle_size_class"][:K], v["mass"][:K], v["level_estimation"][:K],
+                v["position"][:2 * K].reshape(K, 2), v["h2"][:K], v["offsets"][:K + 1], v["indices"][:T])
+
+    def _compact_arrays(self, partner_c, counter_c):
+        mp = np.ascontiguousarray(partner_c, dtype=np.uint32)
+        mc = np.ascontiguousarray(counter_c, dtype=np.uint16)
+        if mp.shape != mc.shape or mp.ndim != 1:
+            raise ValueError("partner_c / counter_c must have one entry per participant")
+        return mp, mc
+
+    def share_particles_compact(self, params: SphParams, ap: "SphAdaptParams", partner_c, counter_c) -> None:
+        """sph_share_particles_compact: share_particles from the decisions on the open problem, in its compact numbering."""
+        mp, mc = self._compact_arrays(partner_c, counter_c)
+        self._check(self._problem_lib().share_particles_compact(self.handle, C.byref(params), C.byref(ap), len(mp), mp.ctypes.data, mc.ctypes.data))
+
+    def merge_particles_compact(self, params: SphParams, ap: "SphAdaptParams", partner_c, counter_c) -> None:
+        """sph_merge_particles_compact: merge_particles from the decisions on the open problem, in its compact numbering."""
+        mp, mc = self._compact_arrays(partner_c, counter_c)
+        self._check(self._problem_lib().merge_particles_compact(self.handle, C.byref(params), C.byref(ap), len(mp), mp.ctypes.data, mc.ctypes.data))
 
     # ---- frames (include/sph_render.h; adaptive_sph_amd/render.py builds the parameters) ----
     def _render_lib(self):

@@ -9,6 +9,7 @@
 #![allow(non_camel_case_types)]
 
 pub mod candidates;   // include/sph_candidates.h: the partner searches' candidates filtered on the device
+pub mod partner_problem;   // include/sph_partner_problem.h: the searches as a compact problem of their participants
 
 pub mod ffi {
     use std::os::raw::{c_char, c_int, c_void};

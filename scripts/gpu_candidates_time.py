@@ -1,13 +1,15 @@
-"""The adaptive half of configs[4]'s step with the full-list export against the candidate export (include/sph_candidates.h).
+"""The adaptive half of configs[4]'s step with the full-list export, the candidate export (include/sph_candidates.h) and the compact
+partner problem (include/sph_partner_problem.h).
 
 configs[4]'s scene and parameters exactly as bench.py's adaptivity leg builds them (adaptive_steps: ratio_stress_4m, EmptyAngle level
 estimation, merging / sharing / splitting, the sizing radii of the two blocks), a few adaptive steps per mode from the same start, ONE
-PROCESS PER MODE (fresh children of this script).  Writes <out-dir>/r8_candidates.json and a short r8_candidates.md: per mode the four
-`seconds` buckets of AdaptivityDriver, the exported indices per step, the bytes that crossed the bus, the candidate kernels' profiler
-times (from two further steps with the event profiler on: it perturbs dispatch, so those steps are not in the buckets) and the event
-counts, which must be equal between the modes.  The comparison is candidates against lists in this run on this device.
+PROCESS PER MODE AND REPEAT (fresh children of this script).  Writes <out-dir>/<name>.json and a short <name>.md: per mode the four
+`seconds` buckets of AdaptivityDriver, per partner search (pass) its participants, exported indices, bytes down / up and its share of
+the buckets, the kernels' profiler times (from two further steps with the event profiler on: it perturbs dispatch, so those steps are
+not in the buckets) and the event counts, which must be equal between the modes.  The comparison is between the modes in this run on
+this device; --repeats gives the run-to-run spread.
 
-    python scripts/gpu_candidates_time.py [--steps 4] [--warmup 2] [--out-dir profiles]
+    python scripts/gpu_candidates_time.py [--steps 2] [--warmup 2] [--repeats 2] [--out-dir profiles] [--name r9_compact_problem]
 """
 import argparse
 import json
@@ -18,7 +20,7 @@ from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
-MODES = ("lists", "candidates")
+MODES = ("lists", "candidates", "compact")
 
 
 def child(mode: str, steps: int, warmup: int) -> dict:
@@ -42,8 +44,10 @@ def child(mode: str, steps: int, warmup: int) -> dict:
         ctx.step(p)
     if mode == "lists":
         ctx.download_neighbors(drv.host)   # (as bench.py: one untimed export, the device-side CSR buffers exist from here on)
-    else:
+    elif mode == "candidates":
         ctx.download_partner_candidates("merge", p, drv_ap(P), drv.host)
+    else:
+        ctx.download_partner_problem("merge", p, drv_ap(P), drv.host)
     per_step = []
     for _ in range(steps):
         t0 = time.perf_counter()
@@ -51,14 +55,10 @@ def child(mode: str, steps: int, warmup: int) -> dict:
         t_step = time.perf_counter() - t0
         n = ctx.n
         info = drv.single_step_adaptivity(P, float(st.dt), int(st.step_number))
-        passes = int(P.sharing) + int(P.merging and int(st.step_number) % 2 == 0)
-        fields = passes * 21 * n                      # class (1) + mass, level, h2 (4 each) + position (8) per decision pass
-        if mode == "lists":
-            moved = fields + 4 * n + 4 * info["n_after"] + 4 * (n + 1) + 4 * info["exported_indices"]     # + the two mass vectors + the CSR
-        else:
-            moved = fields + passes * 4 * (n + 1) + 4 * info["exported_indices"] + 16                  # + a CSR per pass + two f64 sums
+        moved = info["bytes_down"]   # (the driver counts what its exports moved: adaptivity.AdaptivityDriver)
         per_step.append({"step_number": int(st.step_number), "n_before": n, "n_after": info["n_after"], "step_path_s": t_step,
                          "seconds": info["seconds"], "exported_indices": info["exported_indices"], "bytes_device_to_host": moved,
+                         "bytes_host_to_device": info["bytes_up"], "participants": info["participants"], "passes": info["passes"],
                          "events": {k: info[k] for k in ("shares", "merges", "splits")}})
     prof = {}
     ctx.profile_enable(1)
@@ -70,7 +70,7 @@ def child(mode: str, steps: int, warmup: int) -> dict:
         for k in prof_events:
             prof_events[k] += info[k]
     for name, (launches, ms) in ctx.profile_get().items():
-        if name in ("candidates_count", "candidates_fill", "sum_mass", "classify"):
+        if name in ("candidates_count", "candidates_fill", "problem_mark", "problem_pack", "problem_expand", "sum_mass", "classify"):
             prof[name] = {"scopes": launches, "total_ms": ms}
     ctx.profile_enable(0)
     out = {"mode": mode, "workload": desc, "particles": len(mass), "steps": steps, "warmup": warmup, "per_step": per_step,
@@ -90,46 +90,63 @@ def mean(rows, f):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=2, help="adaptive steps per mode (2: one odd step with a split, one even step with a merge)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=2, help="processes per mode: the spread between them is the run-to-run spread")
     ap.add_argument("--out-dir", default=str(REPO / "profiles"))
+    ap.add_argument("--name", default="r9_compact_problem")
     ap.add_argument("--child", choices=MODES, default=None)
-    ap.add_argument("--timeout", type=int, default=420, help="seconds per mode")
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per process")
     a = ap.parse_args()
     if a.child:
         print("RESULT " + json.dumps(child(a.child, a.steps, a.warmup)), flush=True)
         return 0
-    res = {}
-    for mode in MODES:   # one process per mode; a mode that fails ends the run (nothing more is started on the device)
-        r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child", mode, "--steps", str(a.steps), "--warmup", str(a.warmup)],
-                           capture_output=True, text=True, timeout=a.timeout)
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-            return r.returncode or 1
-        res[mode] = json.loads(line[-1][7:])
-    ev = {m: [s["events"] for s in res[m]["per_step"]] for m in MODES}
-    res["events_equal"] = ev["lists"] == ev["candidates"]
+    res = {m: [] for m in MODES}
+    for rep in range(a.repeats):
+        for mode in MODES:   # one process per mode and repeat; a process that fails ends the run (nothing more is started on the device)
+            r = subprocess.run([sys.executable, str(Path(__file__).resolve()), "--child", mode, "--steps", str(a.steps), "--warmup", str(a.warmup)],
+                               capture_output=True, text=True, timeout=a.timeout)
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+            if r.returncode != 0 or not line:
+                sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+                return r.returncode or 1
+            res[mode].append(json.loads(line[-1][7:]))
+            print(f"repeat {rep} {mode}: done", flush=True)
+    ev = {m: [[s["events"] for s in run["per_step"]] for run in res[m]] for m in MODES}
+    res["events_equal"] = all(e == ev["lists"][0] for m in MODES for e in ev[m])
     out = Path(a.out_dir)
     out.mkdir(parents=True, exist_ok=True)
-    (out / "r8_candidates.json").write_text(json.dumps(res, indent=1) + "\n")
-    L = ["# configs[4], adaptive half of the step: full-list export against candidate export", "",
-         f"{res['lists']['particles']} particles, {a.steps} adaptive steps per mode after {a.warmup} plain steps, one process per mode, same start.",
-         "Means per adaptive step; `seconds` buckets of `AdaptivityDriver` (host clock).", "",
-         "| mode | download ms | host_decide ms | apply ms | mass_check ms | exported indices | MB device -> host |", "|---|---|---|---|---|---|---|"]
+    (out / (a.name + ".json")).write_text(json.dumps(res, indent=1) + "\n")
+    first = res["lists"][0]
+    L = ["# configs[4], adaptive half of the step: full lists, candidate rows, compact partner problem", "",
+         f"{first['particles']} particles, {a.steps} adaptive steps per process after {a.warmup} plain steps, {a.repeats} processes per mode, same start.",
+         "`seconds` buckets of `AdaptivityDriver` (host clock), summed over the steps of a process; one column per repeat.", "",
+         "| mode | download ms | host_decide ms | apply ms | mass_check ms | total ms | MB down | MB up |", "|---|---|---|---|---|---|---|---|"]
+    reps = lambda f, m: " / ".join(f"{f(run):.2f}" for run in res[m])   # noqa: E731
     for m in MODES:
-        rows = res[m]["per_step"]
-        b = {k: 1e3 * mean(rows, lambda r, k=k: r["seconds"][k]) for k in ("download", "host_decide", "apply", "mass_check")}
-        L.append(f"| {m} | {b['download']:.2f} | {b['host_decide']:.2f} | {b['apply']:.2f} | {b['mass_check']:.2f} | "
-                 f"{mean(rows, lambda r: r['exported_indices']):.0f} | {mean(rows, lambda r: r['bytes_device_to_host']) / 1e6:.1f} |")
-    L += ["", "Per step (step number: events, exported indices):", ""]
+        cell = {k: reps(lambda run, k=k: 1e3 * sum(s["seconds"][k] for s in run["per_step"]), m) for k in ("download", "host_decide", "apply", "mass_check")}
+        total = reps(lambda run: 1e3 * sum(sum(s["seconds"].values()) for s in run["per_step"]), m)
+        rows = res[m][0]["per_step"]
+        L.append(f"| {m} | {cell['download']} | {cell['host_decide']} | {cell['apply']} | {cell['mass_check']} | {total} | "
+                 f"{sum(r['bytes_device_to_host'] for r in rows) / 1e6:.1f} | {sum(r['bytes_host_to_device'] for r in rows) / 1e6:.1f} |")
+    L += ["", "Per partner search (pass), first repeat's counts; ms = download + host_decide + apply of that pass, one value per repeat:", "",
+          "| mode | step | pass | n | participants | exported indices | bytes down | bytes up | events | download ms | host_decide ms | apply ms |",
+          "|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for m in MODES:
-        L.append(f"- {m}: " + "; ".join(f"{s['step_number']}: {s['events']}, {s['exported_indices']}" for s in res[m]["per_step"]))
-    L += ["", f"Event counts equal between the modes in every step: **{res['events_equal']}**.", "",
-          "Profiler scopes over two further adaptive steps (event profiler on, not part of the buckets above):", ""]
+        for si, srow in enumerate(res[m][0]["per_step"]):
+            for pi, ps in enumerate(srow["passes"]):
+                t = {k: " / ".join(f"{1e3 * run['per_step'][si]['passes'][pi]['seconds'][k]:.2f}" for run in res[m]) for k in ("download", "host_decide", "apply")}
+                L.append(f"| {m} | {srow['step_number']} | {ps['kind']} | {ps['n']} | {ps['participants']} | {ps['exported_indices']} | {ps['bytes_down']} | "
+                         f"{ps['bytes_up']} | {ps['events']} | {t['download']} | {t['host_decide']} | {t['apply']} |")
+    L += ["", "Events per step (first repeat):", ""]
     for m in MODES:
-        L.append(f"- {m}: " + (", ".join(f"{k} {v['total_ms']:.3f} ms in {v['scopes']} scopes" for k, v in sorted(res[m]["profiled_steps"]["scopes"].items())) or "none"))
-    (out / "r8_candidates.md").write_text("\n".join(L) + "\n")
+        L.append(f"- {m}: " + "; ".join(f"{s['step_number']}: {s['events']}" for s in res[m][0]["per_step"]))
+    tot = {k: sum(s["events"][k] for s in first["per_step"]) for k in ("shares", "merges", "splits")}
+    L += ["", f"Totals over the steps: {tot}.  Event counts equal between all modes and repeats in every step: **{res['events_equal']}**.", "",
+          "Profiler scopes over two further adaptive steps (event profiler on, not part of the buckets above; first repeat):", ""]
+    for m in MODES:
+        L.append(f"- {m}: " + (", ".join(f"{k} {v['total_ms']:.3f} ms in {v['scopes']} scopes" for k, v in sorted(res[m][0]["profiled_steps"]["scopes"].items())) or "none"))
+    (out / (a.name + ".md")).write_text("\n".join(L) + "\n")
     print("\n".join(L))
     return 0 if res["events_equal"] else 2
 
