@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "sph_context.hpp"
+#include "sph_rendezvous.hpp"   // RefreshCounts; the thread / shared-memory transports' protocol
 
 enum { RC_BAD = 12, RC_FAR = 13, RC_HL = 14, RC_HR = 15 };   // RC_HL / RC_HR: float bits of the largest h in the region of the left / right cut   // words of dist.counts: the fused refresh's "take the general path" flag being collected; "a migrant may need more than one hand-over"
 
@@ -39,12 +40,6 @@ struct FusedField {
     SolverCtrl* ctrl;
     const uint32_t* gate;
     int iter;
-};
-
-struct RefreshCounts {
-    uint32_t mig[2], halo[2];         // this rank: migrants to / halo members (that stay) towards [left, right]
-    uint32_t in_mig[2], in_halo[2];   // the neighbours': migrants for me / their halo members towards me, from [left, right]
-    float hreg[2], in_hreg[2];        // largest h among this rank's particles in the region of its [left, right] cut; the neighbours' figure for the same cut
 };
 
 struct Comm {

@@ -2,33 +2,28 @@
 //   LocalComm    k contexts of ONE process, device copies ordered by events (sph_group_step: the verification form, and what a
 //                single-process host drives several GPUs with)
 //   RcclComm     one rank per process, ncclSend / ncclRecv grouped per x-neighbour pair over its xGMI link, ncclAllReduce for scalars
-//   ThreadComm   all ranks in this process, one HOST THREAD per rank, collectives as rendezvous in host memory: the per-rank driver
-//                code with everything that would hang RCCL turned into an error
-//   ShmComm      the same protocol between PROCESSES of one node, rendezvous and staging in a POSIX shared-memory segment: the
-//                functional transport where RCCL cannot serve the launch (several ranks on one GPU), and the multi-process check
+//   RendezvousComm<ThreadGroup>   all ranks in this process, one HOST THREAD per rank, collectives as rendezvous in host memory: the
+//                per-rank driver code with everything that would hang RCCL turned into an error
+//   RendezvousComm<ShmSegment>    the same protocol between PROCESSES of one node, rendezvous and staging in a POSIX shared-memory
+//                segment: the functional transport where RCCL cannot serve the launch (several ranks on one GPU), and the multi-process check
+//                (the protocol itself, written once and free of HIP: sph_rendezvous.hpp)
+//   IpcComm      the shared-memory transport's host-value collectives, the exchanges and the solver totals pushed device to device
 // The reference has no counterpart (its only parallelism is rayon inside one process, concurrency.rs:110-204).
-#include <atomic>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <array>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
 #include <vector>
 
 #include <cerrno>
 #include <fcntl.h>
 #include <sys/mman.h>
-#include <time.h>
 #include <unistd.h>
 
-#include "sph_dist.hpp"
+#include "sph_dist.hpp"   // (with sph_rendezvous.hpp: the boards and the protocol of the thread / shared-memory transports)
 
 
 // counts_round (RCCL): out[0] = to_left, out[1] = to_right, out[2] = out[3] = 0 (received below), out[4] = status,
@@ -95,6 +90,31 @@ int Comm::allreduce_sum_u32_dev(Group& G, std::vector<uint32_t*>& bufs, size_t n
             HIPCHK(c, hipMemcpy(bufs[i] + o, rows[i].data(), len * 4, hipMemcpyHostToDevice));
         }
     }
+    return SPH_OK;
+}
+
+// A phase's class counts at `base` (and the "a migrant is far" word) reach counts_host; the status rule of the halo phase (base 4):
+// a non-zero class-3 count is a slab narrower than two ghost layers.  (After a wait on c's stream, c's device current.)
+static int read_class_counts(sph_ctx* c, int base, int* status, uint32_t* to_left, uint32_t* to_right)
+{
+    HIPCHK(c, hipMemcpy(c->dist.counts_host + base, c->dist.counts.as<uint32_t>() + base, 16, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->dist.counts_host + RC_FAR, c->dist.counts.as<uint32_t>() + RC_FAR, 4, hipMemcpyDeviceToHost));
+    *to_left = c->dist.counts_host[base + 1];
+    *to_right = c->dist.counts_host[base + 2];
+    if (status && base == 4 && c->dist.counts_host[base + 3] && *status < SPH_ERR_UNSUPPORTED) *status = SPH_ERR_UNSUPPORTED;
+    return SPH_OK;
+}
+// the fused refresh's seven words: this rank's half of a RefreshCounts, and "take the general path"
+static int read_refresh_counts(sph_ctx* c, RefreshCounts& o, int* fallback)
+{
+    uint32_t w[7];
+    HIPCHK(c, hipMemcpy(w, c->dist.counts.p, 28, hipMemcpyDeviceToHost));
+    o.halo[0] = w[0];
+    o.halo[1] = w[1];
+    o.mig[0] = w[2];
+    o.mig[1] = w[3];
+    if (w[4]) *fallback = 1;
+    memcpy(o.hreg, w + 5, 8);
     return SPH_OK;
 }
 
@@ -198,11 +218,7 @@ struct LocalComm : Comm {
         for (size_t i = 0; i < G.m.size(); i++) {
             sph_ctx* c = G.m[i];
             HIPCHK(c, hipSetDevice(c->device));
-            HIPCHK(c, hipMemcpy(c->dist.counts_host + base, c->dist.counts.as<uint32_t>() + base, 16, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(c->dist.counts_host + RC_FAR, c->dist.counts.as<uint32_t>() + RC_FAR, 4, hipMemcpyDeviceToHost));
-            tl[i] = c->dist.counts_host[base + 1];
-            tr[i] = c->dist.counts_host[base + 2];
-            if (status && base == 4 && c->dist.counts_host[base + 3] && *status < SPH_ERR_UNSUPPORTED) *status = SPH_ERR_UNSUPPORTED;
+            if ((rc = read_class_counts(c, base, status, &tl[i], &tr[i]))) return rc;
         }
         if (red) allreduce_min_f32(G, *red);
         return neighbour_counts(G, tl, tr, fl, fr, nullptr);
@@ -216,14 +232,7 @@ struct LocalComm : Comm {
         for (size_t i = 0; i < n; i++) {
             sph_ctx* c = G.m[i];
             HIPCHK(c, hipSetDevice(c->device));
-            uint32_t w[7];
-            HIPCHK(c, hipMemcpy(w, c->dist.counts.p, 28, hipMemcpyDeviceToHost));
-            rcs[i].halo[0] = w[0];
-            rcs[i].halo[1] = w[1];
-            rcs[i].mig[0] = w[2];
-            rcs[i].mig[1] = w[3];
-            if (w[4]) *fallback = 1;
-            memcpy(rcs[i].hreg, w + 5, 8);
+            if ((rc = read_refresh_counts(c, rcs[i], fallback))) return rc;
         }
         for (size_t i = 0; i < n; i++) {
             rcs[i].in_mig[0] = i > 0 ? rcs[i - 1].mig[1] : 0;
@@ -552,600 +561,153 @@ struct RcclComm : Comm {
     }
 };
 
-// ---- threads: one HOST THREAD per rank, all ranks in this process (and on whatever devices their contexts name) -----------------
-// The verification transport for the per-rank driver code: every rank runs sph_step on its own thread with a group of ONE member,
-// exactly as a rank of the RCCL transport does -- its own view of the counts, its own branches (an exchange only where it has
-// something to send or receive, ...) -- and the collectives are rendezvous in host memory.  A collective that not every rank
-// enters, or a send that no receive of the same size matches, is what would hang RCCL: here it is a time-out / an error message.
-struct ThreadGroup {
-    int n = 0;
-    std::mutex mu;
-    std::condition_variable cv;
-    int arrived = 0;
-    uint64_t gen = 0;
-    std::atomic<bool> broken{false};
-    // a ghost / migrant exchange is point to point, as ncclSend / ncclRecv are: rank r meets only the x-neighbours it sends to or
-    // receives from (a rank with nothing for either neighbour does not enter at all).  One channel per adjacent pair (r, r + 1).
-    struct PairChan {
-        std::mutex mu;
-        std::condition_variable cv;
-        int arrived = 0;
-        uint64_t gen = 0;
-        Xfer xf[2];   // [0] the lower rank's, [1] the upper rank's
-    };
-    std::unique_ptr<PairChan[]> pair;
-    std::vector<std::array<double, 6>> tot;
-    std::vector<std::vector<float>> f32rows;
-    std::vector<std::vector<uint32_t>> u32rows;
-    std::vector<int> i32vals;
-    std::vector<std::array<uint32_t, 8>> words;
-    std::vector<int> op;          // which collective each rank is in (a mismatch is reported, not waited out)
-    explicit ThreadGroup(int k) : n(k), pair(new PairChan[(size_t)std::max(k - 1, 1)]), tot(k), f32rows(k), u32rows(k), i32vals(k), words(k), op(k) {}
-    // the two ranks of a channel meet; false: the other one did not come (60 s) or somebody left with an error
-    bool pair_barrier(PairChan& ch)
-    {
-        std::unique_lock<std::mutex> lk(ch.mu);
-        if (broken) return false;
-        const uint64_t g = ch.gen;
-        if (++ch.arrived == 2) {
-            ch.arrived = 0;
-            ch.gen++;
-            ch.cv.notify_all();
-            return true;
-        }
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-        while (ch.gen == g && !broken) {
-            if (ch.cv.wait_until(lk, std::min(t_end, std::chrono::steady_clock::now() + std::chrono::milliseconds(50))) == std::cv_status::timeout &&
-                std::chrono::steady_clock::now() >= t_end) {
-                broken = true;
-                break;
-            }
-        }
-        if (broken) ch.cv.notify_all();
-        return ch.gen != g && !broken;
-    }
-    // all ranks meet; false: somebody did not come (60 s) or left with an error
-    bool barrier()
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (broken) return false;
-        const uint64_t g = gen;
-        if (++arrived == n) {
-            arrived = 0;
-            gen++;
-            cv.notify_all();
-            return true;
-        }
-        if (!cv.wait_for(lk, std::chrono::seconds(60), [&] { return gen != g || broken; })) broken = true;
-        if (broken) cv.notify_all();
-        return !broken;
-    }
-    void abandon()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            broken = true;
-            cv.notify_all();
-        }
-        for (int i = 0; i + 1 < n; i++) {   // (the pair waits poll `broken` every 50 ms as well)
-            std::lock_guard<std::mutex> lk(pair[(size_t)i].mu);
-            pair[(size_t)i].cv.notify_all();
-        }
-    }
-};
+// ---- threads and processes of one node: the collectives as rendezvous in host memory (the protocol: sph_rendezvous.hpp) ----------
+// Threads (ThreadGroup): the verification transport for the per-rank driver code: every rank runs sph_step on its own thread with a
+// group of ONE member, exactly as a rank of the RCCL transport does -- its own view of the counts, its own branches (an exchange only
+// where it has something to send or receive, ...).  A collective that not every rank enters, or a send that no receive of the same
+// size matches, is what would hang RCCL: here it is a time-out / an error message.
+// Processes (ShmSegment): every rank is a process of its own (launched like the RCCL form: one per GPU, or several on one GPU -- which
+// RCCL refuses, "Duplicate GPU detected"), the collectives are rendezvous on atomics in a segment all ranks map, ghost and migrant
+// records are staged through it (device -> segment by the sender, segment -> device by the receiver).  Host synchronous and PCIe-bound:
+// the functional transport for boxes where RCCL cannot serve the launch (bench.py --gpus 2 on a one-GPU box, CI), and the multi-process
+// check of the launcher glue -- never the fast path.  Same checks as the thread transport: a collective not entered by every rank (60 s),
+// ranks in different collectives, a send whose size no receive pairs with.
+// Here: what only the HIP side can do -- the waits on the rank's stream, the copies of counts, totals and the guard word between device
+// and host, the statistics, and (per board) how an exchange moves its payload.
+template <class Board>
+struct RendezvousComm : Comm {
+    using Rdv = Rendezvous<Board>;
+    static Board* board(sph_ctx* c);
+    static void abandon(sph_ctx* c);   // what a rank whose stream failed tells the others
+    // one side of an exchange: the sender stages its payload before the pair meets, the receiver takes it while the two are together
+    static int stage(sph_ctx* c, Rdv& R, const Xfer& x, int side);
+    static int take(sph_ctx* c, Rdv& R, const Xfer& x, int side);
 
-struct ThreadComm : Comm {
     bool host_collectives_wait() const override { return true; }
-    static ThreadGroup* grp(Group& G) { return (ThreadGroup*)G.m[0]->dist.tgroup; }
-    // publish -> everybody is there -> consume -> everybody is done (the slots may be overwritten again)
-    template <class Pub, class Con>
-    static int meet(Group& G, int opcode, Pub pub, Con con)
+    static int settle(sph_ctx* c)   // everything queued on the rank's stream is through
     {
-        sph_ctx* c = G.m[0];
-        ThreadGroup* g = grp(G);
-        const int r = c->dist.rank;
-        g->op[(size_t)r] = opcode;
-        pub(g, r);
-        if (!g->barrier()) return c->fail(SPH_ERR_DEVICE, "thread transport: a rank did not enter collective %d (it would hang over RCCL)", opcode);
-        int rc = SPH_OK;
-        for (int k = 0; k < g->n; k++)
-            if (g->op[(size_t)k] != opcode) rc = c->fail(SPH_ERR_DEVICE, "thread transport: rank %d is in collective %d, rank %d in %d", r, opcode, k, g->op[(size_t)k]);
-        if (!rc) rc = con(g, r);
-        if (!g->barrier() && !rc) rc = c->fail(SPH_ERR_DEVICE, "thread transport: a rank left collective %d early", opcode);
+        const int rc = wait_stream(c);
+        if (rc) abandon(c);
         return rc;
     }
-    int allreduce_min_f32(Group& G, std::vector<std::vector<float>>& rows) override
+    // f(R) with this rank's view of the board; a failure of the protocol becomes the context's error message
+    template <class F>
+    static int run(Group& G, F f)
     {
-        return meet(G, 1, [&](ThreadGroup* g, int r) { g->f32rows[(size_t)r] = rows[0]; },
-                    [&](ThreadGroup* g, int) {
-                        for (size_t k = 0; k < rows[0].size(); k++) {
-                            float v = rows[0][k];
-                            for (int q = 0; q < g->n; q++) {
-                                if (g->f32rows[(size_t)q].size() != rows[0].size()) return G.m[0]->fail(SPH_ERR_DEVICE, "thread transport: all-reduce sizes differ");
-                                v = fminf(v, g->f32rows[(size_t)q][k]);
-                            }
-                            rows[0][k] = v;
-                        }
-                        return (int)SPH_OK;
-                    });
+        sph_ctx* c = G.m[0];
+        Rdv R(*board(c), c->dist.rank);
+        const int rc = f(R);
+        return rc && !R.err.empty() ? c->fail(rc, "%s", R.err.c_str()) : rc;
     }
-    int allreduce_max_i32(Group& G, std::vector<int>& vals) override
-    {
-        return meet(G, 2, [&](ThreadGroup* g, int r) { g->i32vals[(size_t)r] = vals[0]; },
-                    [&](ThreadGroup* g, int) {
-                        int v = vals[0];
-                        for (int q = 0; q < g->n; q++) v = std::max(v, g->i32vals[(size_t)q]);
-                        vals[0] = v;
-                        return (int)SPH_OK;
-                    });
-    }
-    int allreduce_sum_u32(Group& G, std::vector<std::vector<uint32_t>>& rows) override
-    {
-        std::vector<uint32_t> mine = rows[0];
-        return meet(G, 3, [&](ThreadGroup* g, int r) { g->u32rows[(size_t)r] = mine; },
-                    [&](ThreadGroup* g, int) {
-                        for (size_t k = 0; k < rows[0].size(); k++) {
-                            uint32_t v = 0;
-                            for (int q = 0; q < g->n; q++) v += g->u32rows[(size_t)q][k];
-                            rows[0][k] = v;
-                        }
-                        return (int)SPH_OK;
-                    });
-    }
+    int allreduce_min_f32(Group& G, std::vector<std::vector<float>>& rows) override { return run(G, [&](Rdv& R) { return R.min_f32(rows[0].data(), rows[0].size()); }); }
+    int allreduce_max_i32(Group& G, std::vector<int>& vals) override { return run(G, [&](Rdv& R) { return R.max_i32(&vals[0]); }); }
+    int allreduce_sum_u32(Group& G, std::vector<std::vector<uint32_t>>& rows) override { return run(G, [&](Rdv& R) { return R.sum_u32(rows[0].data(), rows[0].size()); }); }
     int neighbour_counts(Group& G, const std::vector<uint32_t>& tl, const std::vector<uint32_t>& tr, std::vector<uint32_t>& fl,
                          std::vector<uint32_t>& fr, int* status) override
     {
-        return meet(G, 4, [&](ThreadGroup* g, int r) { g->words[(size_t)r] = {tl[0], tr[0], status ? (uint32_t)*status : 0u, 0, 0, 0, 0, 0}; },
-                    [&](ThreadGroup* g, int r) {
-                        fl[0] = r > 0 ? g->words[(size_t)r - 1][1] : 0;
-                        fr[0] = r + 1 < g->n ? g->words[(size_t)r + 1][0] : 0;
-                        if (status)
-                            for (int q = 0; q < g->n; q++) *status = std::max(*status, (int)g->words[(size_t)q][2]);
-                        return (int)SPH_OK;
-                    });
+        return run(G, [&](Rdv& R) { return R.neighbour_counts(tl[0], tr[0], &fl[0], &fr[0], status); });
     }
     int counts_round(Group& G, int base, std::vector<std::vector<float>>* red, int* status, std::vector<uint32_t>& tl, std::vector<uint32_t>& tr,
                      std::vector<uint32_t>& fl, std::vector<uint32_t>& fr) override
     {
         sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            grp(G)->abandon();
-            return rc;
-        }
-        HIPCHK(c, hipMemcpy(c->dist.counts_host + base, c->dist.counts.as<uint32_t>() + base, 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->dist.counts_host + RC_FAR, c->dist.counts.as<uint32_t>() + RC_FAR, 4, hipMemcpyDeviceToHost));
-        tl[0] = c->dist.counts_host[base + 1];
-        tr[0] = c->dist.counts_host[base + 2];
-        if (status && base == 4 && c->dist.counts_host[base + 3] && *status < SPH_ERR_UNSUPPORTED) *status = SPH_ERR_UNSUPPORTED;
+        int rc = settle(c);
+        if (rc || (rc = read_class_counts(c, base, status, &tl[0], &tr[0]))) return rc;
         if (red && (rc = allreduce_min_f32(G, *red))) return rc;
         return neighbour_counts(G, tl, tr, fl, fr, status);
     }
     int refresh_round(Group& G, std::vector<std::vector<float>>* red, int* status, int* fallback, std::vector<RefreshCounts>& rcs) override
     {
         sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            grp(G)->abandon();
-            return rc;
-        }
-        uint32_t w[7];
-        HIPCHK(c, hipMemcpy(w, c->dist.counts.p, 28, hipMemcpyDeviceToHost));
-        RefreshCounts& o = rcs[0];
-        o.halo[0] = w[0];
-        o.halo[1] = w[1];
-        o.mig[0] = w[2];
-        o.mig[1] = w[3];
-        if (w[4]) *fallback = 1;
-        memcpy(o.hreg, w + 5, 8);
-        rc = meet(G, 5, [&](ThreadGroup* g, int r) { g->words[(size_t)r] = {o.mig[0], o.halo[0], o.mig[1], o.halo[1], (uint32_t)*status, (uint32_t)*fallback, w[5], w[6]}; },
-                  [&](ThreadGroup* g, int r) {
-                      o.in_mig[0] = r > 0 ? g->words[(size_t)r - 1][2] : 0;
-                      o.in_halo[0] = r > 0 ? g->words[(size_t)r - 1][3] : 0;
-                      o.in_mig[1] = r + 1 < g->n ? g->words[(size_t)r + 1][0] : 0;
-                      o.in_halo[1] = r + 1 < g->n ? g->words[(size_t)r + 1][1] : 0;
-                      o.in_hreg[0] = o.in_hreg[1] = 0.f;
-                      if (r > 0) memcpy(&o.in_hreg[0], &g->words[(size_t)r - 1][7], 4);        // the left rank's figure for ITS right cut = my left one
-                      if (r + 1 < g->n) memcpy(&o.in_hreg[1], &g->words[(size_t)r + 1][6], 4);
-                      for (int q = 0; q < g->n; q++) {
-                          *status = std::max(*status, (int)g->words[(size_t)q][4]);
-                          if (g->words[(size_t)q][5]) *fallback = 1;
-                      }
-                      return (int)SPH_OK;
-                  });
-        if (rc) return rc;
+        int rc = settle(c);
+        if (rc || (rc = read_refresh_counts(c, rcs[0], fallback))) return rc;
+        if ((rc = run(G, [&](Rdv& R) { return R.refresh(rcs[0], status, fallback); }))) return rc;
         return red ? allreduce_min_f32(G, *red) : SPH_OK;
     }
     int exchange(Group& G, std::vector<Xfer>& x) override
     {
         sph_ctx* c = G.m[0];
-        ThreadGroup* g = grp(G);
-        const int r = c->dist.rank;
+        const Xfer& xf = x[0];
         c->dist.stat_exchanges++;
-        int rc = wait_stream(c);   // my staging buffers are packed
-        if (rc) {
-            g->abandon();
-            return rc;
-        }
-        // point to point, like the grouped ncclSend / ncclRecv of the RCCL transport: one rendezvous per x-neighbour this rank has
-        // something for or expects something from; RCCL pairs every send with a receive of the same size on the other side -- the
-        // same rule, checked; a neighbour that does not come is what would hang RCCL
-        for (int side = 0; side < 2; side++) {
-            const int nb = side == 0 ? r - 1 : r + 1;
-            if (nb < 0 || nb >= g->n) {
-                if (x[0].send_bytes[side] || x[0].recv_bytes[side]) return c->fail(SPH_ERR_DEVICE, "halo exchange across the outer edge of the slab row (rank %d)", r);
-                continue;
-            }
-            if (!x[0].send_bytes[side] && !x[0].recv_bytes[side]) continue;
-            ThreadGroup::PairChan& ch = g->pair[(size_t)std::min(r, nb)];
-            const int mine = r < nb ? 0 : 1;
-            {
-                std::lock_guard<std::mutex> lk(ch.mu);
-                ch.xf[mine] = x[0];
-            }
-            if (!g->pair_barrier(ch))
-                return c->fail(SPH_ERR_DEVICE, "thread transport: rank %d did not enter the exchange rank %d has %zu bytes to send to / %zu bytes to receive from it for (it would hang over RCCL)",
-                               nb, r, x[0].send_bytes[side], x[0].recv_bytes[side]);
-            const Xfer o = ch.xf[mine ^ 1];
-            const int oside = side ^ 1;   // my left neighbour's right side and vice versa
-            if (x[0].recv_bytes[side] != o.send_bytes[oside] || x[0].send_bytes[side] != o.recv_bytes[oside]) {
-                rc = c->fail(SPH_ERR_DEVICE, "halo exchange sizes of ranks %d and %d do not pair up (rank %d: send %zu recv %zu; rank %d: send %zu recv %zu)", r, nb, r,
-                             x[0].send_bytes[side], x[0].recv_bytes[side], nb, o.send_bytes[oside], o.recv_bytes[oside]);
-                g->abandon();
-                return rc;
-            }
-            c->dist.stat_bytes_sent += x[0].send_bytes[side];
-            c->dist.stat_bytes_recv += x[0].recv_bytes[side];
-            if (x[0].recv_bytes[side]) HIPCHK(c, hipMemcpyAsync(x[0].recv[side], o.send[oside], x[0].recv_bytes[side], hipMemcpyDefault, c->stream));
-            if ((rc = wait_stream(c))) {
-                g->abandon();
-                return rc;
-            }
-            // (the sender may reuse its staging buffer once both are past this)
-            if (!g->pair_barrier(ch)) return c->fail(SPH_ERR_DEVICE, "thread transport: rank %d left the exchange with rank %d early", nb, r);
-        }
-        return SPH_OK;
-    }
-    int allreduce_solver(Group& G, int slot) override
-    {
-        sph_ctx* c = G.m[0];
-        c->dist.stat_allreduces++;
-        int rc = wait_stream(c);
-        if (rc) {
-            grp(G)->abandon();
-            return rc;
-        }
-        std::array<double, 6> mine{};
-        HIPCHK(c, hipMemcpy(mine.data(), c->dist.solver_tot.as<double>() + 8 * slot, 48, hipMemcpyDeviceToHost));
-        return meet(G, 7 + slot, [&](ThreadGroup* g, int r) { g->tot[(size_t)r] = mine; },
-                    [&](ThreadGroup* g, int) -> int {
-                        double t[6] = {0, 0, 0, 0, 0, 0};
-                        for (int q = 0; q < g->n; q++)
-                            for (int k = 0; k < 6; k++) t[k] += g->tot[(size_t)q][k];   // (rank order: the same sum on every rank)
-                        HIPCHK(c, hipMemcpy(c->dist.solver_tot.as<double>() + 8 * slot, t, 48, hipMemcpyHostToDevice));
-                        return SPH_OK;
-                    });
-    }
-    int agree_guards_queued(Group& G) override
-    {
-        sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            grp(G)->abandon();
-            return rc;
-        }
-        uint32_t e = 0;
-        HIPCHK(c, hipMemcpy(&e, &c->status.as<DeviceStatus>()->error, 4, hipMemcpyDeviceToHost));
-        return meet(G, 9, [&](ThreadGroup* g, int r) { g->i32vals[(size_t)r] = (int)e; },
-                    [&](ThreadGroup* g, int) -> int {
-                        uint32_t m = 0;
-                        for (int q = 0; q < g->n; q++) m = std::max(m, (uint32_t)g->i32vals[(size_t)q]);
-                        HIPCHK(c, hipMemcpy(&c->ctrl.as<SolverCtrl>()->peer_error, &m, 4, hipMemcpyHostToDevice));
-                        return SPH_OK;
-                    });
-    }
-};
-
-
-// ---- processes of one node WITHOUT RCCL: rendezvous and staging in a POSIX shared-memory segment ---------------------------------
-// ThreadComm's protocol between PROCESSES: every rank is a process of its own (launched like the RCCL form: one per GPU, or several
-// on one GPU -- which RCCL refuses, "Duplicate GPU detected"), the collectives are rendezvous on atomics in a segment all ranks map,
-// ghost and migrant records are staged through it (device -> segment by the sender, segment -> device by the receiver).  Host
-// synchronous and PCIe-bound: the functional transport for boxes where RCCL cannot serve the launch (bench.py --gpus 2 on a one-GPU
-// box, CI), and the multi-process check of the launcher glue -- never the fast path.  Same checks as the thread transport: a collective
-// not entered by every rank (60 s), ranks in different collectives, a send whose size no receive pairs with.
-#define SHM_MAX_RANKS 16
-#define SHM_MAX_F32 16
-#define SHM_MAX_U32 4096
-struct ShmSegment {
-    uint32_t magic;   // written last by the creating rank
-    uint32_t n;
-    uint64_t bytes_per_side, total_bytes;
-    std::atomic<uint32_t> arrived, gen, broken;
-    struct Pair {
-        std::atomic<uint32_t> arrived, gen;
-        uint64_t send_bytes[2][2], recv_bytes[2][2];   // [who: 0 the lower rank, 1 the upper][side]
-    } pair[SHM_MAX_RANKS];
-    int32_t op[SHM_MAX_RANKS];
-    double tot[SHM_MAX_RANKS][8];
-    float f32rows[SHM_MAX_RANKS][SHM_MAX_F32];
-    uint32_t f32len[SHM_MAX_RANKS];
-    uint32_t u32rows[SHM_MAX_RANKS][SHM_MAX_U32];
-    uint32_t u32len[SHM_MAX_RANKS];
-    int32_t i32vals[SHM_MAX_RANKS];
-    uint32_t words[SHM_MAX_RANKS][8];
-    // followed by the outboxes: rank r, side s at payload() + (2 r + s) * bytes_per_side
-    uint8_t* outbox(int r, int side) { return reinterpret_cast<uint8_t*>(this) + ((sizeof(ShmSegment) + 4095) & ~(size_t)4095) + ((size_t)2 * r + side) * bytes_per_side; }
-    static size_t size_for(int n, uint64_t per_side) { return ((sizeof(ShmSegment) + 4095) & ~(size_t)4095) + (size_t)2 * n * per_side; }
-    static bool spin_until(std::atomic<uint32_t>& word, uint32_t old, std::atomic<uint32_t>& broken)
-    {
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-        for (uint32_t k = 0; word.load(std::memory_order_acquire) == old; k++) {
-            if (broken.load(std::memory_order_relaxed)) return false;
-            if ((k & 63u) == 63u) {
-                if (std::chrono::steady_clock::now() >= t_end) {
-                    broken.store(1u);
-                    return false;
-                }
-                struct timespec ts = {0, 20000};
-                nanosleep(&ts, nullptr);
-            }
-        }
-        return !broken.load(std::memory_order_relaxed);
-    }
-    bool barrier()
-    {
-        if (broken.load()) return false;
-        const uint32_t g = gen.load(std::memory_order_acquire);
-        if (arrived.fetch_add(1u, std::memory_order_acq_rel) + 1u == n) {
-            arrived.store(0u, std::memory_order_relaxed);
-            gen.fetch_add(1u, std::memory_order_release);
-            return true;
-        }
-        return spin_until(gen, g, broken);
-    }
-    bool pair_barrier(Pair& ch)
-    {
-        if (broken.load()) return false;
-        const uint32_t g = ch.gen.load(std::memory_order_acquire);
-        if (ch.arrived.fetch_add(1u, std::memory_order_acq_rel) + 1u == 2u) {
-            ch.arrived.store(0u, std::memory_order_relaxed);
-            ch.gen.fetch_add(1u, std::memory_order_release);
-            return true;
-        }
-        return spin_until(ch.gen, g, broken);
-    }
-};
-
-struct ShmComm : Comm {
-    bool host_collectives_wait() const override { return true; }
-    static ShmSegment* seg(Group& G) { return (ShmSegment*)G.m[0]->dist.shm; }
-    template <class Pub, class Con>
-    static int meet(Group& G, int opcode, Pub pub, Con con)
-    {
-        sph_ctx* c = G.m[0];
-        ShmSegment* g = seg(G);
-        const int r = c->dist.rank;
-        g->op[r] = opcode;
-        pub(g, r);
-        if (!g->barrier()) return c->fail(SPH_ERR_DEVICE, "shared-memory transport: a rank did not enter collective %d (it would hang over RCCL)", opcode);
-        int rc = SPH_OK;
-        for (int k = 0; k < (int)g->n; k++)
-            if (g->op[k] != opcode) rc = c->fail(SPH_ERR_DEVICE, "shared-memory transport: rank %d is in collective %d, rank %d in %d", r, opcode, k, g->op[k]);
-        if (!rc) rc = con(g, r);
-        if (!g->barrier() && !rc) rc = c->fail(SPH_ERR_DEVICE, "shared-memory transport: a rank left collective %d early", opcode);
-        return rc;
-    }
-    int allreduce_min_f32(Group& G, std::vector<std::vector<float>>& rows) override
-    {
-        const size_t len = rows[0].size();
-        if (len > SHM_MAX_F32) return G.m[0]->fail(SPH_ERR_INVALID_ARGUMENT, "shared-memory transport: all-reduce of %zu floats", len);
-        return meet(G, 1,
-                    [&](ShmSegment* g, int r) {
-                        g->f32len[r] = (uint32_t)len;
-                        memcpy(g->f32rows[r], rows[0].data(), len * 4);
-                    },
-                    [&](ShmSegment* g, int) {
-                        for (size_t k = 0; k < len; k++) {
-                            float v = rows[0][k];
-                            for (int q = 0; q < (int)g->n; q++) {
-                                if (g->f32len[q] != len) return G.m[0]->fail(SPH_ERR_DEVICE, "shared-memory transport: all-reduce sizes differ");
-                                v = fminf(v, g->f32rows[q][k]);
-                            }
-                            rows[0][k] = v;
-                        }
-                        return (int)SPH_OK;
-                    });
-    }
-    int allreduce_max_i32(Group& G, std::vector<int>& vals) override
-    {
-        return meet(G, 2, [&](ShmSegment* g, int r) { g->i32vals[r] = vals[0]; },
-                    [&](ShmSegment* g, int) {
-                        int v = vals[0];
-                        for (int q = 0; q < (int)g->n; q++) v = std::max(v, (int)g->i32vals[q]);
-                        vals[0] = v;
-                        return (int)SPH_OK;
-                    });
-    }
-    int allreduce_sum_u32(Group& G, std::vector<std::vector<uint32_t>>& rows) override
-    {
-        const size_t len = rows[0].size();
-        if (len > SHM_MAX_U32) return G.m[0]->fail(SPH_ERR_INVALID_ARGUMENT, "shared-memory transport: all-reduce of %zu words", len);
-        return meet(G, 3,
-                    [&](ShmSegment* g, int r) {
-                        g->u32len[r] = (uint32_t)len;
-                        memcpy(g->u32rows[r], rows[0].data(), len * 4);
-                    },
-                    [&](ShmSegment* g, int) {
-                        for (size_t k = 0; k < len; k++) {
-                            uint32_t v = 0;
-                            for (int q = 0; q < (int)g->n; q++) v += g->u32rows[q][k];
-                            rows[0][k] = v;
-                        }
-                        return (int)SPH_OK;
-                    });
-    }
-    int neighbour_counts(Group& G, const std::vector<uint32_t>& tl, const std::vector<uint32_t>& tr, std::vector<uint32_t>& fl,
-                         std::vector<uint32_t>& fr, int* status) override
-    {
-        return meet(G, 4,
-                    [&](ShmSegment* g, int r) {
-                        const uint32_t w[8] = {tl[0], tr[0], status ? (uint32_t)*status : 0u, 0, 0, 0, 0, 0};
-                        memcpy(g->words[r], w, sizeof w);
-                    },
-                    [&](ShmSegment* g, int r) {
-                        fl[0] = r > 0 ? g->words[r - 1][1] : 0;
-                        fr[0] = r + 1 < (int)g->n ? g->words[r + 1][0] : 0;
-                        if (status)
-                            for (int q = 0; q < (int)g->n; q++) *status = std::max(*status, (int)g->words[q][2]);
-                        return (int)SPH_OK;
-                    });
-    }
-    int counts_round(Group& G, int base, std::vector<std::vector<float>>* red, int* status, std::vector<uint32_t>& tl, std::vector<uint32_t>& tr,
-                     std::vector<uint32_t>& fl, std::vector<uint32_t>& fr) override
-    {
-        sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            comm_abandon(c);
-            return rc;
-        }
-        HIPCHK(c, hipMemcpy(c->dist.counts_host + base, c->dist.counts.as<uint32_t>() + base, 16, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->dist.counts_host + RC_FAR, c->dist.counts.as<uint32_t>() + RC_FAR, 4, hipMemcpyDeviceToHost));
-        tl[0] = c->dist.counts_host[base + 1];
-        tr[0] = c->dist.counts_host[base + 2];
-        if (status && base == 4 && c->dist.counts_host[base + 3] && *status < SPH_ERR_UNSUPPORTED) *status = SPH_ERR_UNSUPPORTED;
-        if (red && (rc = allreduce_min_f32(G, *red))) return rc;
-        return neighbour_counts(G, tl, tr, fl, fr, status);
-    }
-    int refresh_round(Group& G, std::vector<std::vector<float>>* red, int* status, int* fallback, std::vector<RefreshCounts>& rcs) override
-    {
-        sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            comm_abandon(c);
-            return rc;
-        }
-        uint32_t w[7];
-        HIPCHK(c, hipMemcpy(w, c->dist.counts.p, 28, hipMemcpyDeviceToHost));
-        RefreshCounts& o = rcs[0];
-        o.halo[0] = w[0];
-        o.halo[1] = w[1];
-        o.mig[0] = w[2];
-        o.mig[1] = w[3];
-        if (w[4]) *fallback = 1;
-        memcpy(o.hreg, w + 5, 8);
-        rc = meet(G, 5,
-                  [&](ShmSegment* g, int r) {
-                      const uint32_t v[8] = {o.mig[0], o.halo[0], o.mig[1], o.halo[1], (uint32_t)*status, (uint32_t)*fallback, w[5], w[6]};
-                      memcpy(g->words[r], v, sizeof v);
-                  },
-                  [&](ShmSegment* g, int r) {
-                      o.in_mig[0] = r > 0 ? g->words[r - 1][2] : 0;
-                      o.in_halo[0] = r > 0 ? g->words[r - 1][3] : 0;
-                      o.in_mig[1] = r + 1 < (int)g->n ? g->words[r + 1][0] : 0;
-                      o.in_halo[1] = r + 1 < (int)g->n ? g->words[r + 1][1] : 0;
-                      o.in_hreg[0] = o.in_hreg[1] = 0.f;
-                      if (r > 0) memcpy(&o.in_hreg[0], &g->words[r - 1][7], 4);
-                      if (r + 1 < (int)g->n) memcpy(&o.in_hreg[1], &g->words[r + 1][6], 4);
-                      for (int q = 0; q < (int)g->n; q++) {
-                          *status = std::max(*status, (int)g->words[q][4]);
-                          if (g->words[q][5]) *fallback = 1;
-                      }
-                      return (int)SPH_OK;
-                  });
+        int rc = settle(c);   // my staging buffers are packed
         if (rc) return rc;
-        return red ? allreduce_min_f32(G, *red) : SPH_OK;
-    }
-    int exchange(Group& G, std::vector<Xfer>& x) override
-    {
-        sph_ctx* c = G.m[0];
-        ShmSegment* g = seg(G);
-        const int r = c->dist.rank;
-        c->dist.stat_exchanges++;
-        int rc = wait_stream(c);   // my staging buffers are packed
-        if (rc) {
-            comm_abandon(c);
-            return rc;
-        }
-        for (int side = 0; side < 2; side++) {
-            const int nb = side == 0 ? r - 1 : r + 1;
-            if (nb < 0 || nb >= (int)g->n) {
-                if (x[0].send_bytes[side] || x[0].recv_bytes[side]) return c->fail(SPH_ERR_DEVICE, "halo exchange across the outer edge of the slab row (rank %d)", r);
-                continue;
+        return run(G, [&](Rdv& R) {
+            for (int side = 0; side < 2; side++) {
+                if ((rc = R.pair_side(side, xf.send_bytes, xf.recv_bytes)) == Rdv::SKIP) continue;
+                if (rc || (rc = stage(c, R, xf, side)) || (rc = R.pair_meet(side, xf.send_bytes, xf.recv_bytes))) return rc;
+                c->dist.stat_bytes_sent += xf.send_bytes[side];
+                c->dist.stat_bytes_recv += xf.recv_bytes[side];
+                if ((rc = take(c, R, xf, side)) || (rc = R.pair_leave(side))) return rc;
             }
-            if (!x[0].send_bytes[side] && !x[0].recv_bytes[side]) continue;
-            if (x[0].send_bytes[side] > g->bytes_per_side) {
-                comm_abandon(c);
-                return c->fail(SPH_ERR_CAPACITY, "shared-memory transport: a message of %zu bytes does not fit the %llu-byte outbox (sph_comm_init_shm bytes_per_side)",
-                               x[0].send_bytes[side], (unsigned long long)g->bytes_per_side);
-            }
-            ShmSegment::Pair& ch = g->pair[std::min(r, nb)];
-            const int mine = r < nb ? 0 : 1;
-            if (x[0].send_bytes[side]) HIPCHK(c, hipMemcpy(g->outbox(r, side), x[0].send[side], x[0].send_bytes[side], hipMemcpyDeviceToHost));
-            for (int sd = 0; sd < 2; sd++) {
-                ch.send_bytes[mine][sd] = x[0].send_bytes[sd];
-                ch.recv_bytes[mine][sd] = x[0].recv_bytes[sd];
-            }
-            if (!g->pair_barrier(ch))
-                return c->fail(SPH_ERR_DEVICE, "shared-memory transport: rank %d did not enter the exchange rank %d has %zu bytes to send to / %zu bytes to receive from it for (it would hang over RCCL)",
-                               nb, r, x[0].send_bytes[side], x[0].recv_bytes[side]);
-            const int oside = side ^ 1;   // my left neighbour's right side and vice versa
-            const uint64_t o_send = ch.send_bytes[mine ^ 1][oside], o_recv = ch.recv_bytes[mine ^ 1][oside];
-            if (x[0].recv_bytes[side] != o_send || x[0].send_bytes[side] != o_recv) {
-                rc = c->fail(SPH_ERR_DEVICE, "halo exchange sizes of ranks %d and %d do not pair up (rank %d: send %zu recv %zu; rank %d: send %llu recv %llu)", r, nb, r,
-                             x[0].send_bytes[side], x[0].recv_bytes[side], nb, (unsigned long long)o_send, (unsigned long long)o_recv);
-                comm_abandon(c);
-                return rc;
-            }
-            c->dist.stat_bytes_sent += x[0].send_bytes[side];
-            c->dist.stat_bytes_recv += x[0].recv_bytes[side];
-            if (x[0].recv_bytes[side]) HIPCHK(c, hipMemcpy(x[0].recv[side], g->outbox(nb, oside), x[0].recv_bytes[side], hipMemcpyHostToDevice));
-            // (the sender may reuse its outbox once both are past this)
-            if (!g->pair_barrier(ch)) return c->fail(SPH_ERR_DEVICE, "shared-memory transport: rank %d left the exchange with rank %d early", nb, r);
-        }
-        return SPH_OK;
+            return (int)SPH_OK;
+        });
     }
     int allreduce_solver(Group& G, int slot) override
     {
         sph_ctx* c = G.m[0];
         c->dist.stat_allreduces++;
-        int rc = wait_stream(c);
-        if (rc) {
-            comm_abandon(c);
-            return rc;
-        }
+        const int rc = settle(c);
+        if (rc) return rc;
+        double* tot = c->dist.solver_tot.as<double>() + 8 * slot;
         double mine[6];
-        HIPCHK(c, hipMemcpy(mine, c->dist.solver_tot.as<double>() + 8 * slot, 48, hipMemcpyDeviceToHost));
-        return meet(G, 7 + slot, [&](ShmSegment* g, int r) { memcpy(g->tot[r], mine, 48); },
-                    [&](ShmSegment* g, int) -> int {
-                        double t[6] = {0, 0, 0, 0, 0, 0};
-                        for (int q = 0; q < (int)g->n; q++)
-                            for (int k = 0; k < 6; k++) t[k] += g->tot[q][k];   // (rank order: the same sum on every rank)
-                        HIPCHK(c, hipMemcpy(c->dist.solver_tot.as<double>() + 8 * slot, t, 48, hipMemcpyHostToDevice));
-                        return SPH_OK;
-                    });
+        HIPCHK(c, hipMemcpy(mine, tot, 48, hipMemcpyDeviceToHost));
+        return run(G, [&](Rdv& R) {
+            return R.sum_f64x6(7 + slot, mine, [&](const double* t) -> int {
+                HIPCHK(c, hipMemcpy(tot, t, 48, hipMemcpyHostToDevice));
+                return SPH_OK;
+            });
+        });
     }
     int agree_guards_queued(Group& G) override
     {
         sph_ctx* c = G.m[0];
-        int rc = wait_stream(c);
-        if (rc) {
-            comm_abandon(c);
-            return rc;
-        }
+        const int rc = settle(c);
+        if (rc) return rc;
         uint32_t e = 0;
         HIPCHK(c, hipMemcpy(&e, &c->status.as<DeviceStatus>()->error, 4, hipMemcpyDeviceToHost));
-        return meet(G, 9, [&](ShmSegment* g, int r) { g->i32vals[r] = (int)e; },
-                    [&](ShmSegment* g, int) -> int {
-                        uint32_t m = 0;
-                        for (int q = 0; q < (int)g->n; q++) m = std::max(m, (uint32_t)g->i32vals[q]);
-                        HIPCHK(c, hipMemcpy(&c->ctrl.as<SolverCtrl>()->peer_error, &m, 4, hipMemcpyHostToDevice));
-                        return SPH_OK;
-                    });
+        return run(G, [&](Rdv& R) {
+            return R.max_guard(e, [&](uint32_t m) -> int {
+                HIPCHK(c, hipMemcpy(&c->ctrl.as<SolverCtrl>()->peer_error, &m, 4, hipMemcpyHostToDevice));
+                return SPH_OK;
+            });
+        });
     }
 };
 
+// threads: the sender's staging pointers travel through the pair channel, the receiver copies device to device on its own stream
+template <> ThreadGroup* RendezvousComm<ThreadGroup>::board(sph_ctx* c) { return (ThreadGroup*)c->dist.tgroup; }
+template <> void RendezvousComm<ThreadGroup>::abandon(sph_ctx* c) { board(c)->abandon(); }
+template <> int RendezvousComm<ThreadGroup>::stage(sph_ctx*, Rdv& R, const Xfer& x, int side)
+{
+    for (int sd = 0; sd < 2; sd++) R.b.pair[(size_t)R.lower(side)].send[R.who(side)][sd] = x.send[sd];
+    return SPH_OK;
+}
+template <> int RendezvousComm<ThreadGroup>::take(sph_ctx* c, Rdv& R, const Xfer& x, int side)
+{
+    const void* src = R.b.pair[(size_t)R.lower(side)].send[R.who(side) ^ 1][side ^ 1];   // my left neighbour's right side and vice versa
+    if (x.recv_bytes[side]) HIPCHK(c, hipMemcpyAsync(x.recv[side], src, x.recv_bytes[side], hipMemcpyDefault, c->stream));
+    return settle(c);
+}
+// processes: device -> my outbox in the segment by the sender, the neighbour's outbox -> device by the receiver
+template <> ShmSegment* RendezvousComm<ShmSegment>::board(sph_ctx* c) { return (ShmSegment*)c->dist.shm; }
+template <> void RendezvousComm<ShmSegment>::abandon(sph_ctx* c) { comm_abandon(c); }
+template <> int RendezvousComm<ShmSegment>::stage(sph_ctx* c, Rdv& R, const Xfer& x, int side)
+{
+    if (x.send_bytes[side] > R.b.bytes_per_side) {
+        comm_abandon(c);
+        return c->fail(SPH_ERR_CAPACITY, "shared-memory transport: a message of %zu bytes does not fit the %llu-byte outbox (sph_comm_init_shm bytes_per_side)",
+                       x.send_bytes[side], (unsigned long long)R.b.bytes_per_side);
+    }
+    if (x.send_bytes[side]) HIPCHK(c, hipMemcpy(R.b.outbox(R.r, side), x.send[side], x.send_bytes[side], hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+template <> int RendezvousComm<ShmSegment>::take(sph_ctx* c, Rdv& R, const Xfer& x, int side)
+{
+    if (x.recv_bytes[side]) HIPCHK(c, hipMemcpy(x.recv[side], R.b.outbox(R.neighbour(side), side ^ 1), x.recv_bytes[side], hipMemcpyHostToDevice));
+    return SPH_OK;
+}
+using ThreadComm = RendezvousComm<ThreadGroup>;
+using ShmComm = RendezvousComm<ShmSegment>;
 
 // ---- peer-mapped PUSH transport: the ranks of one node as processes, device to device --------
 // Every rank owns one device allocation -- its BOX: an inbox per x-neighbour side (two parities), a table of the ranks' solver totals
@@ -1336,6 +898,28 @@ __global__ __launch_bounds__(1024) void k_ipc_wait_unpack(IpcFusedWait f)
 
 struct IpcComm : ShmComm {
     static IpcState* st(sph_ctx* c) { return (IpcState*)c->dist.ipc; }
+    // the totals half of a round's push / wait arguments (Push: IpcPush or IpcFusedPush): my row goes into every rank's table of this
+    // slot and parity, then its flag; the wait adds the rows up in rank order
+    template <class Push>
+    static void fill_totals(sph_ctx* c, int slot, Push& ps, IpcWait& w)
+    {
+        IpcState* I = st(c);
+        const int r = c->dist.rank, nr = c->dist.nranks;
+        const uint32_t seq = ++I->tot_n[slot], parity = seq & 1u;
+        ps.tot = w.tot = c->dist.solver_tot.as<double>() + 8 * slot;
+        ps.tot_seq = w.tot_seq = seq;
+        ps.nr = w.nr = nr;
+        ps.self = w.self = r;
+        for (int q = 0; q < nr; q++) {
+            IpcBox* b = (IpcBox*)I->peer[q];
+            ps.tot_dst[q] = b->tot[slot][parity][r];
+            ps.tot_flag[q] = &b->tot_seq[slot][r];
+        }
+        IpcBox* me = (IpcBox*)I->mine;
+        w.tot_flag = me->tot_seq[slot];
+        w.table = &me->tot[slot][parity][0][0];
+        c->dist.stat_allreduces++;
+    }
     // (rank-local inputs: a rank may fuse while its x-neighbour does not -- the two forms share the sequence counters, the inbox layout and
     //  the totals table; tests/test_gpu_multiprocess.py mixes them through the laboratory's Options::ipc_fuse_max_bytes)
     bool can_fuse_iteration(Group& G, size_t bytes) override
@@ -1384,26 +968,7 @@ struct IpcComm : ShmComm {
             c->dist.stat_bytes_sent += (size_t)f.n_halo[side] * 4;
             c->dist.stat_bytes_recv += (size_t)f.n_ghost[side] * 4;
         }
-        {
-            const uint32_t seq = ++I->tot_n[slot], parity = seq & 1u;
-            ps.tot = c->dist.solver_tot.as<double>() + 8 * slot;
-            ps.tot_seq = seq;
-            ps.nr = nr;
-            ps.self = r;
-            for (int q = 0; q < nr; q++) {
-                IpcBox* b = (IpcBox*)I->peer[q];
-                ps.tot_dst[q] = b->tot[slot][parity][r];
-                ps.tot_flag[q] = &b->tot_seq[slot][r];
-            }
-            IpcBox* me = (IpcBox*)I->mine;
-            w.tot_flag = me->tot_seq[slot];
-            w.tot_seq = seq;
-            w.table = &me->tot[slot][parity][0][0];
-            w.tot = c->dist.solver_tot.as<double>() + 8 * slot;
-            w.nr = nr;
-            w.self = r;
-            c->dist.stat_allreduces++;
-        }
+        fill_totals(c, slot, ps, w);
         c->dist.stat_exchanges++;
         {
             ProfScope p1(&c->prof, "ipc_pack_push", c->stream);
@@ -1461,24 +1026,7 @@ struct IpcComm : ShmComm {
         }
         if (slot >= 0) {
             any = true;
-            const uint32_t seq = ++I->tot_n[slot], parity = seq & 1u;
-            ps.tot = c->dist.solver_tot.as<double>() + 8 * slot;
-            ps.tot_seq = seq;
-            ps.nr = nr;
-            ps.self = r;
-            for (int q = 0; q < nr; q++) {
-                IpcBox* b = (IpcBox*)I->peer[q];
-                ps.tot_dst[q] = b->tot[slot][parity][r];
-                ps.tot_flag[q] = &b->tot_seq[slot][r];
-            }
-            IpcBox* me = (IpcBox*)I->mine;
-            w.tot_flag = me->tot_seq[slot];
-            w.tot_seq = seq;
-            w.table = &me->tot[slot][parity][0][0];
-            w.tot = c->dist.solver_tot.as<double>() + 8 * slot;
-            w.nr = nr;
-            w.self = r;
-            c->dist.stat_allreduces++;
+            fill_totals(c, slot, ps, w);
         }
         if (!any) return SPH_OK;
         if (x) c->dist.stat_exchanges++;
@@ -1593,7 +1141,7 @@ void comm_describe(sph_ctx* c, uint32_t* transport, uint32_t* ranks)
 void comm_abandon(sph_ctx* c)
 {
     if (c->dist.tgroup) ((ThreadGroup*)c->dist.tgroup)->abandon();   // the other ranks' next collective reports it instead of waiting
-    if (c->dist.shm) ((ShmSegment*)c->dist.shm)->broken.store(1u);
+    if (c->dist.shm) ((ShmSegment*)c->dist.shm)->abandon();
 }
 
 
@@ -1667,14 +1215,8 @@ extern "C" int sph_comm_init_shm(sph_ctx* c, const char* name, int rank, int n_r
     close(fd);
     if (mem == MAP_FAILED) return c->fail(SPH_ERR_DEVICE, "mmap of %s (%zu bytes) failed: %s", name, total, strerror(errno));
     ShmSegment* g = (ShmSegment*)mem;
-    if (create) {
-        memset(mem, 0, sizeof(ShmSegment));   // (ftruncate zero-filled the rest)
-        g->n = (uint32_t)n_ranks;
-        g->bytes_per_side = bytes_per_side;
-        g->total_bytes = total;
-        std::atomic_thread_fence(std::memory_order_release);
-        g->magic = 0x53504853u;
-    } else if (g->magic != 0x53504853u || g->n != (uint32_t)n_ranks || g->bytes_per_side != bytes_per_side) {
+    if (create) ShmSegment::create(mem, n_ranks, bytes_per_side);   // (ftruncate zero-filled the outboxes)
+    else if (g->magic != ShmSegment::MAGIC || g->n != (uint32_t)n_ranks || g->bytes_per_side != bytes_per_side) {
         munmap(mem, total);
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s is not the segment of this launch (%d ranks, %llu bytes per side)", name, n_ranks, (unsigned long long)bytes_per_side);
     }
