@@ -718,6 +718,7 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
     c->n = n_new;
     c->dist.n_tot = n_new;
     c->dist.have_flags = false;
+    c->drop_slab_lists();   // (sph_slab_candidates.hip: the rows and slots of the vector before this call)
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
     c->grid_valid = false;
     if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;

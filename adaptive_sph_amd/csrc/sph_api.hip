@@ -697,7 +697,7 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
                      &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos,
-                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
+                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
     for (auto b : all) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);
@@ -742,6 +742,7 @@ extern "C" int sph_set_math_policy(sph_ctx* c, int policy)
     }
     c->grid_valid = false;
     c->export_valid = false;
+    c->drop_slab_lists();
     c->ahead.valid = false;
     c->hdr_ahead = false;
     c->lists_after = false;
@@ -769,6 +770,8 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->export_d_off.release();   // (the CSR export's device buffers: a host that re-uploads is not exporting every step)
     c->export_d_idx.release();
     c->export_valid = false;
+    c->drop_slab_lists();
+    for (DevBuf* b : {&c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx}) b->release();
     for (DevBuf* b : {&c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan}) b->release();
     for (DevBuf* b : {&c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos, &c->prob_h2, &c->prob_off,
                       &c->prob_idx})
@@ -995,6 +998,7 @@ extern "C" int sph_apply_edits(sph_ctx* c, const sph_edit_op* ops, uint64_t n_op
     if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
     HIPCHK(c, hipSetDevice(c->device));
     c->export_valid = false;
+    c->drop_slab_lists();
     const uint32_t n_old = (uint32_t)c->n;
     // ---- resolve the script: which object sits at which index, and the last value written to each field of an object
     std::vector<uint32_t> at(n_old);
@@ -1108,6 +1112,7 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
     c->grid_valid = false;   // lists, cell indices and per-step outputs belong to the vector before this call
     c->export_valid = false;
+    c->drop_slab_lists();
     if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
     c->inc_count_valid = false;   // ... and so does the incremental sort's last mover count (advisor r4)
     c->have_level = false;
@@ -1130,6 +1135,7 @@ extern "C" int sph_upload_field(sph_ctx* c, int field, const void* src, uint64_t
     const uint32_t n = (uint32_t)c->n;
     c->hdr_ahead = false;   // the header computed at the end of the last step no longer describes the state
     if (field == SPH_F_POSITION || field == SPH_F_MASS) c->export_valid = false;   // (the candidate export's lists: sph_candidates.hip)
+    if (field == SPH_F_POSITION || field == SPH_F_MASS || field == SPH_F_PARTICLE_ID) c->drop_slab_lists();   // (sph_slab_candidates.hip: its entries become ids)
     if (bytes != (uint64_t)n * r.elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d: size mismatch", field);
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
@@ -1572,6 +1578,92 @@ int export_lists_on_device(sph_ctx* c)
     c->export_epoch++;
     c->export_valid = true;
     c->export_tot = tot;
+    return SPH_OK;
+}
+
+// ... and on a SLAB context (sph_slab_candidates.hip): rows = the owned slots in slot order, entries = SLOT indices (the filter reads its
+// records in slot space and names a survivor by orig[slot] only when it writes it).  The rowmap is a scan over dist.owned, the counts
+// are read in slot order (ncount, or the low 16 bits of the extended lists' words), k_fill_neighbors runs as in sph_download_neighbors
+// with an identity array in place of orig.  Only the total crosses the bus.
+__global__ __launch_bounds__(256) void k_slab_owned_flags(uint32_t nt, const uint8_t* __restrict__ owned, uint32_t* __restrict__ flag, uint32_t* __restrict__ iota)
+{
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nt) return;
+    flag[s] = owned[s] ? 1u : 0u;
+    iota[s] = s;
+}
+// pos[s] = rank of slot s among the owned slots (in place: the rowmap k_fill_neighbors takes), row_slot / cnt by row; *total64 += the
+// counts (one atomic per wave): the offsets are a 32-bit scan, and a rank whose lists reach 2^32 entries must be refused, not wrapped
+__global__ __launch_bounds__(256) void k_slab_rowmap(uint32_t nt, uint32_t n_rows, const uint8_t* __restrict__ owned, uint32_t* __restrict__ pos,
+                                                      const uint32_t* __restrict__ ncount, const uint4* __restrict__ nl_ext, uint32_t* __restrict__ row_slot,
+                                                      uint32_t* __restrict__ cnt, unsigned long long* __restrict__ total64)
+{
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long c = 0;
+    if (s < nt) {
+        const uint32_t r = pos[s];
+        if (!owned[s] || r >= n_rows) pos[s] = 0xffffffffu;
+        else {
+            row_slot[r] = s;
+            c = nl_ext ? (nl_ext[s].w & 0xffffu) : ncount[s];
+            cnt[r] = (uint32_t)c;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(total64, c);
+}
+int slab_lists_on_device(sph_ctx* c)
+{
+    const uint32_t n = (uint32_t)c->n, nt = c->dist.n_tot;
+    hipStream_t s = c->stream;
+    c->drop_slab_lists();
+    TmpBuf d_iota, d_cnt, d_tot64;
+    HIPCHK(c, d_tot64.ensure(8));
+    HIPCHK(c, hipMemsetAsync(d_tot64.p, 0, 8, s));
+    DevBuf& d_map = c->slab_slot_row;   // (kept: the prepare writes the donors' class bytes by row through it)
+    HIPCHK(c, d_map.ensure((size_t)nt * 4 + 4));
+    HIPCHK(c, d_iota.ensure((size_t)nt * 4 + 4));
+    HIPCHK(c, d_cnt.ensure((size_t)n * 4 + 4));
+    HIPCHK(c, c->slab_row_slot.ensure((size_t)n * 4 + 4));
+    HIPCHK(c, c->slab_off.ensure(((size_t)n + 1) * 4));
+    HIPCHK(c, c->scratch.ensure((size_t)nt * 4 + 4));
+    HIPCHK(c, c->cand_scan.ensure(((size_t)nt / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+    const bool ext = c->lists_after;   // (as sph_download_neighbors: the extended lists of the ADVECTED positions)
+    uint32_t* off = c->slab_off.as<uint32_t>();
+    uint32_t tot[2] = {0, 0};   // owned slots, list entries
+    if (nt) {
+        const dim3 grid((nt + 255) / 256), blk(256);
+        hipLaunchKernelGGL(k_slab_owned_flags, grid, blk, 0, s, nt, c->dist.owned.as<uint8_t>(), c->scratch.as<uint32_t>(), d_iota.as<uint32_t>());
+        device_exclusive_scan_u32(s, c->scratch.as<uint32_t>(), d_map.as<uint32_t>(), nt, c->cand_scan.as<uint32_t>(), d_map.as<uint32_t>() + nt);
+        HIPCHK(c, hipMemcpyAsync(&tot[0], d_map.as<uint32_t>() + nt, 4, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_slab_rowmap, grid, blk, 0, s, nt, n, c->dist.owned.as<uint8_t>(), d_map.as<uint32_t>(), c->ncount.as<uint32_t>(),
+                           ext ? c->nl_ext.as<uint4>() : (const uint4*)nullptr, c->slab_row_slot.as<uint32_t>(), d_cnt.as<uint32_t>(), d_tot64.as<unsigned long long>());
+    }
+    unsigned long long tot64 = 0;
+    HIPCHK(c, hipMemcpyAsync(&tot64, d_tot64.p, 8, hipMemcpyDeviceToHost, s));
+    device_exclusive_scan_u32(s, d_cnt.as<uint32_t>(), off, n, c->cand_scan.as<uint32_t>(), off + n);
+    HIPCHK(c, hipMemcpyAsync(&tot[1], off + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (tot[0] != n) return c->fail(SPH_ERR_DEVICE, "owned-particle count mismatch");
+    if (tot64 >= (1ull << 32) || tot64 != tot[1])
+        return c->fail(SPH_ERR_CAPACITY, "%llu neighbour-list entries on rank %d do not fit the 32-bit CSR offsets", tot64, c->dist.rank);
+    HIPCHK(c, c->slab_idx.ensure((size_t)tot[1] * 4 + 4));
+    if (nt && tot[1]) {
+        const dim3 grid((nt + 255) / 256), blk(256);
+        if (!ext)
+            hipLaunchKernelGGL(k_fill_neighbors, grid, blk, 0, s, nt, c->fgrid, TileP{c->tile_ts, c->tile_tsx, c->tile_tsy, c->tile_h.as<uint32_t>(), 0.f},
+                               c->cell_start.as<uint32_t>(), c->cxy.as<uint32_t>(), (const uint32_t*)d_iota.as<uint32_t>(), c->pm[c->pcur ^ 1].as<float4>(), off,
+                               c->slab_idx.as<uint32_t>(), 2.f, (const uint32_t*)d_map.as<uint32_t>());
+        else
+            hipLaunchKernelGGL(k_fill_neighbors, grid, blk, 0, s, nt, c->fgrid,
+                               TileP{c->tile_ts, c->tile_tsx, c->tile_tsy, c->tile_h_ext.as<uint32_t>(), c->lists_after_slack}, c->cell_start.as<uint32_t>(),
+                               c->cxy.as<uint32_t>(), (const uint32_t*)d_iota.as<uint32_t>(), c->pm[c->pcur].as<float4>(), off, c->slab_idx.as<uint32_t>(),
+                               c->lists_after_k, (const uint32_t*)d_map.as<uint32_t>());
+        HIPCHK(c, hipStreamSynchronize(s));   // (the temporaries go with this scope)
+    }
+    c->slab_lists_valid = true;
+    c->slab_lists_rows = n;
+    c->slab_lists_tot = tot[1];
     return SPH_OK;
 }
 

@@ -34,21 +34,6 @@ __global__ __launch_bounds__(256) void k_cand_gather(uint32_t n, const uint32_t*
     cls[i] = szc[s];
 }
 
-// particle_sharing.rs:50-67 / particle_merging.rs:57-78 for the pair (i, j): true = j stays in row i
-__device__ __forceinline__ bool cand_pass(const CandP& q, const float4 Ai, uint32_t j, const float4* __restrict__ rec, const uint8_t* __restrict__ cls)
-{
-    const uint32_t cj = cls[j];
-    bool can;
-    if (q.share) can = cj == 1u || (cj == 0u && q.allow_too_small) || (cj == 2u && q.allow_optimal);
-    else can = cj == 1u || cj == 0u || (cj == 2u && q.allow_optimal);
-    if (!can && !(!q.share && q.allow_size_diff)) return false;   // (the record is read only where a test needs it)
-    const float4 Aj = rec[j];
-    if (!can && !(Aj.z > __fmul_rn(5.f, Ai.z))) return false;
-    const float dx = __fsub_rn(Ai.x, Aj.x), dy = __fsub_rn(Ai.y, Aj.y);
-    const float max_dist = __fmul_rn(__fmul_rn(__fadd_rn(Ai.w, Aj.w), 0.5f), q.max_dist_factor);
-    return !(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) > __fmul_rn(max_dist, max_dist));
-}
-
 // FILL = false: cnt[i] = candidates of row i.  FILL = true: the candidates at out_off[i] (out_off: the scanned counts).
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_cand_rows(uint32_t n, CandP q, const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx, uint64_t tot,
@@ -185,10 +170,12 @@ __device__ __forceinline__ double block_sum_f64(double v)
     return s_v[0];
 }
 
-__global__ __launch_bounds__(256) void k_sum_mass(uint32_t n, const float4* __restrict__ pm, double* __restrict__ partials)
+// (owned: a slab context's ownership bytes -- a ghost slot adds 0.0, the tree stays the same; nullptr on a plain context)
+__global__ __launch_bounds__(256) void k_sum_mass(uint32_t n, const float4* __restrict__ pm, const uint8_t* __restrict__ owned, double* __restrict__ partials)
 {
     double v = 0.0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)SUM_BLOCKS * 256) v += (double)pm[i].z;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)SUM_BLOCKS * 256)
+        if (!owned || owned[i]) v += (double)pm[i].z;
     const double t = block_sum_f64(v);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
@@ -201,23 +188,28 @@ __global__ __launch_bounds__(256) void k_sum_mass_final(const double* __restrict
     if (threadIdx.x == 0) *out = t;
 }
 
-extern "C" int sph_sum_mass(sph_ctx* c, double* total)
+int cand_sum_mass(sph_ctx* c, uint32_t n, const uint8_t* owned, double* total)
 {
-    if (!c || !total) return SPH_ERR_INVALID_ARGUMENT;
     *total = 0.0;
-    if (int rc = cand_refuse_common(c, "sph_sum_mass")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t n = (uint32_t)c->n;
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
     HIPCHK(c, c->cand_red.ensure((SUM_BLOCKS + 1) * sizeof(double)));
     double* d = c->cand_red.as<double>();
     {
         ProfScope ps(&c->prof, "sum_mass", s);
-        hipLaunchKernelGGL(k_sum_mass, dim3(SUM_BLOCKS), dim3(256), 0, s, n, c->pm[c->pcur].as<float4>(), d);
+        hipLaunchKernelGGL(k_sum_mass, dim3(SUM_BLOCKS), dim3(256), 0, s, n, c->pm[c->pcur].as<float4>(), owned, d);
         hipLaunchKernelGGL(k_sum_mass_final, dim3(1), dim3(256), 0, s, (const double*)d, d + SUM_BLOCKS);
     }
     HIPCHK(c, hipMemcpyAsync(total, d + SUM_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return SPH_OK;
+}
+
+extern "C" int sph_sum_mass(sph_ctx* c, double* total)
+{
+    if (!c || !total) return SPH_ERR_INVALID_ARGUMENT;
+    *total = 0.0;
+    if (int rc = cand_refuse_common(c, "sph_sum_mass")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return cand_sum_mass(c, (uint32_t)c->n, nullptr, total);
 }

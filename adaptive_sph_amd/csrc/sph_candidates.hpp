@@ -14,6 +14,22 @@ struct CandP {
 };
 CandP cand_params(int kind, const sph_adapt_params* ap);
 
+// particle_sharing.rs:50-67 / particle_merging.rs:57-78 for the pair (i, j): true = j stays in row i.  rec / cls: the {x, y, mass, h2}
+// records and class bytes in the index space of j (host order in sph_candidates.hip, slots in sph_slab_candidates.hip).
+__device__ __forceinline__ bool cand_pass(const CandP& q, const float4 Ai, uint32_t j, const float4* __restrict__ rec, const uint8_t* __restrict__ cls)
+{
+    const uint32_t cj = cls[j];
+    bool can;
+    if (q.share) can = cj == 1u || (cj == 0u && q.allow_too_small) || (cj == 2u && q.allow_optimal);
+    else can = cj == 1u || cj == 0u || (cj == 2u && q.allow_optimal);
+    if (!can && !(!q.share && q.allow_size_diff)) return false;   // (the record is read only where a test needs it)
+    const float4 Aj = rec[j];
+    if (!can && !(Aj.z > __fmul_rn(5.f, Ai.z))) return false;
+    const float dx = __fsub_rn(Ai.x, Aj.x), dy = __fsub_rn(Ai.y, Aj.y);
+    const float max_dist = __fmul_rn(__fmul_rn(__fadd_rn(Ai.w, Aj.w), 0.5f), q.max_dist_factor);
+    return !(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) > __fmul_rn(max_dist, max_dist));
+}
+
 // poisoned -> SPH_ERR_POISONED, a slab context -> SPH_ERR_UNSUPPORTED
 int cand_refuse_common(sph_ctx* c, const char* what);
 // the CSR of the last step's lists on the device (export_valid), built here if neither export has built it yet
@@ -23,3 +39,6 @@ int cand_need_lists(sph_ctx* c);
 int cand_count_rows(sph_ctx* c, const CandP& q, uint32_t* offsets_host, uint32_t* tot);
 // tot > 0, after cand_count_rows with the same q: the rows' entries into cand_idx[tot].  Queues the launch, does not wait.
 int cand_fill_rows(sph_ctx* c, const CandP& q, uint32_t tot);
+// the f64 sum of pm[pcur][0 .. n).z over the slots whose `owned` byte is set (nullptr: all of them), k_sum_mass's fixed-order tree.
+// Synchronises the stream.
+int cand_sum_mass(sph_ctx* c, uint32_t n, const uint8_t* owned, double* total);

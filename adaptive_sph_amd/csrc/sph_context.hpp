@@ -120,6 +120,17 @@ struct sph_ctx {
     int prob_kind = 0;
     uint32_t prob_k = 0;
     DevBuf prob_flag, prob_rank, prob_lvl, prob_ids, prob_cls, prob_mass, prob_level, prob_pos, prob_h2, prob_off, prob_idx;
+    // sph_slab_candidates.hip: the same rows on a SLAB context, which the exports above refuse.  slab_off / slab_idx hold the CSR of the
+    // last step's lists over the OWNED rows (the order of sph_download(SPH_F_PARTICLE_ID)) with SLOT indices as entries, slab_row_slot
+    // the slot of every row.  Built by the first prepare behind a step -- the slab share overwrites pm[pcur ^ 1] and clears grid_valid,
+    // so it cannot be rebuilt behind one -- kept by the share (the slots stay where they are), dropped by drop_slab_lists() wherever
+    // export_valid is cleared and by the slab merge / split.  The prepared candidate rows themselves live in cand_cls (class byte per
+    // slot, ghosts included; behind them one per row), cand_cnt, cand_off and cand_idx, which a slab context has no other use for.
+    bool slab_lists_valid = false, slab_rows_open = false;
+    uint32_t slab_lists_rows = 0, slab_rows_n = 0;
+    uint64_t slab_lists_tot = 0, slab_rows_tot = 0;
+    DevBuf slab_row_slot, slab_slot_row, slab_off, slab_idx;   // (slab_slot_row: the row of every slot, 0xffffffff for a ghost)
+    void drop_slab_lists() { slab_lists_valid = slab_rows_open = false; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];
@@ -297,4 +308,7 @@ void launch_check_neighborhood(sph_ctx* c, const SweepArgs& a);
 // The CSR of the last step's lists (the rows of sph_download_neighbors) into export_d_off / export_d_idx without a host copy of the
 // counts or the indices; sets export_valid / export_tot.  One context, grid_valid (sph_candidates.hip checks both).
 int export_lists_on_device(sph_ctx* c);
+// The same on a slab context behind a step (dist.have_flags, grid_valid): slab_off / slab_idx / slab_row_slot, entries = slot indices;
+// sets slab_lists_valid / slab_lists_rows / slab_lists_tot (sph_slab_candidates.hip checks the preconditions).
+int slab_lists_on_device(sph_ctx* c);
 void dist_release(sph_ctx* c);  // sph_step.hip

@@ -1943,7 +1943,10 @@ static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool*
         }
     }
     bool started = false;
-    for (auto c : G.m) c->export_valid = false;   // (sph_candidates.hip: the exported CSR holds the lists of the step before this one)
+    for (auto c : G.m) {   // (sph_candidates.hip, sph_slab_candidates.hip: the exported CSR holds the lists of the step before this one)
+        c->export_valid = false;
+        c->drop_slab_lists();
+    }
     const int rc = group_step_inner(G, p, outs, &started);
     if (rc && started)
         for (auto c : G.m) {

@@ -165,6 +165,9 @@ CANDIDATE_SYMBOLS = ["download_partner_candidates", "sum_mass"]
 PROBLEM_SYMBOLS = ["download_partner_problem", "share_particles_compact", "merge_particles_compact"]
 PROBLEM_FIELDS = ("particle_size_class", "mass", "level_estimation", "position", "h2")   # the five decision fields, in the call's order
 
+# include/sph_slab_candidates.h: the candidate rows of a slab context, in global ids, + the owned particles' mass sum (product only)
+SLAB_CANDIDATE_SYMBOLS = ["slab_candidates_prepare", "group_slab_candidates_prepare", "slab_candidates_download", "slab_sum_mass"]
+
 
 class SphRenderParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("supersample", C.c_int32), ("zoom_out", C.c_float),
@@ -320,6 +323,11 @@ class SphLibrary:
                                                                              C.POINTER(u64), C.POINTER(u64)], required=False)
         self.share_particles_compact = sig("share_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
         self.merge_particles_compact = sig("merge_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
+        self.slab_candidates_prepare = sig("slab_candidates_prepare", i32, [vp, i32, C.POINTER(SphParams), ap, C.POINTER(u64), C.POINTER(u64)], required=False)
+        self.group_slab_candidates_prepare = sig("group_slab_candidates_prepare", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, C.POINTER(u64),
+                                                                                       C.POINTER(u64)], required=False)
+        self.slab_candidates_download = sig("slab_candidates_download", i32, [vp, vp, vp, u64], required=False)
+        self.slab_sum_mass = sig("slab_sum_mass", i32, [vp, C.POINTER(C.c_double)], required=False)
 
 
 _PRODUCT = None
@@ -615,6 +623,43 @@ class Context:
         mp, mc = self._compact_arrays(partner_c, counter_c)
         self._check(self._problem_lib().merge_particles_compact(self.handle, C.byref(params), C.byref(ap), len(mp), mp.ctypes.data, mc.ctypes.data))
 
+    # ---- candidate export of a slab context (include/sph_slab_candidates.h) ----
+    def _slab_candidate_lib(self):
+        if any(getattr(self.lib, s, None) is None for s in SLAB_CANDIDATE_SYMBOLS):
+            raise SphError(30, f"{self.lib.path.name} has no slab candidate export (sph_slab_candidates.h is implemented by the product library only)")
+        return self.lib
+
+    def slab_candidates_prepare(self, kind, params: SphParams, ap: "SphAdaptParams"):
+        """sph_slab_candidates_prepare: COLLECTIVE through the context's own transport (every rank, from its own thread or process, behind
+        the same step): filter the `kind` ("share" / 0, "merge" / 1) rows of the owned particles on the device.  -> (n_rows, n_indices)."""
+        lib = self._slab_candidate_lib()
+        kind = {"share": 0, "merge": 1}.get(kind, kind)
+        rows, tot = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib.slab_candidates_prepare(self.handle, int(kind), C.byref(params) if params is not None else None,
+                                                C.byref(ap) if ap is not None else None, C.byref(rows), C.byref(tot)))
+        self._slab_rows = (int(rows.value), int(tot.value))
+        return self._slab_rows
+
+    def slab_candidates_download(self, host: "HostBuffers" = None, counts=None):
+        """sph_slab_candidates_download: the rows prepared last as CSR (offsets[n_rows + 1], indices): one row per owned particle in the
+        order of download("particle_id"), global ids as entries -- what adaptivity.partner_candidates_reference leaves of the rank's
+        sph_download_neighbors rows.  `counts`: the (n_rows, n_indices) the prepare returned (default: this context's last prepare);
+        `host`: persistent buffers "cand:offsets" / "cand:indices" as in download_partner_candidates."""
+        lib = self._slab_candidate_lib()
+        rows, tot = counts if counts is not None else getattr(self, "_slab_rows", (self.n, 0))
+        if host is None:
+            offsets, indices = np.empty(rows + 1, dtype=np.uint32), np.empty(tot, dtype=np.uint32)
+        else:
+            offsets, indices = host.view("cand:offsets", np.uint32, rows + 1), host.view("cand:indices", np.uint32, tot)
+        self._check(lib.slab_candidates_download(self.handle, offsets.ctypes.data, indices.ctypes.data if tot else None, tot))
+        return offsets, indices
+
+    def slab_sum_mass(self) -> float:
+        """sph_slab_sum_mass: the f64 sum of the OWNED particles' masses, reduced on the device in a fixed order."""
+        v = C.c_double(0.0)
+        self._check(self._slab_candidate_lib().slab_sum_mass(self.handle, C.byref(v)))
+        return float(v.value)
+
     # ---- frames (include/sph_render.h; adaptive_sph_amd/render.py builds the parameters) ----
     def _render_lib(self):
         if self.lib.render is None:
@@ -759,3 +804,23 @@ def group_adapt(contexts, op: str, params: SphParams, ap, merge_partner=None, me
     if rc != 0:
         msgs = [c.lib.last_error(c.handle) for c in contexts]
         raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+
+
+def group_slab_candidates_prepare(contexts, kind, params: SphParams, ap):
+    """sph_group_slab_candidates_prepare: Context.slab_candidates_prepare for the k slab contexts of this process (loopback transport);
+    returns the ranks' (n_rows, n_indices), which Context.slab_candidates_download then takes by default."""
+    lib = contexts[0].lib
+    if getattr(lib, "group_slab_candidates_prepare", None) is None:
+        raise SphError(30, f"{lib.path.name} has no slab candidate export (sph_slab_candidates.h is implemented by the product library only)")
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    rows, tot = (C.c_uint64 * k)(), (C.c_uint64 * k)()
+    rc = lib.group_slab_candidates_prepare(handles, k, int({"share": 0, "merge": 1}.get(kind, kind)), C.byref(params) if params is not None else None,
+                                           C.byref(ap) if ap is not None else None, rows, tot)
+    if rc != 0:
+        msgs = [c.lib.last_error(c.handle) for c in contexts]
+        raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+    out = [(int(rows[i]), int(tot[i])) for i in range(k)]
+    for c, v in zip(contexts, out):
+        c._slab_rows = v
+    return out
