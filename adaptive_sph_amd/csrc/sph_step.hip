@@ -841,6 +841,14 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             return c->fail(SPH_ERR_POSITION_NOT_FINITE, "particle positions are not finite");
         GridP g{};
         const bool coarse_ok = make_grid(h_max_g * 2.f, g);
+        if (!coarse_ok) {
+            // Refused before anything of the build is launched and before the context's grid, tiles or sort state are touched.  One
+            // context with mass-derived smoothing lengths has only run the header so far (h from the masses: the same values again
+            // next time), so the particle state is what it was: the refusal does not poison (sph_ffi.h).  A slab rank has handed
+            // particles over by now, FromDistribution* has swapped h2 / h2_next: those stay half-stepped.
+            if (!G.multi() && h_from_mass_mode) *started = false;
+            return c->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)g.cs);
+        }
         // (constrain_neighborhood_count changes individual smoothing lengths after the lists are built)
         c->uniform_h = (h_min_g == h_max_g) && !p->constrain_neighborhood_count;
         c->h_uniform = h_max_g;
@@ -862,15 +870,11 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                 c->tile_tsy = (fg.sy + ts - 1) / ts;
             } else {
                 fg = g;   // the finest grid that fits is the coarse one: a one-cell tile, 3 x 3 stencils
-                if (coarse_ok) {
-                    c->tile_ts = 1;
-                    c->tile_tsx = fg.sx;
-                    c->tile_tsy = fg.sy;
-                }
+                c->tile_ts = 1;
+                c->tile_tsx = fg.sx;
+                c->tile_tsy = fg.sy;
             }
         }
-        if (!coarse_ok)
-            return c->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)g.cs);
         // (what the last build left behind -- the grid the arrays are sorted by, their cells, the cell ranges -- if nothing touched the
         //  state since: a slab rank's sort below is then a merge)
         const GridP prev_grid = c->fgrid;
