@@ -19,18 +19,12 @@
 #include <stdint.h>
 
 #include "sph_ffi.h"
+#include "sph_grid_plan.hpp"   // GridP
 
 #define SPH_PI_F 3.14159274101257324219f          // std::f32::consts::PI
 #define SPH_FRAC_1_PI_F 0.318309873342514038086f  // std::f32::consts::FRAC_1_PI
 #define SPH_ETA 1.9f                              // simulation.rs:369
 #define SPH_SEVEN_PI (7.f * SPH_PI_F)
-
-struct GridP {
-    float cs;            // cell size = support radius of the largest particle
-    int minx, miny;      // cells_min  (neighborhood_search.rs:273)
-    int sx, sy;          // grid size  (cells_max - cells_min)
-    uint32_t ncells;
-};
 
 // cell key of a position in grid g, clamped into it (the grid of a build queued ahead is a prediction: sph_sort.hip, cell_key_of).
 // IEEE division, like `(particle_pos / kernel_support_radius).map(|x| x.floor() as i32)` (neighborhood_search.rs:253-255)
@@ -55,8 +49,8 @@ struct IncClassifyP {
     uint32_t epoch;
 };
 // key of current-grid cell (cx, cy) in the next grid.  The next grid covers the bounding box the current cells were computed from
-// (queue_ahead_build), so the cell lies inside it; if it ever did not, no key equals the value returned here and the particle counts
-// as a mover -- it is then on exactly one list and in no cell's stayers, like every other mover: the slots still add up to n.
+// (plan_ahead_build: plan_grid on that box with a margin), so the cell lies inside it; if it ever did not, no key equals the value
+// returned here and the particle counts as a mover -- it is then on exactly one list and in no cell's stayers, like every other mover: the slots still add up to n.
 __device__ __forceinline__ uint32_t inc_key_of_cur_cell(const GridP& cur, const GridP& nxt, uint32_t cxy)
 {
     const int cx = (int)(cxy & 0xffffu) + cur.minx - nxt.minx, cy = (int)(cxy >> 16) + cur.miny - nxt.miny;

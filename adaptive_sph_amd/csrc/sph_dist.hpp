@@ -124,6 +124,9 @@ int agree(Group& G, int local_rc);
 enum { SYNC_AGREE = 0, SYNC_DEFER = 1, SYNC_FINAL = 2 };
 int sync_ctrl(Group& G, int mode = SYNC_AGREE);
 void dbg_sync(sph_ctx* c, const char* what, int id = 0);   // SPH_DEBUG_SYNC: synchronise and name the phase just queued
+// the arrays a reorder of the context's state moves: records pm_in -> pm_out, cells to `cxy`, everything else from the buffers of c->cur
+// to the other ones (the caller flips c->cur); `lam`: also this step's lambda sums into lam_prev (FromDistribution* reads them next step)
+ReorderIO reorder_io(sph_ctx* c, const float4* pm_in, float4* pm_out, uint32_t* cxy, bool lam);
 
 // (sph_slabs.hip) slab maintenance of a group step, multi-rank only
 enum { SC_STAY = 0, SC_HALO_L = 1, SC_HALO_R = 2, SC_MIG_L = 3, SC_MIG_R = 4, SC_GHOST = 5, SC_GONE_FROM = 3 };   // classes of the fused refresh

@@ -111,8 +111,8 @@ struct CellKeyGen {
     const uint8_t* gone;
     uint32_t n_gone, gone_from;
     // 1: a record outside the grid gets the key of the nearest cell instead of an index beyond the cell table -- the grid of a build
-    // queued AHEAD is a prediction (sph_step.hip: queue_ahead_build); such a build is never adopted (the real bounding box does not
-    // fit its grid), but its kernels have run by then
+    // queued AHEAD is a prediction (sph_step.hip: plan_ahead_build -- plan_grid with a margin, sph_grid_plan.hpp); such a build is never
+    // adopted (the real bounding box does not fit its grid), but its kernels have run by then
     int clamp = 0;
 };
 // keygen != nullptr: the first pass computes the keys (keyA) and the identity values (valA) itself
@@ -127,7 +127,7 @@ size_t radix_sort_scratch_elems(uint32_t n);
 // Scratch: q.nk[n], q.mv[n] bytes, q.next[n], q.head[q.nxt.ncells] (zeroed once when allocated, never cleared: q.epoch must differ
 // from call to call and from 0), bsum[incremental_sort_block_sums(ncells)], movers (one zeroed word; the call leaves the number of
 // movers in *movers_host).
-struct ReorderIO {   // what launch_reorder moves (same meaning, same optional members)
+struct ReorderIO {   // the per-particle arrays a reorder moves (h2n, lam, szc: optional, nullptr = not moved); sph_step.hip: reorder_io
     const float4* pm_in;
     const float2* vel_in;
     const uint32_t* orig_in;
@@ -156,12 +156,10 @@ void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, co
 void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint32_t n_prev, const CellKeyGen& kg, const IncClassifyP& q, const uint32_t* cell_start_cur,
                                 uint32_t* key_out, uint32_t* perm_out, uint32_t* cell_start_out, uint32_t* bsum, uint32_t* movers, uint32_t* movers_host);
 
-void launch_reorder(hipStream_t s, Profiler* prof, uint32_t n, GridP g, const uint32_t* sorted_key, const uint32_t* perm,
-                    const float4* pm_in, const float2* vel_in, const uint32_t* orig_in, const float* lvl_in,
-                    const float* lvlold_in, float4* pm_out, float2* vel_out, uint32_t* orig_out, float* lvl_out,
-                    float* lvlold_out, uint32_t* cxy, const float* h2n_in = nullptr, float* h2n_out = nullptr,
-                    const float* lam_in = nullptr, float* lam_prev_out = nullptr, void* cell_start_scratch = nullptr,
-                    const uint8_t* szc_in = nullptr, uint8_t* szc_out = nullptr);
+// out[i] = in[perm[i]] for every array of `io`, cxy_out[i] = the cell of sorted_key[i] in grid g; cell_start_scratch != nullptr: also
+// clears the work-list counter of the launch_cell_start that follows
+void launch_reorder(hipStream_t s, Profiler* prof, uint32_t n, GridP g, const uint32_t* sorted_key, const uint32_t* perm, const ReorderIO& io,
+                    void* cell_start_scratch);
 size_t cell_start_scratch_bytes();
 void launch_cell_start(hipStream_t s, Profiler* prof, const uint32_t* sorted_key, uint32_t n, uint32_t ncells,
                        uint32_t* cell_start /* [ncells+1] */, void* scratch /* cell_start_scratch_bytes() */,

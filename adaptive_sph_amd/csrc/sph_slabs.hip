@@ -618,13 +618,9 @@ int partition_and_migrate(Group& G, std::vector<Member>& M, std::vector<int>* mo
             }
             GridP g1{};
             g1.sx = 1;
-            const int k = c->cur;
-            launch_reorder(c->stream, &c->prof, n_prev, g1, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), c->pm[c->pcur].as<float4>(),
-                           c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(), c->lvl[k].as<float>(), c->lvlold[k].as<float>(),
-                           c->pm[c->pcur ^ 1].as<float4>(), c->vel[k ^ 1].as<float2>(), c->orig[k ^ 1].as<uint32_t>(), c->lvl[k ^ 1].as<float>(),
-                           c->lvlold[k ^ 1].as<float>(), c->cxy.as<uint32_t>(), c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(),
-                           c->lam_sum.as<float>(), c->lam_prev.as<float>(), nullptr, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>());
-            c->cur = k ^ 1;
+            launch_reorder(c->stream, &c->prof, n_prev, g1, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(),
+                           reorder_io(c, c->pm[c->pcur].as<float4>(), c->pm[c->pcur ^ 1].as<float4>(), c->cxy.as<uint32_t>(), true), nullptr);
+            c->cur ^= 1;
             c->pcur ^= 1;
             std::swap(c->lam_sum, c->lam_prev);   // the permuted lambda sums are the CURRENT ones again (the cell sort moves them on)
         }

@@ -263,7 +263,7 @@ int radix_sort_pairs(hipStream_t s, Profiler* prof, uint32_t* keyA, uint32_t* va
 // six of two radix passes, the gather reorder and the two of the cell-range table; same sorted keys, same order of the arrays and same
 // cell_start bit for bit, whatever the number of movers -- the per-cell lists are built with atomics but only ever COUNTED, so no
 // result depends on their order.  Cost grows with the movers (one 64-bit atomic exchange each, list walks in the cells they
-// enter): the caller falls back to the radix sort when the previous step's count was large (sph_step.hip: plan_ahead_build).
+// enter): the caller falls back to the radix sort when the previous step's count was large (sph_grid_plan.hpp: inc_sort_worthwhile).
 // The grids of the two steps differ by a translation only (same cell size): lexicographic order of the cells is the same in both.
 // Two callers: the build a plain context queues AHEAD behind its integrating tail (incremental_cell_sort_reorder), and a slab rank's
 // sort at the start of its step, where last step's ghosts and migrants leave the array and the arrivals behind it are movers whatever
@@ -539,16 +539,13 @@ __global__ __launch_bounds__(256) void k_reorder(uint32_t n, GridP g, const uint
     cxy[i] = cx | (cy << 16);
 }
 
-void launch_reorder(hipStream_t s, Profiler* prof, uint32_t n, GridP g, const uint32_t* sorted_key, const uint32_t* perm,
-                    const float4* pm_in, const float2* vel_in, const uint32_t* orig_in, const float* lvl_in,
-                    const float* lvlold_in, float4* pm_out, float2* vel_out, uint32_t* orig_out, float* lvl_out,
-                    float* lvlold_out, uint32_t* cxy, const float* h2n_in, float* h2n_out, const float* lam_in, float* lam_prev_out,
-                    void* cell_start_scratch, const uint8_t* szc_in, uint8_t* szc_out)
+void launch_reorder(hipStream_t s, Profiler* prof, uint32_t n, GridP g, const uint32_t* sorted_key, const uint32_t* perm, const ReorderIO& io,
+                    void* cell_start_scratch)
 {
     ProfScope ps(prof, "reorder", s);
-    hipLaunchKernelGGL(k_reorder, dim3((n + 255) / 256), dim3(256), 0, s, n, g, sorted_key, perm, pm_in, vel_in, orig_in, lvl_in,
-                       lvlold_in, pm_out, vel_out, orig_out, lvl_out, lvlold_out, cxy, h2n_in, h2n_out, lam_in, lam_prev_out,
-                       (uint32_t*)cell_start_scratch, szc_in, szc_out);
+    hipLaunchKernelGGL(k_reorder, dim3((n + 255) / 256), dim3(256), 0, s, n, g, sorted_key, perm, io.pm_in, io.vel_in, io.orig_in, io.lvl_in,
+                       io.lvlold_in, io.pm_out, io.vel_out, io.orig_out, io.lvl_out, io.lvlold_out, io.cxy_out, io.h2n_in, io.h2n_out, io.lam_in,
+                       io.lam_prev_out, (uint32_t*)cell_start_scratch, io.szc_in, io.szc_out);
 }
 
 // cell_start[c] = index of the first sorted particle whose cell is >= c; cell_start[ncells] = n.

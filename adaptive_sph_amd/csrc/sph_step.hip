@@ -638,6 +638,141 @@ static int pressure_iterations(Group& G, std::vector<Member>& M, float max_avg_e
     return SPH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// pieces of the neighbour build and the level estimation that the step queues in more than one place
+// (what a build decides before it launches anything: sph_grid_plan.hpp)
+// ------------------------------------------------------------------------------------------------
+ReorderIO reorder_io(sph_ctx* c, const float4* pm_in, float4* pm_out, uint32_t* cxy, bool lam)
+{
+    const int k = c->cur;
+    return ReorderIO{pm_in, c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(), c->lvl[k].as<float>(), c->lvlold[k].as<float>(), pm_out, c->vel[k ^ 1].as<float2>(),
+                     c->orig[k ^ 1].as<uint32_t>(), c->lvl[k ^ 1].as<float>(), c->lvlold[k ^ 1].as<float>(), cxy, c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(),
+                     lam ? c->lam_sum.as<float>() : nullptr, lam ? c->lam_prev.as<float>() : nullptr, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>()};
+}
+
+// The build through the radix sort: cell keys (made by the sort's first pass) -> stable sort -> reorder -> cell ranges, on the buffers of
+// `v` -- the context's own (the build at the start of a step) or the ones of the build queued ahead.  n_sort >= n slots are sorted (a slab
+// rank's slots that left sort behind the last cell), n are kept; the sorted keys and the permutation end in key[0] / val[0].
+struct CellSortBufs {
+    DevBuf *key, *val;   // [2] each
+    DevBuf* cell_start;
+};
+static void radix_cell_build(sph_ctx* c, const CellSortBufs& v, const CellKeyGen& kg, uint32_t n_sort, int bits, uint32_t n, const ReorderIO& io)
+{
+    if (n_sort && radix_sort_pairs(c->stream, &c->prof, v.key[0].as<uint32_t>(), v.val[0].as<uint32_t>(), v.key[1].as<uint32_t>(), v.val[1].as<uint32_t>(), n_sort, bits,
+                                   c->sort_scratch.as<uint32_t>(), &kg) == 1) {
+        std::swap(v.key[0], v.key[1]);
+        std::swap(v.val[0], v.val[1]);
+    }
+    if (n) launch_reorder(c->stream, &c->prof, n, kg.g, v.key[0].as<uint32_t>(), v.val[0].as<uint32_t>(), io, c->cs_scratch.p);
+    launch_cell_start(c->stream, &c->prof, v.key[0].as<uint32_t>(), n, kg.g.ncells, v.cell_start->as<uint32_t>(), c->cs_scratch.p, n > 0);
+}
+
+// scratch of the incremental sort for a grid of `ncells`: per-cell list heads (zeroed when allocated, never cleared: every call tags its
+// lists with a new epoch, never 0), list links, block sums, the mover counter
+static int ensure_inc_sort_scratch(sph_ctx* c, uint32_t ncells)
+{
+    const size_t head_before = c->inc_head.bytes;
+    HIPCHK(c, c->inc_head.ensure((size_t)ncells * 8));
+    if (c->inc_head.bytes != head_before) HIPCHK(c, hipMemsetAsync(c->inc_head.p, 0, c->inc_head.bytes, c->stream));   // (epoch 0: no list)
+    HIPCHK(c, c->inc_next.ensure((size_t)c->cap * 4));
+    HIPCHK(c, c->inc_bsum.ensure(incremental_sort_block_sums(ncells) * 4));
+    if (!c->inc_movers.p) {
+        HIPCHK(c, c->inc_movers.ensure(4));
+        HIPCHK(c, hipMemsetAsync(c->inc_movers.p, 0, 4, c->stream));
+    }
+    if (++c->inc_epoch == 0u) c->inc_epoch = 1u;
+    return SPH_OK;
+}
+
+// Level estimation of one context (one slab rank): its buffers, and the arguments every form of it shares.  `after`
+// (level_estimation_after_advection): m.a stays what the step ran with; else it is made anew.  The caller adds its own: pm_cell, and the
+// compacted frontier (one context) or the slab's propagation mode and edge flags.
+static int level_setup(Member& m, const sph_params* p, bool after, LevelArgs& l)
+{
+    sph_ctx* c = m.c;
+    const size_t n = m.n ? m.n : 1;
+    HIPCHK(c, c->lvl_tmp.ensure((c->cap ? c->cap : 1) * 4));   // swapped with lvl[cur] at the end of the step: a persistent array, capacity-sized
+    HIPCHK(c, c->lvl_nrm.ensure(n * 8));
+    HIPCHK(c, c->lvl_when.ensure(n * 4));
+    HIPCHK(c, c->lvl_mark.ensure(n * 8));   // two parity buffers (OpLevelPropagate)
+    HIPCHK(c, c->stash.ensure(n * 4));
+    for (DevBuf* b : {&c->lvl_state, &c->flag_surface, &c->flag_insufficient}) HIPCHK(c, b->ensure(n));
+    HIPCHK(c, c->nl_ext.ensure(sweep_list_bytes((uint32_t)n)));
+    HIPCHK(c, c->nlx_ext.ensure(sweep_index_list_bytes((uint32_t)n)));
+    HIPCHK(c, c->lvl_changed_d.ensure(1024 * sizeof(uint32_t)));   // [0, 1000): flags of a batch; 1022: largest displacement; 1023: sweep 0's flag
+    if (!after) {
+        m.a = make_args(c, m.sp);
+        m.a.h_mode = p->support_length_estimation;
+        m.a.sp_check_aii = p->check_aii;
+    }
+    l = LevelArgs{};
+    l.k = p->level_estimation_range / SPH_ETA;                    // simulation.rs:2036
+    l.threshold = cosf(50.f * (SPH_PI_F / 180.f));                // simulation.rs:544
+    l.max_surface_distance = p->maximum_surface_distance;
+    l.boundary_is_fluid_surface = p->boundary_is_fluid_surface;
+    l.maximum_range = (p->support_length_estimation == SPH_H_FROM_DISTRIBUTION || p->support_length_estimation == SPH_H_FROM_DISTRIBUTION2)
+                          ? p->maximum_range : -1.f;   // simulation.rs:705-721
+    l.nrm = c->lvl_nrm.as<float2>();
+    l.state = c->lvl_state.as<uint8_t>();
+    l.flag_surface = c->flag_surface.as<uint8_t>();
+    l.flag_insufficient = c->flag_insufficient.as<uint8_t>();
+    l.size_class = c->szc[c->cur].as<uint8_t>();
+    l.level = c->lvl[c->cur].as<float>();
+    l.when = c->lvl_when.as<uint32_t>();
+    l.mark = c->lvl_mark.as<uint32_t>();
+    l.level_old = c->lvlold[c->cur].as<float>();
+    l.stash_first = p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_FIRST ? c->stash.as<float>() : nullptr;
+    l.center_diff = p->level_estimation_method == SPH_LEVEL_CENTER_DIFF;
+    l.replay_step_lists = after && !p->use_extended_range_for_level_estimation;   // simulation.rs:2680: no rebuild
+    // the extended-range lists (allocated just above when this is the first level estimation of the context) -- or the step's own
+    m.a.nl_ext = l.replay_step_lists ? m.a.nl : c->nl_ext.as<uint4>();
+    m.a.nlx_ext = l.replay_step_lists ? m.a.nlx : c->nlx_ext.as<uint4>();
+    return SPH_OK;
+}
+
+// lists of the advected positions from the cells of the pre-step ones: a neighbour may now sit ceil((k h_max + slack) / tile side) tiles away
+static void redilate_tiles_for_slack(sph_ctx* c, hipStream_t s, float k, float slack)
+{
+    const float tile_side = (float)c->tile_ts * c->fgrid.cs;
+    const int d = (int)ceilf((k * c->h_max_step + slack) / tile_side);
+    launch_tile_redilate(s, &c->prof, c->tile_tsx, c->tile_tsy, d < 1 ? 1 : d, c->tile_raw.as<uint32_t>(), c->tile_h_ext.as<uint32_t>());
+}
+
+// The propagation of one context: `while changed` (simulation.rs:740-800) as sweeps queued in batches; the host learns once per batch how
+// many of them assigned something (a sweep behind the last effective one has no candidates and costs a scan).
+struct LevelBatches {
+    uint32_t t = 1, effective = 0;   // the next sweep; sweeps that assigned something so far
+    int B = 8;                       // length of the batch in flight
+};
+// B sweeps from st.t on and the publish of their count.  The flags live in device memory (a store to mapped host memory from every
+// assigning lane made each sweep wait for PCIe at its end); their sum goes to the host once per batch.
+static void level_queue_batch(sph_ctx* c, hipStream_t ls, const SweepArgs& al, const LevelArgs& lv, bool stash_middle, LevelBatches& st)
+{
+    uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
+    (void)hipMemsetAsync(chg, 0, (size_t)st.B * sizeof(uint32_t), ls);
+    for (int b = 0; b < st.B; b++, st.t++) {
+        launch_level_propagate(ls, &c->prof, al, lv, st.t, chg + b);
+        if (st.t == 1u && stash_middle) launch_fill_stash(ls, &c->prof, al, lv, c->stash.as<float>());   // num_iter == 1, simulation.rs:769-779
+    }
+    c->level_seq++;
+    if (c->level_seq == 0u) c->level_seq = 1u;
+    hipLaunchKernelGGL(k_publish_count, dim3(1), dim3(64), 0, ls, chg, (uint32_t)st.B, c->lvl_changed_dev, 63u, c->level_seq);
+}
+// wait for the batch in flight; while every sweep of it assigned something, another batch of 8
+static int level_collect_batches(sph_ctx* c, hipStream_t ls, const SweepArgs& al, const LevelArgs& lv, bool stash_middle, LevelBatches& st)
+{
+    for (;; level_queue_batch(c, ls, al, lv, stash_middle, st)) {
+        if (int rc = wait_word(c, (volatile uint32_t*)c->lvl_changed + 63, c->level_seq)) return rc;
+        const uint32_t changed = c->lvl_changed[0];   // "nobody assigned anything" is final: the flags are ones, then zeros
+        st.effective += changed;
+        if (changed < (uint32_t)st.B) break;
+        st.B = 8;
+    }
+    c->last_level_sweeps = st.effective;
+    return SPH_OK;
+}
+
 static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs, bool* started)
 {
     int rc = SPH_OK;
@@ -775,24 +910,21 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     // (identical on every rank: all-reduced values only)
     if (!(h_max_g > 0.f) || !std::isfinite(h_max_g))
         return c0->fail(SPH_ERR_POSITION_NOT_FINITE, "particle positions or smoothing lengths are not finite");
-    const HeaderOut gbox{red[0][4], red[0][6], -red[0][5], -red[0][7], h_max_g, h_min_g, min_cfl_g, 0};   // global bounding box
+    const GridBox gbox{red[0][4], red[0][6], -red[0][5], -red[0][7]};   // global bounding box
     // CFL (simulation.rs:2190-2191)
     const float cfl_dt = p->cfl_factor * sqrtf(min_cfl_g);
     const float dt = fminf(p->max_dt, cfl_dt);
 
-    std::vector<HeaderOut> boxes(M.size(), gbox);   // bounding box of what each member sorts: owned + ghosts
+    std::vector<GridBox> boxes(M.size(), gbox);   // bounding box of what each member sorts: owned + ghosts
     if (G.multi()) {
         // Checks every rank evaluates on the SAME all-reduced numbers (no agreement needed): the cell grid of the global box
         // bounds every rank's own grid.
         int status_in = SPH_OK;
         if (!std::isfinite(gbox.min_x) || !std::isfinite(gbox.max_x) || !std::isfinite(gbox.min_y) || !std::isfinite(gbox.max_y))
             return c0->fail(SPH_ERR_POSITION_NOT_FINITE, "particle positions are not finite");
-        {
-            const float cs = h_max_g * 2.f;
-            const long long gx = (long long)floorf(gbox.max_x / cs) - (long long)floorf(gbox.min_x / cs) + 3, gy = (long long)floorf(gbox.max_y / cs) - (long long)floorf(gbox.min_y / cs) + 3;
-            if (gx <= 0 || gy <= 0 || gx >= 65536 || gy >= 65536 || gx * gy >= (1ll << 27))
-                return c0->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)cs);
-        }
+        GridP gg;
+        if (!plan_grid(gbox, h_max_g * 2.f, 0, gg))
+            return c0->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)gg.cs);
         // ghost layer with the real width: one support radius of the largest particle anywhere
         // (the extended lists of the level estimation reach level_estimation_range / ETA smoothing lengths)
         // Two rings of one support radius (2 h_max) each: ghosts of the first ring compute their pressure acceleration here
@@ -812,77 +944,38 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     auto setup_member = [&](Member& m) -> int {
         sph_ctx* c = m.c;
         (void)hipSetDevice(c->device);
-        const HeaderOut hdr = boxes[(size_t)(&m - M.data())];
+        const GridBox hdr = boxes[(size_t)(&m - M.data())];
         const uint32_t n = m.n;
-        // CellGrid (neighborhood_search.rs:261-275) with cell = support radius of the largest particle: the grid the
-        // reference's convention defines (sph_grid, cell_index).  Uniform scenes sort by it.  Multi-resolution scenes sort
-        // by a finer grid `fg` (cell = support of the smallest particle, doubled until the table fits) and give every
-        // particle its own stencil width (TileP, sph_device.h), so a fine particle far from any coarse one still looks
-        // at 3 x 3 small cells instead of 3 x 3 large ones.
-        auto make_grid = [&](float cs, GridP& out) -> bool {
-            out = GridP{};
-            out.cs = cs;
-            if (!n) {
-                out.sx = out.sy = 1;
-                out.ncells = 1;
-                return true;
-            }
-            out.minx = (int)floorf(hdr.min_x / cs) - 1;
-            out.miny = (int)floorf(hdr.min_y / cs) - 1;
-            const long long sx = (long long)((int)floorf(hdr.max_x / cs) + 2) - out.minx;
-            const long long sy = (long long)((int)floorf(hdr.max_y / cs) + 2) - out.miny;
-            if (sx <= 0 || sy <= 0 || sx >= 65536 || sy >= 65536 || sx * sy >= (1ll << 27)) return false;
-            out.sx = (int)sx;
-            out.sy = (int)sy;
-            out.ncells = (uint32_t)sx * (uint32_t)sy;
-            return true;
-        };
         if (n && (!std::isfinite(hdr.min_x) || !std::isfinite(hdr.max_x) || !std::isfinite(hdr.min_y) || !std::isfinite(hdr.max_y)))
             return c->fail(SPH_ERR_POSITION_NOT_FINITE, "particle positions are not finite");
-        GridP g{};
-        const bool coarse_ok = make_grid(h_max_g * 2.f, g);
-        if (!coarse_ok) {
+        // the grid of the reference's convention (sph_grid, cell_index), the grid the step sorts by and its tiles
+        // (constrain_neighborhood_count changes individual smoothing lengths after the lists are built)
+        const bool uniform_h = (h_min_g == h_max_g) && !p->constrain_neighborhood_count;
+        SortGridPlan sg;
+        if (!plan_sorting_grid(hdr, !n, h_min_g, h_max_g, uniform_h, sg)) {
             // Refused before anything of the build is launched and before the context's grid, tiles or sort state are touched.  One
             // context with mass-derived smoothing lengths has only run the header so far (h from the masses: the same values again
             // next time), so the particle state is what it was: the refusal does not poison (sph_ffi.h).  A slab rank has handed
             // particles over by now, FromDistribution* has swapped h2 / h2_next: those stay half-stepped.
             if (!G.multi() && h_from_mass_mode) *started = false;
-            return c->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)g.cs);
+            return c->fail(SPH_ERR_UNSUPPORTED, "cell grid of cell size %g is too large for this build", (double)sg.coarse.cs);
         }
-        // (constrain_neighborhood_count changes individual smoothing lengths after the lists are built)
-        c->uniform_h = (h_min_g == h_max_g) && !p->constrain_neighborhood_count;
+        c->uniform_h = uniform_h;
         c->h_uniform = h_max_g;
         c->h_max_step = h_max_g;
-        GridP fg = g;
-        c->tile_ts = 0;
-        // (a narrow h distribution -- FromDistribution* support lengths wander by a few percent -- keeps the one-cell stencil
-        //  of the coarse grid: the fine grid only pays once 3 x 3 coarse cells hold several times the needed candidates)
-        if (!c->uniform_h && h_max_g >= 1.75f * h_min_g) {
-            float cs = h_min_g * 2.f;
-            bool ok = false;
-            for (int k = 0; k < 24 && cs < g.cs; k++, cs *= 2.f)
-                if ((ok = make_grid(cs, fg))) break;
-            if (ok) {
-                int ts = (int)ceilf(g.cs / fg.cs);
-                while ((float)ts * fg.cs < g.cs) ts++;
-                c->tile_ts = ts;
-                c->tile_tsx = (fg.sx + ts - 1) / ts;
-                c->tile_tsy = (fg.sy + ts - 1) / ts;
-            } else {
-                fg = g;   // the finest grid that fits is the coarse one: a one-cell tile, 3 x 3 stencils
-                c->tile_ts = 1;
-                c->tile_tsx = fg.sx;
-                c->tile_tsy = fg.sy;
-            }
+        c->tile_ts = sg.tile_ts;
+        if (sg.tile_ts > 0) {
+            c->tile_tsx = sg.tile_tsx;
+            c->tile_tsy = sg.tile_tsy;
         }
         // (what the last build left behind -- the grid the arrays are sorted by, their cells, the cell ranges -- if nothing touched the
         //  state since: a slab rank's sort below is then a merge)
         const GridP prev_grid = c->fgrid;
         const bool prev_valid = c->grid_valid;
-        c->grid = g;
-        c->fgrid = fg;
+        c->grid = sg.coarse;
+        c->fgrid = sg.sort;
         c->grid_valid = true;
-        g = fg;   // everything below (keys, sort, cell ranges, sweeps) works on the sorting grid
+        GridP g = sg.sort;   // everything below (keys, sort, cell ranges, sweeps) works on the sorting grid
 
         StepP sp{};
         sp.rest_density = p->rest_density;
@@ -917,14 +1010,10 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const uint32_t n_prev = pre ? c->dist.pre_cls_n : 0u;
         uint32_t* movers_host = (uint32_t*)(c->ctrl_host + 2) + 1;
         bool merge = pre && c->opt.inc_sort && prev_valid && prev_grid.cs == g.cs && prev_grid.ncells > 0 && n_prev > 0 && n_prev <= n_sort && !c->exact &&
-                     g.ncells <= n_sort + 4096u;   // (k_inc_scan adds up the preceding block sums per block: quadratic in ncells / 1024 -- a sparse grid takes the radix sort; advisor r4)
-        if (merge) {
-            const uint32_t limit = n_sort / (c->opt.inc_sort > 1 ? (uint32_t)c->opt.inc_sort : 3u);
-            if (n_sort - n_prev > limit) merge = false;
-            else if (c->inc_count_valid && *movers_host > limit) {
-                merge = ++c->inc_radix_streak >= 8;
-                if (merge) c->inc_radix_streak = 0;
-            }
+                     inc_sort_fits(g.ncells, n_sort);
+        if (merge) {   // (the arrivals are movers of THIS build, whatever the last count was: too many of them do not touch the streak)
+            const uint32_t limit = inc_sort_mover_limit(n_sort, c->opt.inc_sort);
+            merge = n_sort - n_prev <= limit && inc_sort_worthwhile(c->inc_count_valid, *movers_host, limit, c->inc_radix_streak);
         }
         if (!merge) HIPCHK(c, c->cell_start.ensure(((size_t)g.ncells + 1) * sizeof(uint32_t)));
         // the build the previous step queued ahead (queue_ahead_build): adopted if nothing touched the state since (the header that
@@ -956,21 +1045,13 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             c->pcur ^= 1;
             c->fgrid = ag;
             g = ag;
-        } else if (n_sort) {
+        } else {
             // (the keys -- cell index, or one past the last cell for a slot that left -- are made by the sort's first pass)
             const CellKeyGen kg{c->pm[c->pcur].as<float4>(), g, pre ? c->dist.cls.as<uint8_t>() : nullptr, pre ? c->dist.pre_cls_n : 0u, (uint32_t)SC_GONE_FROM};
-            if (merge) {
-                const size_t head_before = c->inc_head.bytes;
-                HIPCHK(c, c->inc_head.ensure((size_t)g.ncells * 8));
-                if (c->inc_head.bytes != head_before) HIPCHK(c, hipMemsetAsync(c->inc_head.p, 0, c->inc_head.bytes, s));   // (epoch 0: no list)
-                HIPCHK(c, c->inc_next.ensure((size_t)c->cap * 4));
-                HIPCHK(c, c->inc_bsum.ensure(incremental_sort_block_sums(g.ncells) * 4));
-                if (!c->inc_movers.p) {
-                    HIPCHK(c, c->inc_movers.ensure(4));
-                    HIPCHK(c, hipMemsetAsync(c->inc_movers.p, 0, 4, s));
-                }
+            const ReorderIO io = reorder_io(c, c->pm[c->pcur].as<float4>(), c->pm[c->pcur ^ 1].as<float4>(), c->cxy.as<uint32_t>(), true);
+            if (merge && n_sort) {
                 HIPCHK(c, c->acell_start.ensure(((size_t)g.ncells + 1) * sizeof(uint32_t)));
-                if (++c->inc_epoch == 0u) c->inc_epoch = 1u;
+                if ((rc = ensure_inc_sort_scratch(c, g.ncells))) return rc;
                 const IncClassifyP q{prev_grid, g, c->cxy.as<uint32_t>(), c->key[1].as<uint32_t>(), c->val[1].as<uint8_t>(), c->inc_next.as<uint32_t>(),
                                      c->inc_head.as<unsigned long long>(), c->inc_epoch};
                 incremental_cell_sort_perm(s, prof, n_sort, n_prev, kg, q, c->cell_start.as<uint32_t>(), c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(),
@@ -978,24 +1059,15 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                                            (uint32_t*)(c->ctrl_host_dev + 2) + 1);
                 c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
                 std::swap(c->cell_start, c->acell_start);   // (the old table was read while the new one was written)
+                if (n) launch_reorder(s, prof, n, g, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), io, c->cs_scratch.p);
             } else {
-                int res = radix_sort_pairs(s, prof, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), c->key[1].as<uint32_t>(),
-                                           c->val[1].as<uint32_t>(), n_sort, ilog2_ceil(g.ncells + (pre ? 1u : 0u)), c->sort_scratch.as<uint32_t>(), &kg);
-                if (res == 1) {  // keep the sorted keys in key[0] / val[0]
-                    std::swap(c->key[0], c->key[1]);
-                    std::swap(c->val[0], c->val[1]);
-                }
+                radix_cell_build(c, CellSortBufs{c->key, c->val, &c->cell_start}, kg, n_sort, ilog2_ceil(g.ncells + (pre ? 1u : 0u)), n, io);
             }
-            if (n)
-                launch_reorder(s, prof, n, g, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), c->pm[c->pcur].as<float4>(), c->vel[k].as<float2>(),
-                               c->orig[k].as<uint32_t>(), c->lvl[k].as<float>(), c->lvlold[k].as<float>(), c->pm[c->pcur ^ 1].as<float4>(),
-                               c->vel[k ^ 1].as<float2>(), c->orig[k ^ 1].as<uint32_t>(), c->lvl[k ^ 1].as<float>(), c->lvlold[k ^ 1].as<float>(),
-                               c->cxy.as<uint32_t>(), c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(), c->lam_sum.as<float>(),
-                               c->lam_prev.as<float>(), c->cs_scratch.p, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>());
-            c->cur = k ^ 1;
-            c->pcur ^= 1;
+            if (n_sort) {
+                c->cur = k ^ 1;
+                c->pcur ^= 1;
+            }
         }
-        if (!adopt && !(merge && n_sort)) launch_cell_start(s, prof, c->key[0].as<uint32_t>(), n, g.ncells, c->cell_start.as<uint32_t>(), c->cs_scratch.p, n > 0);
         if (c->tile_ts > 0) {
             const size_t nt = (size_t)c->tile_tsx * (size_t)c->tile_tsy;
             // the extended-range lists reach k * h_max with k = level_estimation_range / ETA > 2: a larger particle may sit
@@ -1042,11 +1114,9 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     // `side`: detection and propagation are queued on the context's SECOND stream and the call returns without waiting
     // (level estimation BEFORE advection: nothing of it is read until the smoothing at the end of the step, so the ~100
     // latency-bound propagation sweeps run under the step's own sweeps); level_estimation_finish() collects it.
-    struct LevelPending {
-        bool on = false;
-        uint32_t t = 1, effective = 0;
-        int B = 8;
-    } lvp;
+    LevelBatches lvb;
+    bool lv_pending = false;   // a batch is in flight on the side stream
+    const bool stash_middle = p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_MIDDLE;
     auto level_estimation = [&](const float4* pm_geo, const float4* pm_old, bool side) -> int {
         const auto t_lvl0 = std::chrono::steady_clock::now();
         Member& m = M[0];
@@ -1056,56 +1126,18 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         }
+        if ((rc = level_setup(m, p, pm_old != nullptr, lv))) return rc;
         const size_t n = m.n ? m.n : 1;
-        HIPCHK(c, c->lvl_tmp.ensure((c->cap ? c->cap : 1) * 4));   // swapped with lvl[cur] at the end of the step: a persistent array, capacity-sized
-        HIPCHK(c, c->lvl_nrm.ensure(n * 8));
-        HIPCHK(c, c->lvl_when.ensure(n * 4));
-        HIPCHK(c, c->lvl_mark.ensure(n * 8));   // two parity buffers (OpLevelPropagate)
-        HIPCHK(c, c->stash.ensure(n * 4));
-        for (DevBuf* b : {&c->lvl_state, &c->flag_surface, &c->flag_insufficient}) HIPCHK(c, b->ensure(n));
-        HIPCHK(c, c->nl_ext.ensure(sweep_list_bytes((uint32_t)n)));
-        HIPCHK(c, c->nlx_ext.ensure(sweep_index_list_bytes((uint32_t)n)));
-        HIPCHK(c, c->lvl_changed_d.ensure(1024 * sizeof(uint32_t)));   // [0, 1000): flags of a batch; 1022, 1023: see below
         uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
-        if (!pm_old) {
-            m.a = make_args(c, m.sp);
-            m.a.h_mode = p->support_length_estimation;
-            m.a.sp_check_aii = p->check_aii;
-        }
-        m.a.nl_ext = c->nl_ext.as<uint4>();   // (allocated just above when this is the first level estimation of the context)
-        m.a.nlx_ext = c->nlx_ext.as<uint4>();
-        lv.k = p->level_estimation_range / SPH_ETA;                    // simulation.rs:2036
-        lv.threshold = cosf(50.f * (SPH_PI_F / 180.f));                // simulation.rs:544
-        lv.max_surface_distance = p->maximum_surface_distance;
-        lv.boundary_is_fluid_surface = p->boundary_is_fluid_surface;
-        lv.maximum_range = (p->support_length_estimation == SPH_H_FROM_DISTRIBUTION || p->support_length_estimation == SPH_H_FROM_DISTRIBUTION2)
-                               ? p->maximum_range : -1.f;   // simulation.rs:705-721
-        lv.nrm = c->lvl_nrm.as<float2>();
-        lv.state = c->lvl_state.as<uint8_t>();
-        lv.flag_surface = c->flag_surface.as<uint8_t>();
-        lv.flag_insufficient = c->flag_insufficient.as<uint8_t>();
-        lv.size_class = c->szc[c->cur].as<uint8_t>();
-        lv.level = c->lvl[c->cur].as<float>();
-        lv.when = c->lvl_when.as<uint32_t>();
-        lv.mark = c->lvl_mark.as<uint32_t>();
-        lv.level_old = c->lvlold[c->cur].as<float>();
-        lv.stash_first = p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_FIRST ? c->stash.as<float>() : nullptr;
         lv.pm_cell = pm_old;
-        lv.center_diff = p->level_estimation_method == SPH_LEVEL_CENTER_DIFF;
-        lv.replay_step_lists = pm_old != nullptr && !p->use_extended_range_for_level_estimation;   // simulation.rs:2680: no rebuild
         // the propagation on a compacted frontier (explicit index lists: the extended-range lists; the step's own lists of a uniform
         // scene are mask words, which the sweep forms replay)
-        lv.fmap = nullptr;
         if (c->opt.level_queue && !lv.replay_step_lists) {
             uint32_t lg = 0;
             while ((64ull << lg) < n) lg++;
             HIPCHK(c, c->lvl_queue.ensure((size_t)128 << lg));
             lv.fmap = c->lvl_queue.as<uint8_t>();
             lv.fmap_lg_s = lg;
-        }
-        if (lv.replay_step_lists) {
-            m.a.nl_ext = m.a.nl;
-            m.a.nlx_ext = m.a.nlx;
         }
         SweepArgs al = m.a;
         lv_slack = 0.f;
@@ -1120,12 +1152,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             if (!std::isfinite(dmax)) return c->fail(SPH_ERR_POSITION_NOT_FINITE, "Assertion 'p_position[d].is_finite()' failed!");
             lv_slack = 2.f * dmax;
             al.t_ext.slack = lv_slack;
-            if (c->tile_ts > 0) {
-                // a neighbour may now sit ceil((k h_max + slack) / tile side) tiles away
-                const float tile_side = (float)c->tile_ts * c->fgrid.cs;
-                const int d = (int)ceilf((lv.k * c->h_max_step + lv_slack) / tile_side);
-                launch_tile_redilate(ls, &c->prof, c->tile_tsx, c->tile_tsy, d < 1 ? 1 : d, c->tile_raw.as<uint32_t>(), c->tile_h_ext.as<uint32_t>());
-            }
+            if (c->tile_ts > 0) redilate_tiles_for_slack(c, ls, lv.k, lv_slack);
         }
         if (m.n) {
             // (lab, SPH_SIDE_CUS: the side stream owns a few CUs -- the heavy detection sweeps then run on the MAIN stream, and only the
@@ -1140,40 +1167,19 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                 HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
             }
-            // propagate until a sweep assigns nothing (`while changed`, simulation.rs:740-800).  Sweeps are queued in batches and the
-            // host learns once per batch how many of them assigned something (a sweep behind the last effective one has no
-            // candidates and costs a scan).  The first batch is as long as the previous step's propagation + 1 -- the fluid's
-            // depth hardly changes from step to step -- so a step usually waits once instead of once per 8 sweeps.
+            // propagate until a sweep assigns nothing, in batches (LevelBatches).  The first batch is as long as the previous step's
+            // propagation + 1 -- the fluid's depth hardly changes from step to step -- so a step usually waits once instead of once per 8 sweeps.
             launch_level_propagate(ls, &c->prof, al, lv, 0u, chg + 1023);   // surface particles mark their neighbours
-            uint32_t t = 1, effective = 0;
-            int B = (int)std::min<uint32_t>(std::max<uint32_t>(c->last_level_sweeps + 1u, 8u), 1000u);
-            if (c->opt.level_batch8) B = 8;   // measurement aid: the fixed batches of 8
-            for (bool done = false; !done; B = 8) {
-                // the flags live in device memory (a store to mapped host memory from every assigning lane made each sweep
-                // wait for PCIe at its end); their sum goes to the host once per batch
-                (void)hipMemsetAsync(chg, 0, (size_t)B * sizeof(uint32_t), ls);
-                for (int b = 0; b < B; b++, t++) {
-                    launch_level_propagate(ls, &c->prof, al, lv, t, chg + b);
-                    if (t == 1u && p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_MIDDLE)   // num_iter == 1, simulation.rs:769-779
-                        launch_fill_stash(ls, &c->prof, al, lv, c->stash.as<float>());
-                }
-                c->level_seq++;
-                if (c->level_seq == 0u) c->level_seq = 1u;
-                hipLaunchKernelGGL(k_publish_count, dim3(1), dim3(64), 0, ls, chg, (uint32_t)B, c->lvl_changed_dev, 63u, c->level_seq);
-                if (side) {   // collected by level_estimation_finish()
-                    lvp.on = true;
-                    lvp.t = t;
-                    lvp.B = B;
-                    lvp.effective = effective;
-                    lv_args = al;
-                    break;
-                }
-                if ((rc = wait_word(c, (volatile uint32_t*)c->lvl_changed + 63, c->level_seq))) return rc;
-                const uint32_t changed = c->lvl_changed[0];   // "nobody assigned anything" is final: the flags are ones, then zeros
-                effective += changed;
-                done = changed < (uint32_t)B;
+            lvb = LevelBatches{};
+            lvb.B = (int)std::min<uint32_t>(std::max<uint32_t>(c->last_level_sweeps + 1u, 8u), 1000u);
+            if (c->opt.level_batch8) lvb.B = 8;   // measurement aid: the fixed batches of 8
+            level_queue_batch(c, ls, al, lv, stash_middle, lvb);
+            if (side) {   // collected by level_estimation_finish()
+                lv_pending = true;
+                lv_args = al;
+            } else if ((rc = level_collect_batches(c, ls, al, lv, stash_middle, lvb))) {
+                return rc;
             }
-            if (!side) c->last_level_sweeps = effective;
         }
         c->have_level = true;
         m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
@@ -1182,30 +1188,12 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     // the rest of a propagation that was queued on the side stream: wait for its first batch, continue in batches of 8 if the
     // prediction (the previous step's sweep count + 1) fell short
     auto level_estimation_finish = [&]() -> int {
-        if (!lvp.on) return SPH_OK;
-        lvp.on = false;
+        if (!lv_pending) return SPH_OK;
+        lv_pending = false;
         const auto t_lvl0 = std::chrono::steady_clock::now();
-        Member& m = M[0];
-        sph_ctx* c = m.c;
-        hipStream_t ls = c->stream2;
-        uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
-        uint32_t t = lvp.t, effective = lvp.effective;
-        int B = lvp.B;
-        for (;;) {
-            if ((rc = wait_word(c, (volatile uint32_t*)c->lvl_changed + 63, c->level_seq))) return rc;
-            const uint32_t changed = c->lvl_changed[0];
-            effective += changed;
-            if (changed < (uint32_t)B) break;
-            B = 8;
-            (void)hipMemsetAsync(chg, 0, (size_t)B * sizeof(uint32_t), ls);
-            for (int b = 0; b < B; b++, t++) launch_level_propagate(ls, &c->prof, lv_args, lv, t, chg + b);
-            c->level_seq++;
-            if (c->level_seq == 0u) c->level_seq = 1u;
-            hipLaunchKernelGGL(k_publish_count, dim3(1), dim3(64), 0, ls, chg, (uint32_t)B, c->lvl_changed_dev, 63u, c->level_seq);
-        }
-        c->last_level_sweeps = effective;
+        if ((rc = level_collect_batches(c0, c0->stream2, lv_args, lv, stash_middle, lvb))) return rc;
         // (the host saw the side stream's last publish: everything queued there has finished before the main stream goes on)
-        m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
+        M[0].st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
         return SPH_OK;
     };
     // the same on a slab decomposition (before advection): ghost lanes idle, the ghosts' (level, when) refreshed from their
@@ -1258,61 +1246,19 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             sph_ctx* c = m.c;
             (void)hipSetDevice(c->device);
             const size_t n = m.n ? m.n : 1;
-            HIPCHK(c, c->lvl_tmp.ensure((c->cap ? c->cap : 1) * 4));   // swapped with lvl[cur] at the end of the step: a persistent array, capacity-sized
-            HIPCHK(c, c->lvl_nrm.ensure(n * 8));
-            HIPCHK(c, c->lvl_when.ensure(n * 4));
-            HIPCHK(c, c->lvl_mark.ensure(n * 8));   // two parity buffers (OpLevelPropagate)
-            HIPCHK(c, c->stash.ensure(n * 4));
-            for (DevBuf* b : {&c->lvl_state, &c->flag_surface, &c->flag_insufficient}) HIPCHK(c, b->ensure(n));
-            HIPCHK(c, c->nl_ext.ensure(sweep_list_bytes((uint32_t)n)));
-            HIPCHK(c, c->nlx_ext.ensure(sweep_index_list_bytes((uint32_t)n)));
-            HIPCHK(c, c->lvl_changed_d.ensure(1024 * sizeof(uint32_t)));
-            if (!after) {
-                m.a = make_args(c, m.sp);
-                m.a.h_mode = p->support_length_estimation;
-                m.a.sp_check_aii = p->check_aii;
-            }
-            m.a.nl_ext = c->nl_ext.as<uint4>();
-            m.a.nlx_ext = c->nlx_ext.as<uint4>();
             LevelArgs& l = LV[i];
-            l = LevelArgs{};
-            l.k = p->level_estimation_range / SPH_ETA;
-            l.threshold = cosf(50.f * (SPH_PI_F / 180.f));
-            l.max_surface_distance = p->maximum_surface_distance;
-            l.boundary_is_fluid_surface = p->boundary_is_fluid_surface;
-            l.maximum_range = (p->support_length_estimation == SPH_H_FROM_DISTRIBUTION || p->support_length_estimation == SPH_H_FROM_DISTRIBUTION2)
-                                  ? p->maximum_range : -1.f;   // simulation.rs:705-721
-            l.nrm = c->lvl_nrm.as<float2>();
-            l.state = c->lvl_state.as<uint8_t>();
-            l.flag_surface = c->flag_surface.as<uint8_t>();
-            l.flag_insufficient = c->flag_insufficient.as<uint8_t>();
-            l.size_class = c->szc[c->cur].as<uint8_t>();
-            l.level = c->lvl[c->cur].as<float>();
-            l.when = c->lvl_when.as<uint32_t>();
-            l.mark = c->lvl_mark.as<uint32_t>();
-            l.level_old = c->lvlold[c->cur].as<float>();
-            l.stash_first = p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_FIRST ? c->stash.as<float>() : nullptr;
+            if ((rc = level_setup(m, p, after, l))) return rc;
             // frontier form with probing halo members (OpLevelPropagate, mode 2); SPH_SLAB_LEVEL_PLAIN=1: every unassigned particle in
             // every sweep (measurement / tests; parameters only: the same on every rank)
             l.plain_propagate = c0->opt.slab_level_plain ? 1 : 2;
             l.edge = c->dist.edge.as<uint8_t>();
             l.pm_cell = after ? c->pm[c->pcur].as<float4>() : nullptr;
-            l.center_diff = p->level_estimation_method == SPH_LEVEL_CENTER_DIFF;
-            l.replay_step_lists = replay_step_lists;
-            if (replay_step_lists) {
-                m.a.nl_ext = m.a.nl;
-                m.a.nlx_ext = m.a.nlx;
-            }
             SweepArgs& al = AL[i];
             al = m.a;
             if (after) {
                 al.pm = c->pm[c->pcur ^ 1].as<float4>();
                 al.t_ext.slack = slab_lv_slack;
-                if (!replay_step_lists && c->tile_ts > 0) {
-                    const float tile_side = (float)c->tile_ts * c->fgrid.cs;
-                    const int dd = (int)ceilf((l.k * c->h_max_step + slab_lv_slack) / tile_side);
-                    launch_tile_redilate(c->stream, &c->prof, c->tile_tsx, c->tile_tsy, dd < 1 ? 1 : dd, c->tile_raw.as<uint32_t>(), c->tile_h_ext.as<uint32_t>());
-                }
+                if (!replay_step_lists && c->tile_ts > 0) redilate_tiles_for_slack(c, c->stream, l.k, slab_lv_slack);
             }
             m.lv_level = (float*)l.level;
             m.lv_when = (float*)l.when;
@@ -1554,19 +1500,12 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // at most cfl_factor supports per step): two cells of a uniform scene, two tiles of a multi-resolution one
         const float cs = c->fgrid.cs;
         const int ts = c->tile_ts, margin = 2 * (ts > 0 ? ts : 1);
-        GridP g{};
-        g.cs = cs;
-        g.minx = (int)floorf(boxes[0].min_x / cs) - 1 - margin;
-        g.miny = (int)floorf(boxes[0].min_y / cs) - 1 - margin;
-        const long long sx = (long long)((int)floorf(boxes[0].max_x / cs) + 2 + margin) - g.minx, sy = (long long)((int)floorf(boxes[0].max_y / cs) + 2 + margin) - g.miny;
-        if (sx <= 0 || sy <= 0 || sx >= 65536 || sy >= 65536 || sx * sy >= (1ll << 27)) return SPH_OK;
-        g.sx = (int)sx;
-        g.sy = (int)sy;
-        g.ncells = (uint32_t)sx * (uint32_t)sy;
+        GridP g;
+        if (!plan_grid(boxes[0], cs, margin, g)) return SPH_OK;
         if (ts > 0) {
             plan.tile_ts = ts;
-            plan.tile_tsx = (g.sx + ts - 1) / ts;
-            plan.tile_tsy = (g.sy + ts - 1) / ts;
+            plan.tile_tsx = tiles_across(g.sx, ts);
+            plan.tile_tsy = tiles_across(g.sy, ts);
             const size_t nt = (size_t)plan.tile_tsx * (size_t)plan.tile_tsy;
             HIPCHK(c, c->atile_raw.ensure(nt * 4));
             HIPCHK(c, c->atile_h.ensure(nt * 4));
@@ -1585,23 +1524,10 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // and cell ranges as the radix sort, whatever the number of movers; its cost grows with them, so a large count (the last one
         // the device reported: a step or two old) sends the build through the radix sort, and every eighth such build probes again.
         const uint32_t* movers_host = (const uint32_t*)(c->ctrl_host + 2) + 1;   // (second word of the mapped block whose first word is the paced solves' progress)
-        bool incremental = c->opt.inc_sort && c->grid_valid && c->fgrid.cs == cs && c->fgrid.ncells > 0 && g.ncells <= n + 4096u;   // (see k_inc_scan: quadratic in ncells / 1024; a grid much sparser than one cell per particle takes the radix sort)
-        if (incremental && c->inc_count_valid && *movers_host > n / (c->opt.inc_sort > 1 ? (uint32_t)c->opt.inc_sort : 3u)) {
-            incremental = ++c->inc_radix_streak >= 8;
-            if (incremental) c->inc_radix_streak = 0;
-        }
-        if (!incremental) return SPH_OK;
-        hipStream_t s = c->stream;
-        const size_t head_before = c->inc_head.bytes;
-        HIPCHK(c, c->inc_head.ensure((size_t)g.ncells * 8));
-        if (c->inc_head.bytes != head_before) HIPCHK(c, hipMemsetAsync(c->inc_head.p, 0, c->inc_head.bytes, s));   // (epoch 0: no list)
-        HIPCHK(c, c->inc_next.ensure((size_t)c->cap * 4));
-        HIPCHK(c, c->inc_bsum.ensure(incremental_sort_block_sums(g.ncells) * 4));
-        if (!c->inc_movers.p) {
-            HIPCHK(c, c->inc_movers.ensure(4));
-            HIPCHK(c, hipMemsetAsync(c->inc_movers.p, 0, 4, s));
-        }
-        if (++c->inc_epoch == 0u) c->inc_epoch = 1u;
+        if (!(c->opt.inc_sort && c->grid_valid && c->fgrid.cs == cs && c->fgrid.ncells > 0 && inc_sort_fits(g.ncells, n) &&
+              inc_sort_worthwhile(c->inc_count_valid, *movers_host, inc_sort_mover_limit(n, c->opt.inc_sort), c->inc_radix_streak)))
+            return SPH_OK;
+        if ((rc = ensure_inc_sort_scratch(c, g.ncells))) return rc;
         plan.incremental = true;
         plan.q = IncClassifyP{c->fgrid, g, c->cxy.as<uint32_t>(), c->akey[1].as<uint32_t>(), c->aval[1].as<uint8_t>(), c->inc_next.as<uint32_t>(),
                               c->inc_head.as<unsigned long long>(), c->inc_epoch};
@@ -1619,30 +1545,17 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const uint32_t n = M[0].n;
         const GridP g = plan.g;
         hipStream_t s = c->stream;
-        const int k = c->cur;
         const float4* integrated = c->pm[c->pcur ^ 1].as<float4>();   // (the tail's output; the step's end flips pcur)
         if (plan.incremental) {
-            const ReorderIO io{integrated, c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(), c->lvl[k].as<float>(), c->lvlold[k].as<float>(), c->pm2.as<float4>(),
-                               c->vel[k ^ 1].as<float2>(), c->orig[k ^ 1].as<uint32_t>(), c->lvl[k ^ 1].as<float>(), c->lvlold[k ^ 1].as<float>(), c->acxy.as<uint32_t>(),
-                               c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(), /* lambda sums of this step: only FromDistribution* reads them next step,
-                               and a step in that mode does not adopt this build */ nullptr, nullptr, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>()};
+            // (without the lambda sums of this step: only FromDistribution* reads them next step, and a step in that mode does not adopt this build)
             incremental_cell_sort_reorder(s, &c->prof, n, integrated, plan.q, /* classified by the tail */ true, c->cell_start.as<uint32_t>(), c->akey[0].as<uint32_t>(),
-                                          c->acell_start.as<uint32_t>(), io, c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(),
-                                          (uint32_t*)(c->ctrl_host_dev + 2) + 1);
+                                          c->acell_start.as<uint32_t>(), reorder_io(c, integrated, c->pm2.as<float4>(), c->acxy.as<uint32_t>(), false),
+                                          c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1);
             c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
         } else {
             const CellKeyGen kg{integrated, g, nullptr, 0u, (uint32_t)SC_GONE_FROM, 1};   // (clamped keys: the grid is a prediction)
-            const int res = radix_sort_pairs(s, &c->prof, c->akey[0].as<uint32_t>(), c->aval[0].as<uint32_t>(), c->akey[1].as<uint32_t>(), c->aval[1].as<uint32_t>(), n,
-                                             ilog2_ceil(g.ncells), c->sort_scratch.as<uint32_t>(), &kg);
-            if (res == 1) {
-                std::swap(c->akey[0], c->akey[1]);
-                std::swap(c->aval[0], c->aval[1]);
-            }
-            launch_reorder(s, &c->prof, n, g, c->akey[0].as<uint32_t>(), c->aval[0].as<uint32_t>(), integrated, c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(),
-                           c->lvl[k].as<float>(), c->lvlold[k].as<float>(), c->pm2.as<float4>(), c->vel[k ^ 1].as<float2>(), c->orig[k ^ 1].as<uint32_t>(),
-                           c->lvl[k ^ 1].as<float>(), c->lvlold[k ^ 1].as<float>(), c->acxy.as<uint32_t>(), c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(),
-                           c->lam_sum.as<float>(), c->lam_prev.as<float>(), c->cs_scratch.p, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>());
-            launch_cell_start(s, &c->prof, c->akey[0].as<uint32_t>(), n, g.ncells, c->acell_start.as<uint32_t>(), c->cs_scratch.p, true);
+            radix_cell_build(c, CellSortBufs{c->akey, c->aval, &c->acell_start}, kg, n, ilog2_ceil(g.ncells), n,
+                             reorder_io(c, integrated, c->pm2.as<float4>(), c->acxy.as<uint32_t>(), true));
         }
         if (plan.tile_ts > 0)
             launch_tile_hmax(s, &c->prof, n, c->pm2.as<float4>(), g, plan.tile_ts, plan.tile_tsx, plan.tile_tsy, c->atile_raw.as<uint32_t>(), c->atile_h.as<uint32_t>(),

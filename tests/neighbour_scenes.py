@@ -20,7 +20,7 @@ RS_TILE = 2048            # keys per workgroup of a sort pass: 64 x RS_ITEMS
 RS_TRIP = 1024            # tiles one trip of k_rs_rowscan scans: 256 threads x 4 counts
 CS_INLINE = 64            # a gap of >= 64 cells between two occupied keys goes to the work list ...
 CS_WORK_CAP = 65536       # ... unless the list is full: then the owning thread fills it after all
-MERGE_SLACK = 4096        # the merge is admitted for a predicted grid of at most n + 4096 cells (sph_step.hip: plan_ahead_build)
+MERGE_SLACK = 4096        # the merge is admitted for a predicted grid of at most n + 4096 cells (sph_grid_plan.hpp: inc_sort_fits)
 AHEAD_MARGIN = 2          # cells the predicted grid of a uniform scene adds on every side
 GRID_DIM_LIMIT = 65536    # a grid dimension must stay below it (cx | cy << 16), the cell count below 2^27
 GRID_CELL_LIMIT = 1 << 27
@@ -355,7 +355,8 @@ MULTIRES_SCENES = {
 
 
 def sorting_grid(pos, mass):
-    """setup_member's make_grid and its search for the sorting grid of a multi-resolution scene, in f32 like the product:
+    """plan_grid and plan_sorting_grid (csrc/sph_grid_plan.hpp: the coarse grid and the search for the sorting grid of a multi-resolution
+    scene) restated in f32 like the product -- tests/test_build_plan_host.py compares the two on the CPU:
     -> (coarse (sx, sy), sorting (sx, sy), doublings or None for the fallback, tile side)"""
     h = h_of_mass(mass)
     lo, hi = pos.min(axis=0).astype(np.float32), pos.max(axis=0).astype(np.float32)
