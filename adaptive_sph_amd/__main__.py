@@ -38,10 +38,11 @@ def build_parser() -> argparse.ArgumentParser:
     run.add_argument("--split-patterns", default=None,
                      help="SplitPatterns file (load_split_patterns_from_file); default ./split-patterns.yaml, the path the reference reads (main_loop.rs:200-203)")
     run.add_argument("--capacity-factor", type=float, default=4.0, help="device capacity = this x the initial particle count (splitting adds particles)")
-    run.add_argument("--adaptivity-export", choices=["lists", "candidates", "compact"], default="lists",
+    run.add_argument("--adaptivity-export", choices=["lists", "candidates", "compact", "device"], default="lists",
                      help="what the partner searches read from the device: every neighbour list; per search only the donors' neighbours "
                           "that pass its class and distance tests (filtered on the device); or only the donors and candidates themselves, "
-                          "renumbered on the device, with the decisions sent back in that numbering (same decisions in all three)")
+                          "renumbered on the device, with the decisions sent back in that numbering; or nothing at all -- the search itself runs on the "
+                          "device and only its counts come back (same decisions in all four)")
     run.add_argument("--device", type=int, default=0)
     # the reference's VtkExporter is compiled in but switched off (main_loop.rs:253 `export_vtk_data = false`); same writer here
     run.add_argument("--vtk", default=None, metavar="FOLDER", help="write FOLDER/my-sph-NNNNN.vtk + my-sph.vtk.series (one snapshot per step)")

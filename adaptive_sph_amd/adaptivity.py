@@ -86,12 +86,10 @@ def mass_base(P: SimulationParams) -> np.float32:
     return radius_to_sphere_volume(f32(P.particle_radius_base)) * f32(P.rest_density)     # simulation_parameters.rs:129-131
 
 
-def _find_partners(kind: str, size_class, mass, level, position, h2, offsets, indices, P: SimulationParams, dt: float) -> Tuple[np.ndarray, np.ndarray]:
-    """find_share_partner_sequential (particle_sharing.rs:14-117) / find_merge_partner_sequential (particle_merging.rs:16-125):
-    the same greedy loop, in particle order, over each particle's neighbour list in list order."""
-    n = len(mass)
-    merge_partner = np.full(n, MERGE_PARTNER_AVAILABLE, np.uint32)
-    merge_counter = np.zeros(n, np.uint16)
+def _row_runner(kind: str, size_class, mass, level, position, h2, offsets, indices, P: SimulationParams, dt: float):
+    """The body of find_share_partner_sequential (particle_sharing.rs:14-117) / find_merge_partner_sequential (particle_merging.rs:16-125)
+    for ONE donor: -> (donors, run) with `donors` the particles of the donor class in ascending index and run(i, merge_partner,
+    merge_counter) the walk over i's list in list order, which writes the two arrays and returns the j it claimed."""
     mass = np.asarray(mass, np.float32)
     target = target_mass(level, P)
     mbase = mass_base(P)
@@ -99,8 +97,9 @@ def _find_partners(kind: str, size_class, mass, level, position, h2, offsets, in
     donors = np.nonzero(np.asarray(size_class) == (LARGE if share else TOO_SMALL))[0]
     max_dist_factor = f32(P.max_share_distance if share else P.max_merge_distance)
     dtf = f32(dt)
-    for i in donors:
-        i = int(i)
+
+    def run(i: int, merge_partner, merge_counter):
+        claimed = []
         if share:
             dropped_i = min(mass[i] - target[i], target[i] * f32(P.max_mass_transfer_sharing) * dtf)   # dropped_mass_sharing
         else:
@@ -137,8 +136,108 @@ def _find_partners(kind: str, size_class, mass, level, position, h2, offsets, in
                 merge_partner[i] = MERGE_PARTNER_DELETE
             merge_partner[j] = i
             merge_counter[i] += 1
+            claimed.append(j)
             assert merge_counter[i] < 1000
+        return claimed
+
+    return donors, run
+
+
+def _find_partners(kind: str, size_class, mass, level, position, h2, offsets, indices, P: SimulationParams, dt: float) -> Tuple[np.ndarray, np.ndarray]:
+    """find_share_partner_sequential (particle_sharing.rs:14-117) / find_merge_partner_sequential (particle_merging.rs:16-125):
+    the same greedy loop, in particle order, over each particle's neighbour list in list order."""
+    n = len(mass)
+    merge_partner = np.full(n, MERGE_PARTNER_AVAILABLE, np.uint32)
+    merge_counter = np.zeros(n, np.uint16)
+    donors, run = _row_runner(kind, size_class, mass, level, position, h2, offsets, indices, P, dt)
+    for i in donors:
+        run(int(i), merge_partner, merge_counter)
     return merge_partner, merge_counter
+
+
+def find_partners_frontier(kind: str, size_class, mass, level, position, h2, offsets, indices, P: SimulationParams, dt: float):
+    """The sequential loop of `_find_partners` in its exact PARALLEL schedule (the numpy twin of
+    csrc/sph_partner_search.hip) -> (merge_partner, merge_counter, info), the two arrays equal to `_find_partners`'s.
+
+    touch(i) = row(i) + {i} for a donor i with a non-empty row: everything the loop reads or writes of merge_partner while it visits i.
+    writers(x): the donors whose touch set holds x, ascending.  A donor is FINISHED once it ran its row and RETIRED once it was claimed
+    before it ran (the loop lets such a donor accept nobody).  head(x): the first writer of x that is neither.  Donor i is READY iff every
+    x of touch(i) is claimed already (final: i skips it) or has head(x) == i.  A round runs the rows of all ready donors: no two of them
+    share an unclaimed x, so the order among them does not matter, and by induction over the donor index every row sees what it sees in
+    the sequential loop.  After a round, the writers of every particle claimed in it are checked again, the donors claimed in it retire,
+    and head(x) moves past finished and retired writers for every x such a donor touched; the new heads are checked again.  The donors
+    that are ready among those checked are the next frontier -- nothing ever sweeps over all undecided donors.
+
+    Asserted in every round: the frontier's touch sets are disjoint on unclaimed particles, and the smallest undecided donor is in it.
+    info: participants (n), candidates (the entries), donors (merge_counter > 0), transfers (the counters' sum), rounds, max_frontier,
+    row_walks (rows walked by a decision or a readiness check)."""
+    n = len(mass)
+    AV = MERGE_PARTNER_AVAILABLE
+    merge_partner = np.full(n, AV, np.uint32)
+    merge_counter = np.zeros(n, np.uint16)
+    donors, run = _row_runner(kind, size_class, mass, level, position, h2, offsets, indices, P, dt)
+    off = np.asarray(offsets, np.int64)
+    idx = np.asarray(indices, np.int64)
+    donors = [int(d) for d in donors if off[d + 1] > off[d]]
+    touch = {d: sorted(set(idx[off[d]:off[d + 1]].tolist()) | {d}) for d in donors}
+    writers = [[] for _ in range(n)]
+    for d in donors:                      # ascending, so every writers list is
+        for x in touch[d]:
+            writers[x].append(d)
+    UNDECIDED, FINISHED, RETIRED = 0, 1, 2
+    state = {d: UNDECIDED for d in donors}
+    hp = [0] * n                          # head(x) = writers[x][hp[x]]
+    walks = 0
+
+    def head(x):
+        return writers[x][hp[x]] if hp[x] < len(writers[x]) else -1
+
+    def ready(i):
+        nonlocal walks
+        walks += 1
+        return all(merge_partner[x] != AV or head(x) == i for x in touch[i])
+
+    frontier = [d for d in donors if ready(d)]
+    remaining, lo, rounds, max_frontier = len(donors), 0, 0, 0
+    while frontier:
+        rounds += 1
+        max_frontier = max(max_frontier, len(frontier))
+        while lo < len(donors) and state[donors[lo]] != UNDECIDED:
+            lo += 1
+        assert donors[lo] in frontier, "the smallest undecided donor is ready in every round"
+        seen = set()
+        for i in frontier:
+            for x in touch[i]:
+                if merge_partner[x] == AV:
+                    assert x not in seen, "two ready donors share an unclaimed particle"
+                    seen.add(x)
+        claimed = []
+        for i in frontier:
+            claimed += run(i, merge_partner, merge_counter)
+            state[i] = FINISHED
+        walks += len(frontier)
+        remaining -= len(frontier)
+        recheck, dirty = set(), set()
+        for j in claimed:
+            recheck.update(writers[j])                    # (1) a claimed particle blocks none of its writers any more
+            if state.get(j) == UNDECIDED:                 # (2) a claimed donor never runs
+                state[j] = RETIRED
+                remaining -= 1
+                dirty.update(touch[j])
+        for i in frontier:                                # (3) what a finished donor leaves unclaimed gets a new head
+            dirty.update(x for x in touch[i] if merge_partner[x] == AV)
+        for x in dirty:
+            if merge_partner[x] != AV:
+                continue
+            while hp[x] < len(writers[x]) and state[writers[x][hp[x]]] != UNDECIDED:
+                hp[x] += 1
+            if head(x) >= 0:
+                recheck.add(head(x))
+        frontier = sorted(d for d in recheck if state[d] == UNDECIDED and ready(d))
+    assert remaining == 0, f"{remaining} donors undecided and nobody ready"
+    info = {"participants": n, "candidates": int(len(idx)), "donors": int(np.count_nonzero(merge_counter)), "transfers": int(merge_counter.sum()),
+            "rounds": rounds, "max_frontier": max_frontier, "row_walks": walks}
+    return merge_partner, merge_counter, info
 
 
 def find_share_partner_sequential(size_class, mass, level, position, h2, offsets, indices, P: SimulationParams, dt: float):
@@ -289,6 +388,10 @@ class AdaptivityDriver:
     renumbered 0..K-1 on the device with their five fields and their rows (download_partner_problem, include/sph_partner_problem.h);
     the same search runs with n = K and its K decisions go back through share_particles_compact / merge_particles_compact.  No full
     field and no list crosses the bus in this mode.
+    "device": the same compact problem is built AND solved on the device (find_partners_device, include/sph_partner_search.h: the loop's
+    exact parallel schedule, `find_partners_frontier` is its numpy twin) and share_particles_device / merge_particles_device apply the
+    decisions where they are.  Per pass only the 48-byte info struct comes down and nothing goes up; the info gains "rounds" and
+    "max_frontier" (the largest of the step's passes).  `DEVICE_EXPORTS` names it: `EXPORTS` stays the modes whose decisions the host takes.
 
     The returned info counts what crossed it: "exported_indices" (list or candidate entries), "participants" (the sum of K over the
     passes; compact mode only, else 0), "bytes_down" / "bytes_up" (the payload arrays of the step's exports and applies, computed
@@ -296,16 +399,18 @@ class AdaptivityDriver:
     arrays, 8 B per device mass sum)."""
 
     EXPORTS = ("lists", "candidates", "compact")
+    DEVICE_EXPORTS = ("device",)
+    INFO_BYTES = 48   # sizeof(sph_partner_search_info)
 
     def __init__(self, ctx: ffi.Context, split_patterns: SplitPatterns = None, log=None, export: str = "lists"):
-        if export not in self.EXPORTS:
-            raise ValueError(f"export must be one of {self.EXPORTS}, not {export!r}")
+        if export not in self.EXPORTS + self.DEVICE_EXPORTS:
+            raise ValueError(f"export must be one of {self.EXPORTS + self.DEVICE_EXPORTS}, not {export!r}")
         self.ctx = ctx
         self.log = log
         self.export = export
         self.host = ffi.HostBuffers()   # the exports land in the same host memory every step (round 6: the 26 ms "download" of configs[4]'s adaptive step were mostly page faults of fresh arrays)
         if ctx.n:
-            if export in ("candidates", "compact"):
+            if export in ("candidates", "compact", "device"):
                 self.host.reserve(ctx.n, export=export)
             else:
                 self.host.reserve(ctx.n)
@@ -319,11 +424,14 @@ class AdaptivityDriver:
         ctx, log = self.ctx, self.log
         candidates = self.export == "candidates"
         compact = self.export == "compact"
-        if (candidates or compact) and lists is not None:
+        device = self.export == "device"
+        if (candidates or compact or device) and lists is not None:
             raise ValueError(f"export=\"{self.export}\" filters the lists that live in the context: it cannot be combined with lists= (slab assembly)")
         p, ap = P.to_ffi(), adapt_params(P, dt)
         info = {"n_before": ctx.n, "shares": 0, "merges": 0, "splits": 0, "export": self.export, "exported_indices": 0, "participants": 0,
                 "bytes_down": 0, "bytes_up": 0}
+        if device:
+            info["rounds"] = info["max_frontier"] = 0
         # what the adaptive half of a step costs, by phase (bench.py reports it): device -> host of the lists and the five fields a
         # decision reads, the sequential partner searches on the host, the apply calls on the device
         tm = info["seconds"] = {"download": 0.0, "host_decide": 0.0, "apply": 0.0, "mass_check": 0.0}
@@ -336,7 +444,7 @@ class AdaptivityDriver:
         t0 = _t.perf_counter()
         host = self.host
         off = idx = None
-        if candidates or compact:
+        if candidates or compact or device:
             total_mass1 = ctx.sum_mass()
             info["bytes_down"] += 8
             tm["mass_check"] += _t.perf_counter() - t0
@@ -393,26 +501,42 @@ class AdaptivityDriver:
         def run_pass(kind, apply_f):
             keys = ("participants", "exported_indices", "bytes_down", "bytes_up")
             c0, t0, n0 = {k: info[k] for k in keys}, dict(tm), ctx.n
-            mp, mc = decide(kind)
-            events = int(mc.sum())
+            extra = {}
+            if device:   # classify, search and apply on the device: the host sees the info struct ("apply" holds all three)
+                ta = _t.perf_counter()
+                ctx.classify(p)
+                found = ctx.find_partners_device(kind, p, ap)
+                events = found["transfers"]
+                info["participants"] += found["participants"]
+                info["bytes_down"] += self.INFO_BYTES
+                for k in ("rounds", "max_frontier"):
+                    info[k] = max(info[k], found[k])
+                extra = {"search": found}
+                tm["apply"] += _t.perf_counter() - ta
+            else:
+                mp, mc = decide(kind)
+                events = int(mc.sum())
             if log:
                 log(f"SEQUENTIAL {kind.upper()} {events} {kind}s")
-            apply(apply_f, p, ap, mp, mc)
-            info["passes"].append({"kind": kind, "n": n0, "events": events, **{k: info[k] - c0[k] for k in keys},
+            if device:
+                apply(apply_f, p, ap)
+            else:
+                apply(apply_f, p, ap, mp, mc)
+            info["passes"].append({"kind": kind, "n": n0, "events": events, **{k: info[k] - c0[k] for k in keys}, **extra,
                                    "seconds": {k: tm[k] - t0[k] for k in ("download", "host_decide", "apply")}})
             return events
 
         if P.sharing:
-            info["shares"] = run_pass("share", ctx.share_particles_compact if compact else ctx.share_particles)
+            info["shares"] = run_pass("share", ctx.share_particles_device if device else ctx.share_particles_compact if compact else ctx.share_particles)
         if step_number % 2 == 0:
             if P.merging:
-                info["merges"] = run_pass("merge", ctx.merge_particles_compact if compact else ctx.merge_particles)
+                info["merges"] = run_pass("merge", ctx.merge_particles_device if device else ctx.merge_particles_compact if compact else ctx.merge_particles)
         elif P.splitting:
             n0 = ctx.n
             apply(lambda: (ctx.classify(p), ctx.split_particles(p, ap)))
             info["splits"] = ctx.n - n0
         t0 = _t.perf_counter()
-        if candidates or compact:
+        if candidates or compact or device:
             total_mass2 = ctx.sum_mass()
             info["bytes_down"] += 8
             tm["mass_check"] += _t.perf_counter() - t0

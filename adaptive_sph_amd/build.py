@@ -53,6 +53,10 @@ def build_hip(force: bool = False, verbose: bool = False, out_name: str = "libsp
     objdir.mkdir(parents=True, exist_ok=True)
     stamp = objdir / ("linked-" + out_name)   # which flag set that .so was linked from
     objs = [objdir / (s.stem + ".o") for s in srcs]
+    # a library linked from this flag set and newer than every source and header is up to date, with or without its objects (a tree
+    # that was copied without them)
+    if not force and out.exists() and stamp.exists() and not _stale(out, srcs + headers) and not _stale(stamp, [out]) and not any(o.exists() and _stale(out, [o]) for o in objs):
+        return out
     todo = [(s, o) for s, o in zip(srcs, objs) if force or _stale(o, [s] + headers)]
     if not todo and out.exists() and stamp.exists() and not _stale(out, objs) and not _stale(stamp, [out]):
         return out

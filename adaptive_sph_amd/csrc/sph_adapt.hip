@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "sph_dist.hpp"
+#include "sph_target_mass.hpp"
 
 // (a slab context takes the slab form below: slab_adapt)
 static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter);
@@ -100,30 +101,7 @@ void device_exclusive_scan_u32(hipStream_t s, const uint32_t* in, uint32_t* out,
     if (nb) hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(SCAN_BLOCK), 0, s, in, out, n, scratch);
 }
 
-// ---- LevelEstimationState::target_mass (simulation.rs:213-237) -- the same IEEE operations as k_classify -----------------
-struct TargetP {
-    float max_surface_distance, rest_density, radius_fine, radius_base;
-    int sizing_function;
-};
-__device__ __forceinline__ float target_mass(float lv, const TargetP& t)
-{
-    const float lvl = fmaxf(lv, -t.max_surface_distance);
-    const float interp = lvl / -t.max_surface_distance;
-    const float mass_fine = (SPH_PI_F * t.radius_fine * t.radius_fine) * t.rest_density;
-    const float mass_base = (SPH_PI_F * t.radius_base * t.radius_base) * t.rest_density;
-    if (t.sizing_function == SPH_SIZING_MASS) return mass_fine * (1.f - interp) + mass_base * interp;
-    if (t.sizing_function == SPH_SIZING_RADIUS) {
-        const float r = t.radius_fine * (1.f - interp) + t.radius_base * interp;
-        return (SPH_PI_F * r * r) * t.rest_density;
-    }
-    const float e = 1.f / 2.f;
-    const float r = t.radius_fine * (1.f - powf(interp, e)) + t.radius_base * powf(interp, e);
-    return (SPH_PI_F * r * r) * t.rest_density;
-}
-static TargetP target_params(const sph_params* p)
-{
-    return TargetP{p->maximum_surface_distance, p->rest_density, p->particle_radius_fine, p->particle_radius_base, p->sizing_function};
-}
+// LevelEstimationState::target_mass (TargetP, target_mass, target_params): sph_target_mass.hpp, shared with sph_partner_search.hip
 
 __global__ __launch_bounds__(256) void k_slot_of(uint32_t n, const uint32_t* __restrict__ orig, uint32_t* __restrict__ slot_of)
 {

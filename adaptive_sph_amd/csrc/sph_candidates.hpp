@@ -42,3 +42,17 @@ int cand_fill_rows(sph_ctx* c, const CandP& q, uint32_t tot);
 // the f64 sum of pm[pcur][0 .. n).z over the slots whose `owned` byte is set (nullptr: all of them), k_sum_mass's fixed-order tree.
 // Synchronises the stream.
 int cand_sum_mass(sph_ctx* c, uint32_t n, const uint8_t* owned, double* total);
+
+// sph_partner_problem.hip, shared with sph_partner_search.hip.  prob_build_on_device: the compact problem of `kind` into prob_ids ..
+// prob_idx without a bulk copy (lists present: cand_need_lists came first); `caps` (may be null): the host buffers a download was given.
+struct ProbCaps {
+    bool participants_given;
+    uint64_t participants;
+    bool indices_given;
+    uint64_t indices;
+};
+int prob_build_on_device(sph_ctx* c, int kind, const sph_adapt_params* ap, const char* what, const ProbCaps* caps, uint32_t* K, uint32_t* tot);
+// the problem just built becomes THE OPEN PROBLEM of the context
+void prob_open_problem(sph_ctx* c, int kind, uint32_t K);
+// queues k_prob_expand: K decisions in compact ids -> merge_partner / merge_counter of the whole vector (pre-filled with AVAILABLE / 0)
+void prob_expand_launch(sph_ctx* c, uint32_t K, const uint32_t* d_partner_c, const uint16_t* d_counter_c, uint32_t* d_partner, uint16_t* d_counter);

@@ -83,6 +83,7 @@ struct Options {
     int main_exclude = 0;       // SPH_MAIN_EXCLUDE=1       (lab) ... and the main stream is masked OFF those CUs
     int ipc_fuse_max_bytes = 64 << 10;   // SPH_IPC_FUSE_MAX_BYTES=<b>  push transport: a Jacobi iteration's exchange is fused (Comm::exchange_fused) while its largest message is <= b (0: never)
     int ipc_copy_min_bytes = 256 << 10;  // SPH_IPC_COPY_MIN_BYTES=<b>  push transport: a message above b bytes is copied by k_ipc_copy, the push kernel only signals
+    int search_block = 1024;    // SPH_SEARCH_BLOCK=<t>     (lab) workgroup size of the partner search's resident driver (a multiple of 64, 64..1024; profiles/r11_device_search.md)
 };
 Options options_from_env();   // sph_api.hip
 
@@ -120,6 +121,11 @@ struct sph_ctx {
     int prob_kind = 0;
     uint32_t prob_k = 0;
     DevBuf prob_flag, prob_rank, prob_lvl, prob_ids, prob_cls, prob_mass, prob_level, prob_pos, prob_h2, prob_off, prob_idx;
+    // sph_partner_search.hip: the decisions taken on the device for the open problem (compact ids), THE OPEN SOLUTION while the problem
+    // it belongs to is open (prob_open && sol_serial == prob_serial: prob_serial counts the problems opened), and the search's work
+    // arrays -- the writers CSR, head positions, donor states, dedupe stamps, the round lists and the progress record.
+    uint64_t prob_serial = 0, sol_serial = 0;
+    DevBuf sol_partner, sol_counter, ps_w, ps_words, ps_state, ps_rec;
     // sph_slab_candidates.hip: the same rows on a SLAB context, which the exports above refuse.  slab_off / slab_idx hold the CSR of the
     // last step's lists over the OWNED rows (the order of sph_download(SPH_F_PARTICLE_ID)) with SLOT indices as entries, slab_row_slot
     // the slot of every row.  Built by the first prepare behind a step -- the slab share overwrites pm[pcur ^ 1] and clears grid_valid,

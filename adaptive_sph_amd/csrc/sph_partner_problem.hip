@@ -94,19 +94,10 @@ __global__ __launch_bounds__(256) void k_prob_expand(uint32_t K, uint32_t n, con
     counter[i] = counter_c[c];
 }
 
-extern "C" int sph_download_partner_problem(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t* ids, uint8_t* size_class, float* mass,
-                                            float* level, float* position, float* h2, uint32_t* offsets, uint64_t pcap, uint32_t* indices, uint64_t icap,
-                                            uint64_t* n_participants, uint64_t* n_indices)
+// mark / rank / pack / relabel on the device, no bulk copy: the compact problem of `kind` in prob_ids .. prob_idx (see the head of this
+// file).  n > 0 or not; *K / *tot are set once they are known (one 4-byte copy each), also when `caps` then refuses the sizes.
+int prob_build_on_device(sph_ctx* c, int kind, const sph_adapt_params* ap, const char* what, const ProbCaps* caps, uint32_t* K_out, uint32_t* tot_out)
 {
-    if (!c) return SPH_ERR_INVALID_ARGUMENT;
-    if (n_participants) *n_participants = 0;
-    if (n_indices) *n_indices = 0;
-    c->prob_open = false;   // (this call replaces the open problem, or closes it)
-    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_problem: params and ap must be given");
-    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_problem: kind %d is neither 0 (share) nor 1 (merge)", kind);
-    if (int rc = cand_refuse_common(c, "sph_download_partner_problem")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = cand_need_lists(c)) return rc;
     const uint32_t n = (uint32_t)c->n;
     hipStream_t s = c->stream;
     const dim3 grid((n + 255) / 256), blk(256);
@@ -128,13 +119,13 @@ extern "C" int sph_download_partner_problem(sph_ctx* c, int kind, const sph_para
             }
             HIPCHK(c, hipMemcpyAsync(&K, c->prob_rank.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipStreamSynchronize(s));
-            if (K == 0 || K > n) return c->fail(SPH_ERR_DEVICE, "sph_download_partner_problem: %u candidates but %u participants of %u particles", tot, K, n);
+            if (K == 0 || K > n) return c->fail(SPH_ERR_DEVICE, "%s: %u candidates but %u participants of %u particles", what, tot, K, n);
         }
     }
-    if (n_participants) *n_participants = K;
-    if (n_indices) *n_indices = tot;
-    if ((ids || size_class || mass || level || position || h2 || offsets) && pcap < K) return c->fail(SPH_ERR_INVALID_ARGUMENT, "participant buffers too small");
-    if (indices && icap < tot) return c->fail(SPH_ERR_INVALID_ARGUMENT, "indices buffer too small");
+    *K_out = K;
+    *tot_out = tot;
+    if (caps && caps->participants_given && caps->participants < K) return c->fail(SPH_ERR_INVALID_ARGUMENT, "participant buffers too small");
+    if (caps && caps->indices_given && caps->indices < tot) return c->fail(SPH_ERR_INVALID_ARGUMENT, "indices buffer too small");
     if (K) {
         HIPCHK(c, c->prob_lvl.ensure((size_t)n * 4));
         HIPCHK(c, c->prob_ids.ensure((size_t)K * 4));
@@ -145,18 +136,56 @@ extern "C" int sph_download_partner_problem(sph_ctx* c, int kind, const sph_para
         HIPCHK(c, c->prob_h2.ensure((size_t)K * 4));
         HIPCHK(c, c->prob_off.ensure(((size_t)K + 1) * 4));
         HIPCHK(c, c->prob_idx.ensure((size_t)tot * 4));
-        {
-            ProfScope ps(&c->prof, "problem_pack", s);
-            hipLaunchKernelGGL(k_prob_level, grid, blk, 0, s, n, (const uint32_t*)c->orig[c->cur].as<uint32_t>(), (const float*)c->lvl[c->cur].as<float>(),
-                               c->prob_lvl.as<float>());
-            hipLaunchKernelGGL(k_prob_pack, grid, blk, 0, s, n, K, tot, (const uint32_t*)c->prob_flag.as<uint32_t>(), (const uint32_t*)c->prob_rank.as<uint32_t>(),
-                               (const float4*)c->cand_rec.as<float4>(), (const uint8_t*)c->cand_cls.as<uint8_t>(), (const float*)c->prob_lvl.as<float>(),
-                               (const uint32_t*)c->cand_off.as<uint32_t>(),
-                               ProbOut{c->prob_ids.as<uint32_t>(), c->prob_cls.as<uint8_t>(), c->prob_mass.as<float>(), c->prob_level.as<float>(),
-                                       c->prob_pos.as<float2>(), c->prob_h2.as<float>(), c->prob_off.as<uint32_t>()});
-            hipLaunchKernelGGL(k_prob_relabel, dim3((tot + 255) / 256), blk, 0, s, tot, n, (const uint32_t*)c->cand_idx.as<uint32_t>(),
-                               (const uint32_t*)c->prob_rank.as<uint32_t>(), c->prob_idx.as<uint32_t>());
-        }
+        ProfScope ps(&c->prof, "problem_pack", s);
+        hipLaunchKernelGGL(k_prob_level, grid, blk, 0, s, n, (const uint32_t*)c->orig[c->cur].as<uint32_t>(), (const float*)c->lvl[c->cur].as<float>(),
+                           c->prob_lvl.as<float>());
+        hipLaunchKernelGGL(k_prob_pack, grid, blk, 0, s, n, K, tot, (const uint32_t*)c->prob_flag.as<uint32_t>(), (const uint32_t*)c->prob_rank.as<uint32_t>(),
+                           (const float4*)c->cand_rec.as<float4>(), (const uint8_t*)c->cand_cls.as<uint8_t>(), (const float*)c->prob_lvl.as<float>(),
+                           (const uint32_t*)c->cand_off.as<uint32_t>(),
+                           ProbOut{c->prob_ids.as<uint32_t>(), c->prob_cls.as<uint8_t>(), c->prob_mass.as<float>(), c->prob_level.as<float>(),
+                                   c->prob_pos.as<float2>(), c->prob_h2.as<float>(), c->prob_off.as<uint32_t>()});
+        hipLaunchKernelGGL(k_prob_relabel, dim3((tot + 255) / 256), blk, 0, s, tot, n, (const uint32_t*)c->cand_idx.as<uint32_t>(),
+                           (const uint32_t*)c->prob_rank.as<uint32_t>(), c->prob_idx.as<uint32_t>());
+    }
+    return SPH_OK;
+}
+
+void prob_open_problem(sph_ctx* c, int kind, uint32_t K)
+{
+    c->prob_open = true;
+    c->prob_kind = kind;
+    c->prob_k = K;
+    c->prob_epoch = c->export_epoch;
+    c->prob_serial++;   // (a solution of an earlier problem is not one of this problem: sph_partner_search.hip)
+}
+
+void prob_expand_launch(sph_ctx* c, uint32_t K, const uint32_t* d_partner_c, const uint16_t* d_counter_c, uint32_t* d_partner, uint16_t* d_counter)
+{
+    hipLaunchKernelGGL(k_prob_expand, dim3((K + 255) / 256), dim3(256), 0, c->stream, K, (uint32_t)c->n, (const uint32_t*)c->prob_ids.as<uint32_t>(), d_partner_c,
+                       d_counter_c, d_partner, d_counter);
+}
+
+extern "C" int sph_download_partner_problem(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t* ids, uint8_t* size_class, float* mass,
+                                            float* level, float* position, float* h2, uint32_t* offsets, uint64_t pcap, uint32_t* indices, uint64_t icap,
+                                            uint64_t* n_participants, uint64_t* n_indices)
+{
+    if (!c) return SPH_ERR_INVALID_ARGUMENT;
+    if (n_participants) *n_participants = 0;
+    if (n_indices) *n_indices = 0;
+    c->prob_open = false;   // (this call replaces the open problem, or closes it)
+    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_problem: params and ap must be given");
+    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_problem: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    if (int rc = cand_refuse_common(c, "sph_download_partner_problem")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = cand_need_lists(c)) return rc;
+    hipStream_t s = c->stream;
+    uint32_t tot = 0, K = 0;
+    const ProbCaps caps{ids || size_class || mass || level || position || h2 || offsets, pcap, indices != nullptr, icap};
+    const int rc = prob_build_on_device(c, kind, ap, "sph_download_partner_problem", &caps, &K, &tot);
+    if (n_participants) *n_participants = K;
+    if (n_indices) *n_indices = tot;
+    if (rc) return rc;
+    if (K) {
         const size_t k = K;
         if (ids) HIPCHK(c, hipMemcpyAsync(ids, c->prob_ids.p, k * 4, hipMemcpyDeviceToHost, s));
         if (size_class) HIPCHK(c, hipMemcpyAsync(size_class, c->prob_cls.p, k, hipMemcpyDeviceToHost, s));
@@ -168,10 +197,7 @@ extern "C" int sph_download_partner_problem(sph_ctx* c, int kind, const sph_para
         if (indices) HIPCHK(c, hipMemcpyAsync(indices, c->prob_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     } else if (offsets) offsets[0] = 0;
-    c->prob_open = true;
-    c->prob_kind = kind;
-    c->prob_k = K;
-    c->prob_epoch = c->export_epoch;
+    prob_open_problem(c, kind, K);
     return SPH_OK;
 }
 
@@ -206,8 +232,7 @@ static int apply_compact(sph_ctx* c, const sph_params* p, const sph_adapt_params
         if (K) {
             HIPCHK(c, hipMemcpyAsync(d_pc.p, partner_c, (size_t)K * 4, hipMemcpyHostToDevice, s));
             HIPCHK(c, hipMemcpyAsync(d_cc.p, counter_c, (size_t)K * 2, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_prob_expand, dim3((K + 255) / 256), dim3(256), 0, s, K, n, (const uint32_t*)c->prob_ids.as<uint32_t>(),
-                               (const uint32_t*)d_pc.as<uint32_t>(), (const uint16_t*)d_cc.as<uint16_t>(), d_partner.as<uint32_t>(), d_counter.as<uint16_t>());
+            prob_expand_launch(c, K, d_pc.as<uint32_t>(), d_cc.as<uint16_t>(), d_partner.as<uint32_t>(), d_counter.as<uint16_t>());
         }
     }
     return transfer_on_device(c, p, ap, d_partner.as<uint32_t>(), d_counter.as<uint16_t>(), merging);

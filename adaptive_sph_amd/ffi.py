@@ -165,6 +165,18 @@ CANDIDATE_SYMBOLS = ["download_partner_candidates", "sum_mass"]
 PROBLEM_SYMBOLS = ["download_partner_problem", "share_particles_compact", "merge_particles_compact"]
 PROBLEM_FIELDS = ("particle_size_class", "mass", "level_estimation", "position", "h2")   # the five decision fields, in the call's order
 
+# include/sph_partner_search.h: the partner searches solved on the device, their decisions applied there (product only)
+SEARCH_SYMBOLS = ["find_partners_device", "download_partner_decisions", "share_particles_device", "merge_particles_device"]
+
+
+class SphPartnerSearchInfo(C.Structure):
+    _fields_ = [("participants", C.c_uint64), ("candidates", C.c_uint64), ("donors", C.c_uint64), ("transfers", C.c_uint64),
+                ("rounds", C.c_uint32), ("max_frontier", C.c_uint32), ("wide_rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 # include/sph_slab_candidates.h: the candidate rows of a slab context, in global ids, + the owned particles' mass sum (product only)
 SLAB_CANDIDATE_SYMBOLS = ["slab_candidates_prepare", "group_slab_candidates_prepare", "slab_candidates_download", "slab_sum_mass"]
 
@@ -209,6 +221,8 @@ class HostBuffers:
         Context.download_partner_candidates instead of the full lists (its indices: room for 4 per particle instead of 16, grown on demand).
         `export="compact"`: the "prob:*" buffers of Context.download_partner_problem only, sized for n participants and 4 n candidates --
         the most a pass can need of the former (a cold first merge touches nearly every particle), grown on demand for the latter."""
+        if export == "device":   # (nothing per particle crosses the bus)
+            return
         if export == "compact":
             self.reserve_problem(n, 4 * n)
             self.view("merge_partner", np.uint32, n)
@@ -323,6 +337,10 @@ class SphLibrary:
                                                                              C.POINTER(u64), C.POINTER(u64)], required=False)
         self.share_particles_compact = sig("share_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
         self.merge_particles_compact = sig("merge_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp], required=False)
+        self.find_partners_device = sig("find_partners_device", i32, [vp, i32, C.POINTER(SphParams), ap, C.c_uint32, C.POINTER(SphPartnerSearchInfo)], required=False)
+        self.download_partner_decisions = sig("download_partner_decisions", i32, [vp, u64, vp, vp, vp], required=False)
+        self.share_particles_device = sig("share_particles_device", i32, [vp, C.POINTER(SphParams), ap], required=False)
+        self.merge_particles_device = sig("merge_particles_device", i32, [vp, C.POINTER(SphParams), ap], required=False)
         self.slab_candidates_prepare = sig("slab_candidates_prepare", i32, [vp, i32, C.POINTER(SphParams), ap, C.POINTER(u64), C.POINTER(u64)], required=False)
         self.group_slab_candidates_prepare = sig("group_slab_candidates_prepare", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, C.POINTER(u64),
                                                                                        C.POINTER(u64)], required=False)
@@ -622,6 +640,43 @@ class Context:
         """sph_merge_particles_compact: merge_particles from the decisions on the open problem, in its compact numbering."""
         mp, mc = self._compact_arrays(partner_c, counter_c)
         self._check(self._problem_lib().merge_particles_compact(self.handle, C.byref(params), C.byref(ap), len(mp), mp.ctypes.data, mc.ctypes.data))
+
+    # ---- partner search on the device (include/sph_partner_search.h) ----
+    def _search_lib(self):
+        if any(getattr(self.lib, s, None) is None for s in SEARCH_SYMBOLS):
+            raise SphError(30, f"{self.lib.path.name} has no device partner search (sph_partner_search.h is implemented by the product library only)")
+        return self.lib
+
+    def find_partners_device(self, kind, params: SphParams, ap: "SphAdaptParams", wide_threshold: int = 0) -> dict:
+        """sph_find_partners_device: build the compact problem of the `kind` ("share" / 0, "merge" / 1) search on the device and solve it
+        there (the schedule of adaptivity.find_partners_frontier).  The decisions stay on the device as the context's open solution for
+        share_particles_device / merge_particles_device; -> the info struct as a dict (participants, candidates, donors, transfers, rounds,
+        max_frontier, wide_rounds).  `wide_threshold`: 0 = the library's default, 1 = every round as grid launches, 0xFFFFFFFF = every
+        round inside the resident kernel; the decisions do not depend on it."""
+        lib = self._search_lib()
+        kind = int({"share": 0, "merge": 1}.get(kind, kind))
+        info = SphPartnerSearchInfo()
+        self._check(lib.find_partners_device(self.handle, kind, C.byref(params) if params is not None else None, C.byref(ap) if ap is not None else None,
+                                             int(wide_threshold), C.byref(info)))
+        return info.as_dict()
+
+    def download_partner_decisions(self, k: int):
+        """sph_download_partner_decisions (inspection; the solution stays open): -> (ids, partner_c, counter_c) of the open solution, which
+        must have exactly `k` participants."""
+        lib = self._search_lib()
+        k = int(k)
+        ids, mp, mc = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint16)
+        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+        self._check(lib.download_partner_decisions(self.handle, k, ptr(ids), ptr(mp), ptr(mc)))
+        return ids, mp, mc
+
+    def share_particles_device(self, params: SphParams, ap: "SphAdaptParams") -> None:
+        """sph_share_particles_device: share_particles from the open solution, without a copy of the decisions."""
+        self._check(self._search_lib().share_particles_device(self.handle, C.byref(params), C.byref(ap)))
+
+    def merge_particles_device(self, params: SphParams, ap: "SphAdaptParams") -> None:
+        """sph_merge_particles_device: merge_particles from the open solution, without a copy of the decisions."""
+        self._check(self._search_lib().merge_particles_device(self.handle, C.byref(params), C.byref(ap)))
 
     # ---- candidate export of a slab context (include/sph_slab_candidates.h) ----
     def _slab_candidate_lib(self):

@@ -106,8 +106,8 @@ class FluidSimulation:
     def __init__(self, position, velocity, mass, planes, counters_enabled: bool = False,
                  lib: Optional[ffi.SphLibrary] = None, device_id: int = 0, n_capacity: Optional[int] = None, split_patterns=None,
                  adaptivity_export: str = "lists"):
-        if adaptivity_export not in ("lists", "candidates", "compact"):
-            raise ValueError(f"adaptivity_export must be 'lists', 'candidates' or 'compact', not {adaptivity_export!r}")
+        if adaptivity_export not in ("lists", "candidates", "compact", "device"):
+            raise ValueError(f"adaptivity_export must be 'lists', 'candidates', 'compact' or 'device', not {adaptivity_export!r}")
         self.adaptivity_export = adaptivity_export   # what single_step_adaptivity reads of the neighbour lists (adaptivity.AdaptivityDriver)
         self.lib = lib if lib is not None else ffi.load_product()
         mass = np.ascontiguousarray(mass, dtype=np.float32)
@@ -228,7 +228,7 @@ def init_fluid_sim(simulation_params: SimulationParams, scene_config: SceneConfi
                    lib: Optional[ffi.SphLibrary] = None, device_id: int = 0, split_patterns=None,
                    n_capacity: Optional[int] = None, adaptivity_export: str = "lists") -> FluidSimulation:
     """simulation.rs:3074-3231.  `n_capacity`: room for the particles splitting will add (the reference's Vecs grow on demand;
-    the device arrays are sized once).  `adaptivity_export`: "lists", "candidates" or "compact" (adaptivity.AdaptivityDriver)."""
+    the device arrays are sized once).  `adaptivity_export`: "lists", "candidates", "compact" or "device" (adaptivity.AdaptivityDriver)."""
     pos, mass, vel = init_particles(scene_config)
     planes = boundary_planes(scene_config.boundary, simulation_params.init_boundary_handler)
     return FluidSimulation(pos, vel, mass, planes, counters_enabled, lib=lib, device_id=device_id, split_patterns=split_patterns,
