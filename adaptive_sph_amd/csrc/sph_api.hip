@@ -698,7 +698,7 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
                      &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos,
-                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->sol_partner, &c->sol_counter, &c->ps_w, &c->ps_words, &c->ps_state, &c->ps_rec, &c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev};
+                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->sol_partner, &c->sol_counter, &c->ps_w, &c->ps_words, &c->ps_state, &c->ps_rec, &c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage};
     for (auto b : all) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);

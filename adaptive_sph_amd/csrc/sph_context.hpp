@@ -280,6 +280,12 @@ struct sph_ctx {
     DevBuf rnd_rec, rnd_keys, rnd_out, rnd_max, rnd_prev;
     uint64_t rnd_prev_n = 0;
     bool rnd_have_prev = false;
+    // frames from slab contexts (sph_slab_render.hip): this rank's layer -- rnd_layer_hs rows of the sample columns [rnd_layer_sx0,
+    // rnd_layer_sx1), one 64-bit word per sample -- kept until the next layer call; the three words of the band reduction; the
+    // WS x HS words a compose merges the layers into, and the staging of layers that arrive from the host
+    DevBuf rnd_layer, rnd_band, rnd_words, rnd_stage;
+    bool rnd_have_layer = false;
+    int rnd_layer_sx0 = 0, rnd_layer_sx1 = 0, rnd_layer_hs = 0;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)

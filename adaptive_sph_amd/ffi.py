@@ -181,6 +181,18 @@ class SphPartnerSearchInfo(C.Structure):
 SLAB_CANDIDATE_SYMBOLS = ["slab_candidates_prepare", "group_slab_candidates_prepare", "slab_candidates_download", "slab_sum_mass"]
 
 
+# include/sph_slab_render.h: frames drawn from slab contexts -- rank layers composed on the device (product only)
+SLAB_RENDER_SYMBOLS = ["slab_render_pressure_max", "slab_render_layer", "slab_render_layer_download", "render_compose", "group_render"]
+
+
+class SphRenderBand(C.Structure):
+    """sph_render_band: the sample columns [sx0, sx1) that hold a rank's layer, and the owned discs drawn into it."""
+    _fields_ = [("sx0", C.c_int32), ("sx1", C.c_int32), ("n_drawn", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return int(self.sx0), int(self.sx1), int(self.n_drawn)
+
+
 class SphRenderParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("supersample", C.c_int32), ("zoom_out", C.c_float),
                 ("attribute", C.c_int32), ("flags", C.c_uint32), ("alpha", C.c_float), ("n_stops", C.c_int32),
@@ -346,6 +358,12 @@ class SphLibrary:
                                                                                        C.POINTER(u64)], required=False)
         self.slab_candidates_download = sig("slab_candidates_download", i32, [vp, vp, vp, u64], required=False)
         self.slab_sum_mass = sig("slab_sum_mass", i32, [vp, C.POINTER(C.c_double)], required=False)
+        bp = C.POINTER(SphRenderBand)
+        self.slab_render_pressure_max = sig("slab_render_pressure_max", i32, [vp, C.POINTER(C.c_float)], required=False)
+        self.slab_render_layer = sig("slab_render_layer", i32, [vp, C.POINTER(SphParams), rpp, C.c_float, bp], required=False)
+        self.slab_render_layer_download = sig("slab_render_layer_download", i32, [vp, vp, u64], required=False)
+        self.render_compose = sig("render_compose", i32, [vp, rpp, i32, bp, C.POINTER(vp), vp, u64], required=False)
+        self.group_render = sig("group_render", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), rpp, vp, u64], required=False)
 
 
 _PRODUCT = None
@@ -738,6 +756,60 @@ class Context:
         """sph_render_snapshot: keep the current positions for the next interpolated frame."""
         self._check(self._render_lib().render_snapshot(self.handle))
 
+    # ---- frames from slab contexts (include/sph_slab_render.h; adaptive_sph_amd/render.py: render_group, render_rank) ----
+    def _slab_render_lib(self):
+        if any(getattr(self.lib, s, None) is None for s in SLAB_RENDER_SYMBOLS):
+            raise SphError(30, f"{self.lib.path.name} has no slab renderer (sph_slab_render.h is implemented by the product library only)")
+        return self.lib
+
+    def slab_render_pressure_max(self) -> float:
+        """sph_slab_render_pressure_max: max(0, max p) over this rank's owned particles.  The maximum over the ranks goes to every
+        rank's slab_render_layer."""
+        v = C.c_float(0.0)
+        self._check(self._slab_render_lib().slab_render_pressure_max(self.handle, C.byref(v)))
+        return float(v.value)
+
+    def slab_render_layer(self, params: SphParams, rp: "SphRenderParams", pressure_max: float = 0.0) -> "SphRenderBand":
+        """sph_slab_render_layer: draw this rank's owned particles into its layer (kept on the device) -> the band of sample columns."""
+        band = SphRenderBand()
+        self._layer_shape = None
+        self._check(self._slab_render_lib().slab_render_layer(self.handle, C.byref(params) if params is not None else None,
+                                                              C.byref(rp) if rp is not None else None, float(pressure_max), C.byref(band)))
+        self._layer_shape = (int(rp.height) * int(rp.supersample), int(band.sx1) - int(band.sx0))
+        return band
+
+    def slab_render_layer_download(self) -> np.ndarray:
+        """sph_slab_render_layer_download: the layer drawn last as uint64[HS, sx1 - sx0], row 0 at the top:
+        (global id + 1) << 32 | r | g << 8 | b << 16 of the sample's winner among the owned particles, 0 where none covers it."""
+        lib = self._slab_render_lib()
+        shape = getattr(self, "_layer_shape", None)
+        if shape is None:   # (no layer call through this object: the library says what is missing)
+            self._check(lib.slab_render_layer_download(self.handle, None, 0))
+            return np.zeros((0, 0), np.uint64)
+        out = np.empty(shape, np.uint64)
+        self._check(lib.slab_render_layer_download(self.handle, out.ctypes.data if out.size else None, out.size))
+        return out
+
+    def render_compose(self, rp: "SphRenderParams", bands, layers) -> np.ndarray:
+        """sph_render_compose on this context (plain or slab): the ranks' layers -> the frame as uint8[height, width, 3].  layers[k]:
+        uint64[HS, sx1 - sx0] of bands[k], or None for an empty band."""
+        lib = self._slab_render_lib()
+        k = len(bands)
+        barr = (SphRenderBand * max(1, k))()
+        ptrs = (C.c_void_p * max(1, k))()
+        keep = []
+        for i, (b, l) in enumerate(zip(bands, layers)):
+            barr[i] = SphRenderBand(int(b.sx0), int(b.sx1), int(b.n_drawn), 0)
+            if l is not None and np.asarray(l).size:
+                a = np.ascontiguousarray(l, np.uint64)
+                keep.append(a)
+                ptrs[i] = a.ctypes.data
+            else:
+                ptrs[i] = None
+        out = np.empty((int(rp.height), int(rp.width), 3), np.uint8)
+        self._check(lib.render_compose(self.handle, C.byref(rp), k, barr, ptrs, out.ctypes.data, out.nbytes))
+        return out
+
     def grid(self) -> SphGridInfo:
         g = SphGridInfo()
         self._check(self.lib.grid(self.handle, C.byref(g)))
@@ -878,4 +950,25 @@ def group_slab_candidates_prepare(contexts, kind, params: SphParams, ap):
     out = [(int(rows[i]), int(tot[i])) for i in range(k)]
     for c, v in zip(contexts, out):
         c._slab_rows = v
+    return out
+
+
+def group_render(contexts, params: SphParams, rp: "SphRenderParams") -> np.ndarray:
+    """sph_group_render: the frame of the k slab contexts of this process (the group sph_group_step steps) as uint8[height, width, 3]:
+    every member draws its layer, member 0 merges them on the device."""
+    contexts = list(contexts)
+    if not contexts:
+        raise SphError(1, "sph_group_render: n < 1 (no contexts)")
+    lib = contexts[0].lib
+    if getattr(lib, "group_render", None) is None:
+        raise SphError(30, f"{lib.path.name} has no slab renderer (sph_slab_render.h is implemented by the product library only)")
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    out = np.empty((int(rp.height), int(rp.width), 3), np.uint8)
+    rc = lib.group_render(handles, k, C.byref(params) if params is not None else None, C.byref(rp) if rp is not None else None, out.ctypes.data, out.nbytes)
+    if rc != 0:
+        msgs = [c.lib.last_error(c.handle) for c in contexts]
+        raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+    for c in contexts:
+        c._layer_shape = None   # (the members' layers were redrawn; their bands stayed in the library)
     return out

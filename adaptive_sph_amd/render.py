@@ -235,6 +235,57 @@ def render_colors(ctx: ffi.Context, simulation_params, vis: VisualizationParams)
     return ctx.render_colors(p, render_params(vis, simulation_params, 1, 1))
 
 
+# ---- frames from slab contexts (include/sph_slab_render.h) ------------------------------------------------------------------
+def _slab_frame_params(name, simulation_params, vis, width, height, supersample, zoom_out, planes, alpha):
+    if alpha is not None:
+        raise ValueError(f"{name}: interpolated frames (alpha) are not drawn from slab contexts -- a particle may have changed rank since the snapshot")
+    p = simulation_params.to_ffi() if hasattr(simulation_params, "to_ffi") else simulation_params
+    return p, render_params(vis, simulation_params, width, height, supersample, zoom_out, boundary_segments(planes))
+
+
+def render_group(contexts, simulation_params, vis: VisualizationParams, width: int = 2000, height: int = 2000, supersample: int = 1,
+                 zoom_out: float = 1.04, planes=(), alpha: Optional[float] = None) -> np.ndarray:
+    """The frame of a slab group of ONE process (the contexts ffi.group_step steps) as uint8[height, width, 3]: byte for byte what
+    `render` draws for one context that holds the same particles.  Every member draws the particles it owns into a layer of
+    (id + 1) << 32 | rgb words, member 0 takes the per-sample maximum on the device (sph_group_render); only the frame crosses the bus."""
+    p, rp = _slab_frame_params("render_group", simulation_params, vis, width, height, supersample, zoom_out, planes, alpha)
+    return ffi.group_render(contexts, p, rp)
+
+
+def render_rank(ctx: ffi.Context, simulation_params, vis: VisualizationParams, width: int = 2000, height: int = 2000, supersample: int = 1,
+                zoom_out: float = 1.04, planes=(), alpha: Optional[float] = None, root: int = 0) -> Optional[np.ndarray]:
+    """The same frame with ONE PROCESS PER RANK: every rank calls this behind the same step.  The pressure maximum is all-gathered,
+    every rank draws its layer and sends `root` its (band, layer) through the launcher's process group (torch.distributed
+    gather_object, as distributed.rank_single_step_adaptivity_on_slabs sends its rows), `root` composes them on its own context.
+    Returns the frame on `root`, None elsewhere; a failure on the root is re-raised on every rank."""
+    import torch.distributed as dist
+    p, rp = _slab_frame_params("render_rank", simulation_params, vis, width, height, supersample, zoom_out, planes, alpha)
+    rank, world = dist.get_rank(), dist.get_world_size()
+    pmax = 0.0
+    if vis.visualized_attribute == "Pressure":
+        vals = [None] * world
+        dist.all_gather_object(vals, ctx.slab_render_pressure_max())
+        pmax = max(vals)   # (an f32 maximum: the same on every rank whatever the order)
+    band = ctx.slab_render_layer(p, rp, pmax)
+    layer = ctx.slab_render_layer_download() if band.sx1 > band.sx0 else None
+    parts = [None] * world if rank == root else None
+    dist.gather_object((band.as_tuple(), layer), parts, dst=root)
+    out, frame = [None], None
+    if rank == root:
+        try:
+            bands = [ffi.SphRenderBand(b[0], b[1], b[2], 0) for b, _ in parts]
+            frame = ctx.render_compose(rp, bands, [l for _, l in parts])
+        except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
+            out = [(type(e).__name__, e.status if isinstance(e, ffi.SphError) else None, str(e))]
+    dist.broadcast_object_list(out, src=root)
+    if out[0] is not None:
+        kind, code, msg = out[0]
+        if code is not None:
+            raise ffi.SphError(code, f"render failed on rank {root}: {msg}")
+        raise RuntimeError(f"render failed on rank {root} ({kind}): {msg}")
+    return frame
+
+
 def _u8(c) -> np.ndarray:
     return np.clip(np.floor(np.asarray(c, np.float32) * f32(255.0) + f32(0.5)), 0, 255).astype(np.uint8)
 
