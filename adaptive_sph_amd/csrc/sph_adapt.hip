@@ -352,7 +352,7 @@ int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* 
                        merging ? d_del.as<uint32_t>() : nullptr);
     int rc = check_status(c, "merge_partner holds an index outside the particle vector");
     // positions and masses changed: what the last step left behind no longer describes the state
-    c->hdr_ahead = false;
+    c->drop_ahead();
     c->grid_valid = false;
     if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
     c->inc_count_valid = false;   // (the incremental sort's last mover count belongs to the vector before this call)
@@ -704,7 +704,7 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
     c->have_level = false;
     c->have_reduced = false;
     c->lists_after = false;
-    c->hdr_ahead = false;
+    c->drop_ahead();
 }
 
 // op: 0 share, 1 merge, 2 split -- for every member of the group (collective over ALL ranks of the decomposition)
@@ -793,7 +793,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             HIPLOC(c, hipMemcpyAsync(c->vel[k].p, c->vel[k ^ 1].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
             int r2 = check_status(c, "merge_partner holds an index outside the particle vector, or a donor that is not a neighbour of its receiver");
             if (r2) local_rc = r2;
-            c->hdr_ahead = false;
+            c->drop_ahead();
             c->grid_valid = false;
             if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
     c->inc_count_valid = false;   // (the incremental sort's last mover count belongs to the vector before this call)

@@ -744,8 +744,7 @@ extern "C" int sph_set_math_policy(sph_ctx* c, int policy)
     c->grid_valid = false;
     c->export_valid = false;
     c->drop_slab_lists();
-    c->ahead.valid = false;
-    c->hdr_ahead = false;
+    c->drop_ahead();
     c->lists_after = false;
     if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
     c->inc_count_valid = false;
@@ -781,7 +780,7 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->have_level = false;
     c->have_reduced = false;
     c->lists_after = false;
-    c->hdr_ahead = false;
+    c->drop_ahead();
     c->rnd_have_prev = false;   // a render snapshot (sph_render.hip) belongs to the particle set it was taken from
     if (n == 0) return SPH_OK;
     // stage host arrays through scratch buffers: mass -> key[1], pos -> scratch, vel -> vel_tmp
@@ -1119,7 +1118,7 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     c->have_level = false;
     c->have_reduced = false;
     c->lists_after = false;
-    c->hdr_ahead = false;
+    c->drop_ahead();
     return SPH_OK;
 }
 
@@ -1134,7 +1133,7 @@ extern "C" int sph_upload_field(sph_ctx* c, int field, const void* src, uint64_t
     } else if (!field_ref(c, field, &r) || !r.uploadable)
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d cannot be uploaded", field);
     const uint32_t n = (uint32_t)c->n;
-    c->hdr_ahead = false;   // the header computed at the end of the last step no longer describes the state
+    c->drop_ahead();   // the header computed at the end of the last step no longer describes the state
     if (field == SPH_F_POSITION || field == SPH_F_MASS) c->export_valid = false;   // (the candidate export's lists: sph_candidates.hip)
     if (field == SPH_F_POSITION || field == SPH_F_MASS || field == SPH_F_PARTICLE_ID) c->drop_slab_lists();   // (sph_slab_candidates.hip: its entries become ids)
     if (bytes != (uint64_t)n * r.elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d: size mismatch", field);

@@ -250,6 +250,10 @@ struct sph_ctx {
     DevBuf hdr_ahead_partials;   // per sweep block: next step's header terms from the integrating final sweep
     bool hdr_ahead = false;      // hdr_host already holds the header of the state on the device (no k_header needed)
     float hdr_ahead_rest_density = 0.f;
+    // An entry point that writes particle state between two steps: neither the header nor the build the last step left behind for the
+    // next one describes the state any more (the step adopts the build only while that header is in force: sph_step.hip).  sph_classify
+    // writes the classes alone -- the header does not read them, the queued build carries a copy of them -- and drops the build only.
+    void drop_ahead() { hdr_ahead = false; ahead.valid = false; }
     DevBuf h2n[2];     // ParticleVec::h2_next (FromDistribution* support-length estimation), ping-pong across the reorder
     DevBuf lam_prev;   // lambda_sum of the previous step in this step's order (estimate_h_next_from_distribution)
     // level estimation (simulation.rs:539-927), sorted order

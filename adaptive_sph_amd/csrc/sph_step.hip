@@ -1903,6 +1903,9 @@ extern "C" int sph_classify(sph_ctx* c, const sph_params* p)
     const uint32_t n = flags ? c->dist.n_tot : (uint32_t)c->n;
     launch_classify(c->stream, &c->prof, n, c->pm[c->pcur].as<float4>(), c->lvl[c->cur].as<float>(), c->szc[c->cur].as<uint8_t>(),
                     flags ? c->dist.owned.as<uint8_t>() : nullptr, c->orig[c->cur].as<uint32_t>(), c->status.as<DeviceStatus>(), p);
+    // The build the last step queued for the next one (queue_ahead_build) has already copied the classes as they were BEFORE this call
+    // into the other half of the ping-pong set: a step that adopted it would flip to that half and lose the ones written here.
+    c->ahead.valid = false;
     Group G;
     G.m.push_back(c);
     int rc = sync_ctrl(G);   // surfaces the unreachable!() of a particle without a level value
@@ -1934,7 +1937,7 @@ extern "C" int sph_dist_configure(sph_ctx* c, int rank, int n_ranks, float cut_l
     c->dist.cut_lo = cut_lo;
     c->dist.cut_hi = cut_hi;
     c->dist.have_flags = false;
-    c->hdr_ahead = false;
+    c->drop_ahead();
     c->dist.n_tot = (uint32_t)c->n;
     if (c->dist.on) {
         HIPCHK(c, hipSetDevice(c->device));

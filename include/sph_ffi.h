@@ -364,7 +364,9 @@ int  sph_step(sph_ctx* ctx, const sph_params* params, sph_step_stats* out);
  * (simulation.rs:2749, 2764, 2778), never from the step: IISPH2's omega (simulation.rs:2277-2288) therefore reads whatever
  * the last adaptivity pass left behind (Optimal if there never was one).  Reads params->maximum_surface_distance,
  * rest_density, sizing_function, particle_radius_fine / _base.  A particle without a level value (FluidInterior) is
- * `unreachable!()` in the reference: SPH_ERR_INVALID_ARGUMENT here. */
+ * `unreachable!()` in the reference: SPH_ERR_INVALID_ARGUMENT here.  The classes it writes survive the following steps,
+ * whatever they are stepped with: they change only with the next sph_classify, an upload of the field or a call that
+ * replaces the particles (tests/test_gpu_call_sequences.py). */
 int  sph_classify(sph_ctx* ctx, const sph_params* params);
 
 /* Message for the last non-zero status of this context (what the Rust shim puts in panic!). */
