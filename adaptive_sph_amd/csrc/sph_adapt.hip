@@ -26,7 +26,7 @@
 static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter);
 #define ADAPT_CHECK(c, OP, PARTNER, COUNTER)                                                                                    \
     if (!(c) || !p || !ap) return SPH_ERR_INVALID_ARGUMENT;                                                                     \
-    if ((c)->poisoned) return (c)->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload"); \
+    if ((c)->poisoned) return (c)->refuse_poisoned();                                                                           \
     if ((c)->dist.on) return slab_adapt_rank((c), (OP), p, ap, (PARTNER), (COUNTER))
 
 // ---- exclusive prefix sum (u32), three launches: block sums, scan of the block sums, local scans ------------------------
@@ -352,11 +352,7 @@ int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* 
                        merging ? d_del.as<uint32_t>() : nullptr);
     int rc = check_status(c, "merge_partner holds an index outside the particle vector");
     // positions and masses changed: what the last step left behind no longer describes the state
-    c->drop_ahead();
-    c->grid_valid = false;
-    if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;   // (the incremental sort's last mover count belongs to the vector before this call)
-    c->lists_after = false;
+    c->drop(DROPS_TRANSFER);
     // (sharing neither reorders nor resizes the vector: stash and the step's flags keep describing the particles in their slots,
     //  as the reference's ParticleVec keeps them through share_particles -- snapshots taken after single_step show them)
     if (rc || !merging) {
@@ -373,8 +369,7 @@ int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* 
         release();
         return SPH_OK;
     }
-    c->have_level = false;    // the deletion reorders the vector: per-step outputs that do not travel (stash, flags) are gone
-    c->have_reduced = false;
+    c->drop(DROPS_DELETION);   // the deletion reorders the vector: per-step outputs that do not travel (stash, flags) are gone
     // (the reference's loop never removes the particle it ends on when everything is deleted: last_particle_id is a usize that
     //  would underflow -- it panics there; an empty vector is what truncate(0) would leave)
     const uint32_t n_new = n - n_del;
@@ -402,7 +397,7 @@ extern "C" int sph_share_particles(sph_ctx* c, const sph_params* p, const sph_ad
 extern "C" int sph_merge_particles(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter)
 {
     ADAPT_CHECK(c, 1, partner, counter);
-    c->export_valid = false;   // (the candidate export's lists index the vector before the deletions: sph_candidates.hip)
+    c->drop(DROPS_EXPORT_EARLY);   // (the candidate export's lists index the vector before the deletions: sph_candidates.hip)
     return transfer(c, p, ap, partner, counter, 1);
 }
 
@@ -422,7 +417,7 @@ extern "C" int sph_set_split_patterns(sph_ctx* c, uint32_t n_patterns, const flo
 extern "C" int sph_split_particles(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap)
 {
     ADAPT_CHECK(c, 2, nullptr, nullptr);
-    c->export_valid = false;
+    c->drop(DROPS_EXPORT_EARLY);
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t n = (uint32_t)c->n;
     if (n == 0) return SPH_OK;
@@ -695,16 +690,8 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
     c->pcur ^= 1;
     c->n = n_new;
     c->dist.n_tot = n_new;
-    c->dist.have_flags = false;
-    c->drop_slab_lists();   // (sph_slab_candidates.hip: the rows and slots of the vector before this call)
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
-    c->grid_valid = false;
-    if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;   // (the incremental sort's last mover count belongs to the vector before this call)
-    c->have_level = false;
-    c->have_reduced = false;
-    c->lists_after = false;
-    c->drop_ahead();
+    c->drop(DROPS_REGATHER);
 }
 
 // op: 0 share, 1 merge, 2 split -- for every member of the group (collective over ALL ranks of the decomposition)
@@ -724,8 +711,8 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
     const size_t nm = G.m.size();
     int rc = SPH_OK;
     for (auto c : G.m) {
-        if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
-        if (!c->dist.have_flags)
+        if (c->poisoned) return c->refuse_poisoned();
+        if (!c->have_flags)
             return c->fail(SPH_ERR_INVALID_ARGUMENT, "the adaptivity apply on a slab context follows a step (it reads the donors across a cut from that step's ghost layer)");
         if (op == 2 && c->n_split_patterns + 1u < 2u) return c->fail(SPH_ERR_NO_SPLIT_PATTERN, "no split pattern for a 1-to-2 split (sph_set_split_patterns was not called)");
     }
@@ -793,11 +780,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             HIPLOC(c, hipMemcpyAsync(c->vel[k].p, c->vel[k ^ 1].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
             int r2 = check_status(c, "merge_partner holds an index outside the particle vector, or a donor that is not a neighbour of its receiver");
             if (r2) local_rc = r2;
-            c->drop_ahead();
-            c->grid_valid = false;
-            if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;   // (the incremental sort's last mover count belongs to the vector before this call)
-            c->lists_after = false;
+            c->drop(DROPS_TRANSFER);
         }
         if ((rc = agree(G, local_rc))) return rc;
         if (!merging) return SPH_OK;

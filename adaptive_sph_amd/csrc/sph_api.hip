@@ -634,8 +634,9 @@ extern "C" int sph_create(uint64_t n_capacity, int device_id, const sph_plane* p
     if (hipEventCreateWithFlags(&c->ev_sync, hipEventDisableTiming) != hipSuccess) return bail(SPH_ERR_DEVICE);
     memset(c->status_host, 0, sizeof(DeviceStatus));
     memset((void*)c->ctrl_host, 0, 3 * sizeof(SolverCtrl));
-    c->prog_host = (volatile uint32_t*)(c->ctrl_host + 2);   // (the third block: only its first word is used)
+    c->prog_host = (volatile uint32_t*)(c->ctrl_host + 2);   // (the third block: its first two words are used)
     c->prog_host_dev = (uint32_t*)(c->ctrl_host_dev + 2);
+    c->movers_host = c->prog_host + 1;   // (the second word: the incremental sort's mover count)
     // BoundaryWinchenbach2020::new (boundary_winchenbach2020.rs:33-36)
     std::vector<float> lam, dlam;
     sph_lambda::build_luts(lam, dlam);
@@ -696,10 +697,11 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
-                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->export_d_off, &c->export_d_idx,
-                     &c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan, &c->cand_red, &c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos,
-                     &c->prob_h2, &c->prob_off, &c->prob_idx, &c->sol_partner, &c->sol_counter, &c->ps_w, &c->ps_words, &c->ps_state, &c->ps_rec, &c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage};
+                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage};
     for (auto b : all) b->release();
+    for (DevBuf* b : c->export_bufs()) b->release();
+    for (DevBuf* b : c->prob_bufs()) b->release();
+    for (DevBuf* b : c->slab_bufs()) b->release();
     if (c->hdr_host) (void)hipHostFree(c->hdr_host);
     if (c->ctrl_host) (void)hipHostFree(c->ctrl_host);
     if (c->status_host) (void)hipHostFree(c->status_host);
@@ -741,13 +743,7 @@ extern "C" int sph_set_math_policy(sph_ctx* c, int policy)
         HIPCHK(c, c->wall_pl.ensure(n * sizeof(float2) * SPH_MAX_PLANES));
         HIPCHK(c, c->wall_cnt.ensure(n));
     }
-    c->grid_valid = false;
-    c->export_valid = false;
-    c->drop_slab_lists();
-    c->drop_ahead();
-    c->lists_after = false;
-    if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;
+    c->drop(DROPS_POLICY);
     return SPH_OK;
 }
 extern "C" int sph_get_math_policy(const sph_ctx* c) { return c ? c->exact : -1; }
@@ -762,26 +758,11 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     c->cur = 0;
     c->pcur = 0;
     c->poisoned = false;
-    c->dist.have_flags = false;
     c->dist.n_tot = (uint32_t)n;
-    c->grid_valid = false;   // lists, cell indices and per-step outputs belong to the vector before this call
-    if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;   // ... and so does the incremental sort's last mover count (advisor r4)
-    c->export_d_off.release();   // (the CSR export's device buffers: a host that re-uploads is not exporting every step)
-    c->export_d_idx.release();
-    c->export_valid = false;
-    c->drop_slab_lists();
-    for (DevBuf* b : {&c->slab_row_slot, &c->slab_slot_row, &c->slab_off, &c->slab_idx}) b->release();
-    for (DevBuf* b : {&c->cand_rec, &c->cand_cls, &c->cand_cnt, &c->cand_off, &c->cand_idx, &c->cand_scan}) b->release();
-    for (DevBuf* b : {&c->prob_flag, &c->prob_rank, &c->prob_lvl, &c->prob_ids, &c->prob_cls, &c->prob_mass, &c->prob_level, &c->prob_pos, &c->prob_h2, &c->prob_off,
-                      &c->prob_idx, &c->sol_partner, &c->sol_counter, &c->ps_w, &c->ps_words, &c->ps_state, &c->ps_rec})
-        b->release();
-    c->prob_open = false;
-    c->have_level = false;
-    c->have_reduced = false;
-    c->lists_after = false;
-    c->drop_ahead();
-    c->rnd_have_prev = false;   // a render snapshot (sph_render.hip) belongs to the particle set it was taken from
+    c->drop(DROPS_UPLOAD);   // everything the last step left belongs to the vector before this call
+    for (DevBuf* b : c->export_bufs()) b->release();   // (a host that re-uploads is not exporting every step)
+    for (DevBuf* b : c->slab_bufs()) b->release();
+    for (DevBuf* b : c->prob_bufs()) b->release();
     if (n == 0) return SPH_OK;
     // stage host arrays through scratch buffers: mass -> key[1], pos -> scratch, vel -> vel_tmp
     HIPCHK(c, hipMemcpyAsync(c->key[1].p, mass, n * sizeof(float), hipMemcpyHostToDevice, s));
@@ -839,13 +820,13 @@ static bool field_ref(sph_ctx* c, int field, FieldRef* r)
 static int download_slab(sph_ctx* c, int kind, const void* src, size_t elem, void* dst, uint64_t bytes)
 {
     hipStream_t s = c->stream;
-    const uint32_t nt = c->dist.have_flags ? c->dist.n_tot : (uint32_t)c->n;
+    const uint32_t nt = c->have_flags ? c->dist.n_tot : (uint32_t)c->n;
     if (bytes != (uint64_t)c->n * elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "size mismatch (slab holds %llu particles)", (unsigned long long)c->n);
     if (nt == 0) return SPH_OK;
     std::vector<uint8_t> raw((size_t)nt * elem), flags(nt, 1);
     hipLaunchKernelGGL(k_to_host_order, dim3((nt + 255) / 256), dim3(256), 0, s, nt, kind, (const uint32_t*)nullptr, src, c->scratch.p);
     HIPCHK(c, hipMemcpyAsync(raw.data(), c->scratch.p, raw.size(), hipMemcpyDeviceToHost, s));
-    if (c->dist.have_flags) HIPCHK(c, hipMemcpyAsync(flags.data(), c->dist.owned.p, nt, hipMemcpyDeviceToHost, s));
+    if (c->have_flags) HIPCHK(c, hipMemcpyAsync(flags.data(), c->dist.owned.p, nt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     size_t w = 0;
     for (uint32_t i = 0; i < nt; i++)
@@ -995,10 +976,9 @@ __global__ __launch_bounds__(256) void k_edit_apply(uint32_t n_new, uint32_t n_o
 extern "C" int sph_apply_edits(sph_ctx* c, const sph_edit_op* ops, uint64_t n_ops)
 {
     if (!c || (n_ops && !ops)) return SPH_ERR_INVALID_ARGUMENT;
-    if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+    if (c->poisoned) return c->refuse_poisoned();
     HIPCHK(c, hipSetDevice(c->device));
-    c->export_valid = false;
-    c->drop_slab_lists();
+    c->drop(DROPS_EDITS_EARLY);
     const uint32_t n_old = (uint32_t)c->n;
     // ---- resolve the script: which object sits at which index, and the last value written to each field of an object
     std::vector<uint32_t> at(n_old);
@@ -1077,7 +1057,7 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     if (slab) {
         // slab context: "host index" = row of the owned order (what sph_download returns); the arrays also hold the ghosts
         std::vector<uint32_t> slot_of(n_old ? n_old : 1);
-        if (c->dist.have_flags) {
+        if (c->have_flags) {
             const uint32_t nt = c->dist.n_tot;
             std::vector<uint8_t> flags(nt ? nt : 1);
             if (nt) HIPCHK(c, hipMemcpy(flags.data(), c->dist.owned.p, nt, hipMemcpyDeviceToHost));
@@ -1108,17 +1088,8 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     c->pcur ^= 1;
     c->n = n_new;
     c->dist.n_tot = n_new;
-    c->dist.have_flags = false;   // (slab context: owned particles only, in row order; the next step selects new ghosts)
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
-    c->grid_valid = false;   // lists, cell indices and per-step outputs belong to the vector before this call
-    c->export_valid = false;
-    c->drop_slab_lists();
-    if (c->ctrl_host) ((uint32_t*)(c->ctrl_host + 2))[1] = 0u;
-    c->inc_count_valid = false;   // ... and so does the incremental sort's last mover count (advisor r4)
-    c->have_level = false;
-    c->have_reduced = false;
-    c->lists_after = false;
-    c->drop_ahead();
+    c->drop(DROPS_REGATHER);   // (slab context: owned particles only, in row order; the next step selects new ghosts)
     return SPH_OK;
 }
 
@@ -1133,13 +1104,12 @@ extern "C" int sph_upload_field(sph_ctx* c, int field, const void* src, uint64_t
     } else if (!field_ref(c, field, &r) || !r.uploadable)
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d cannot be uploaded", field);
     const uint32_t n = (uint32_t)c->n;
-    c->drop_ahead();   // the header computed at the end of the last step no longer describes the state
-    if (field == SPH_F_POSITION || field == SPH_F_MASS) c->export_valid = false;   // (the candidate export's lists: sph_candidates.hip)
-    if (field == SPH_F_POSITION || field == SPH_F_MASS || field == SPH_F_PARTICLE_ID) c->drop_slab_lists();   // (sph_slab_candidates.hip: its entries become ids)
+    static_assert(CARRY_F_MASS == SPH_F_MASS && CARRY_F_POSITION == SPH_F_POSITION && CARRY_F_PARTICLE_ID == SPH_F_PARTICLE_ID, "sph_carry.hpp: field codes");
+    c->drop(drops_upload_field(field));
     if (bytes != (uint64_t)n * r.elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d: size mismatch", field);
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
-    if (c->dist.on && c->dist.have_flags) {
+    if (c->dist.on && c->have_flags) {
         // a slab context behind a step: the rows are the OWNED particles in download order, the arrays also hold the ghosts (whose
         // values stay: they are refreshed from their owners whenever something reads them)
         const uint32_t nt = c->dist.n_tot;
@@ -1410,11 +1380,11 @@ extern "C" int sph_profile_list_forms(sph_ctx* c, sph_list_forms* out)
     if (!c || !out) return SPH_ERR_INVALID_ARGUMENT;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->grid_valid) return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists yet: run a step first");
-    const uint32_t n = c->dist.on && c->dist.have_flags ? c->dist.n_tot : (uint32_t)c->n;
+    const uint32_t n = c->dist.on && c->have_flags ? c->dist.n_tot : (uint32_t)c->n;
     TmpBuf acc;
     HIPCHK(c, acc.ensure(5 * sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(acc.p, 0, 5 * sizeof(unsigned long long), c->stream));
-    const bool flags = c->dist.on && c->dist.have_flags;
+    const bool flags = c->dist.on && c->have_flags;
     if (n)
         hipLaunchKernelGGL(k_list_forms, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->nl.as<uint4>(), flags ? c->dist.owned.as<uint8_t>() : nullptr,
                            flags ? c->dist.ring1.as<uint8_t>() : nullptr, acc.as<unsigned long long>());
@@ -1445,7 +1415,7 @@ extern "C" int sph_download_neighbors(sph_ctx* c, uint32_t* offsets, uint32_t* i
     if (c->dist.on) {
         // Slab context: one row per OWNED particle, in the order of sph_download(SPH_F_PARTICLE_ID); the indices are global particle
         // ids (an owned particle's neighbours are all among owned + ghosts, and the ghost records carry their ids).
-        if (!c->dist.have_flags) return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists yet: run a step first");
+        if (!c->have_flags) return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists yet: run a step first");
         const uint32_t nt = c->dist.n_tot;
         const bool ext = c->lists_after;   // (as on a plain context: the extended lists of the ADVECTED positions)
         std::vector<uint8_t> flags(nt);
@@ -1537,8 +1507,7 @@ extern "C" int sph_download_neighbors(sph_ctx* c, uint32_t* offsets, uint32_t* i
                            c->lists_after_k, (const uint32_t*)nullptr);
     HIPCHK(c, hipMemcpyAsync(indices, d_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (!c->export_valid) c->export_epoch++;   // (sph_partner_problem.hip: an open problem belongs to the lists it was made from)
-    c->export_valid = true;   // (sph_candidates.hip filters this CSR in place of building its own)
+    c->export_built();   // (sph_candidates.hip filters this CSR in place of building its own)
     c->export_tot = tot;
     return SPH_OK;
 }
@@ -1549,7 +1518,7 @@ int export_lists_on_device(sph_ctx* c)
     const uint32_t n = (uint32_t)c->n;
     hipStream_t s = c->stream;
     DevBuf &d_off = c->export_d_off, &d_idx = c->export_d_idx;
-    c->export_valid = false;
+    c->drop(CARRY_EXPORT);
     HIPCHK(c, d_off.ensure(((size_t)n + 1) * 4));
     HIPCHK(c, c->scratch.ensure((size_t)n * 4 + 4));
     HIPCHK(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
@@ -1575,8 +1544,7 @@ int export_lists_on_device(sph_ctx* c)
                                c->cxy.as<uint32_t>(), c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(), d_off.as<uint32_t>(), d_idx.as<uint32_t>(),
                                c->lists_after_k, (const uint32_t*)nullptr);
     }
-    c->export_epoch++;
-    c->export_valid = true;
+    c->export_built();
     c->export_tot = tot;
     return SPH_OK;
 }
@@ -1616,7 +1584,7 @@ int slab_lists_on_device(sph_ctx* c)
 {
     const uint32_t n = (uint32_t)c->n, nt = c->dist.n_tot;
     hipStream_t s = c->stream;
-    c->drop_slab_lists();
+    c->drop(CARRY_SLAB_LISTS);
     TmpBuf d_iota, d_cnt, d_tot64;
     HIPCHK(c, d_tot64.ensure(8));
     HIPCHK(c, hipMemsetAsync(d_tot64.p, 0, 8, s));

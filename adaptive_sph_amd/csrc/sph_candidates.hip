@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_cand_rows(uint32_t n, CandP q, const ui
 
 int cand_refuse_common(sph_ctx* c, const char* what)
 {
-    if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+    if (c->poisoned) return c->refuse_poisoned();
     if (c->dist.on)
         return c->fail(SPH_ERR_UNSUPPORTED, "%s: a slab context holds a slab of the particles (assemble the full lists: sph_download_neighbors per rank)", what);
     return SPH_OK;

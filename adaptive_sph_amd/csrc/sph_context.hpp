@@ -3,12 +3,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <vector>
 
+#include "sph_carry.hpp"
 #include "sph_internal.hpp"
 
 struct DevBuf {
@@ -87,7 +89,7 @@ struct Options {
 };
 Options options_from_env();   // sph_api.hip
 
-struct sph_ctx {
+struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its validity flags and what each entry point drops of them)
     int device = 0;
     Options opt;
     uint64_t cap = 0, n = 0;
@@ -107,17 +109,13 @@ struct sph_ctx {
     std::vector<uint32_t> export_cnt, export_off;   // sph_download_neighbors: host staging of the counts / offsets, kept across calls
     DevBuf export_d_off, export_d_idx;              // ... and its device-side CSR (a 200 MB hipMalloc + hipFree per call otherwise); freed by sph_destroy and by sph_upload
 
-    // sph_candidates.hip: export_d_off / export_d_idx hold the CSR of the LAST STEP's lists (export_tot entries).  Set when either export
-    // built it, kept by sph_share_particles (it renumbers nothing: the merge search that follows still iterates the step's lists),
-    // cleared by whatever replaces the lists or the vector they index (step, upload, position / mass upload, edits, merge, split, policy)
-    bool export_valid = false;
+    // sph_candidates.hip: export_d_off / export_d_idx hold the CSR of the LAST STEP's lists (export_tot entries) while export_valid.
+    // Which entry point drops export_valid, prob_open and the slab lists below: sph_carry.hpp, nowhere else.
     uint64_t export_tot = 0;
     DevBuf cand_rec, cand_cls, cand_cnt, cand_off, cand_idx, cand_scan, cand_red;   // host-order records / classes, counts, offsets, indices, scan and reduction scratch
-    // sph_partner_problem.hip: the compact partner problem.  export_epoch counts the times export_valid went from false to true, so
-    // "the lists are still those the problem was made from" is export_valid && prob_epoch == export_epoch without a hook in every
-    // call that drops the lists.  prob_ids[prob_k] (host indices, ascending) and prob_kind are the OPEN problem (prob_open).
-    uint64_t export_epoch = 0, prob_epoch = 0;
-    bool prob_open = false;
+    std::array<DevBuf*, 8> export_bufs() { return {&export_d_off, &export_d_idx, &cand_rec, &cand_cls, &cand_cnt, &cand_off, &cand_idx, &cand_scan}; }   // (released by sph_upload)
+    // sph_partner_problem.hip: the compact partner problem.  prob_ids[prob_k] (host indices, ascending) and prob_kind are the OPEN
+    // problem (prob_open: opened with export_valid, closed by whatever drops the export).
     int prob_kind = 0;
     uint32_t prob_k = 0;
     DevBuf prob_flag, prob_rank, prob_lvl, prob_ids, prob_cls, prob_mass, prob_level, prob_pos, prob_h2, prob_off, prob_idx;
@@ -126,17 +124,18 @@ struct sph_ctx {
     // arrays -- the writers CSR, head positions, donor states, dedupe stamps, the round lists and the progress record.
     uint64_t prob_serial = 0, sol_serial = 0;
     DevBuf sol_partner, sol_counter, ps_w, ps_words, ps_state, ps_rec;
+    std::array<DevBuf*, 17> prob_bufs() { return {&prob_flag, &prob_rank, &prob_lvl, &prob_ids, &prob_cls, &prob_mass, &prob_level, &prob_pos, &prob_h2, &prob_off, &prob_idx,
+                                                  &sol_partner, &sol_counter, &ps_w, &ps_words, &ps_state, &ps_rec}; }
     // sph_slab_candidates.hip: the same rows on a SLAB context, which the exports above refuse.  slab_off / slab_idx hold the CSR of the
     // last step's lists over the OWNED rows (the order of sph_download(SPH_F_PARTICLE_ID)) with SLOT indices as entries, slab_row_slot
     // the slot of every row.  Built by the first prepare behind a step -- the slab share overwrites pm[pcur ^ 1] and clears grid_valid,
-    // so it cannot be rebuilt behind one -- kept by the share (the slots stay where they are), dropped by drop_slab_lists() wherever
-    // export_valid is cleared and by the slab merge / split.  The prepared candidate rows themselves live in cand_cls (class byte per
-    // slot, ghosts included; behind them one per row), cand_cnt, cand_off and cand_idx, which a slab context has no other use for.
-    bool slab_lists_valid = false, slab_rows_open = false;
+    // so it cannot be rebuilt behind one -- and kept by the share (the slots stay where they are).  The prepared candidate rows
+    // themselves live in cand_cls (class byte per slot, ghosts included; behind them one per row), cand_cnt, cand_off and cand_idx,
+    // which a slab context has no other use for.
     uint32_t slab_lists_rows = 0, slab_rows_n = 0;
     uint64_t slab_lists_tot = 0, slab_rows_tot = 0;
     DevBuf slab_row_slot, slab_slot_row, slab_off, slab_idx;   // (slab_slot_row: the row of every slot, 0xffffffff for a ghost)
-    void drop_slab_lists() { slab_lists_valid = slab_rows_open = false; }
+    std::array<DevBuf*, 4> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx}; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];
@@ -173,14 +172,13 @@ struct sph_ctx {
         int rank = 0, nranks = 1;
         float cut_lo = 0.f, cut_hi = 0.f;
         uint32_t n_tot = 0;          // particles in the arrays incl. ghosts (== n when not distributed)
-        bool have_flags = false;     // `owned` describes the current arrays (after a step)
         uint32_t n_halo[2] = {0, 0}, n_ghost[2] = {0, 0};   // [left, right]
         // Ghost width PER CUT: H = the largest smoothing length among the particles of both ranks within the region a global-width
         // layer would span around the cut ([left, right]; agreed with the x-neighbour), layer width = base_k * H + slack.  A fine
         // region of a strongly multi-resolution scene then pays for its own support, not for the coarsest particle anywhere.
         float hcut[2] = {0.f, 0.f};     // of the current ghost layer (the next fused refresh predicts with it)
         float halo_w[2] = {0.f, 0.f};   // the widths the current layer was selected with
-        DevBuf owned;                // u8 per slot: 1 owned, 0 ghost
+        DevBuf owned;                // u8 per slot: 1 owned, 0 ghost; describes the current arrays while sph_ctx::have_flags (after a step)
         // fused refresh (sph_step.hip, slab_refresh_fused): class byte per slot of the previous step's arrays, per-block class
         // counts / offsets; `pre_*` describe the arrays between the refresh and the cell sort, which drops the slots that left
         DevBuf cls, blk;
@@ -221,7 +219,6 @@ struct sph_ctx {
     } dist;
 
     GridP grid{};
-    bool grid_valid = false;
     GridP fgrid{};          // the grid the particles are sorted by (== grid in uniform scenes)
     int tile_ts = 0, tile_tsx = 0, tile_tsy = 0;
     DevBuf tile_raw, tile_h, tile_h_ext, nlx;
@@ -238,30 +235,20 @@ struct sph_ctx {
     DevBuf inc_head, inc_next, inc_bsum, inc_movers;
     uint32_t inc_epoch = 0;     // tag of the current call's list heads
     int inc_radix_streak = 0;   // ahead builds in a row that took the radix sort because the last known mover count was large
-    bool inc_count_valid = false;   // the mapped mover-count word was written by a merge queued SINCE the state was last replaced (upload, edits,
-                                    // adaptivity, math policy): a build still in flight at such a call may write its stale count after the host's reset (advisor r5)
-    struct Ahead {
-        bool valid = false;
+    struct Ahead {   // the build queued while ahead_valid
         GridP g{};
         float h_max = 0.f, h_min = 0.f, rest_density = 0.f;
         int tile_ts = 0, tile_tsx = 0, tile_tsy = 0;   // multi-resolution scenes: the tiles of the predicted grid
         uint64_t n = 0;
     } ahead;
     DevBuf hdr_ahead_partials;   // per sweep block: next step's header terms from the integrating final sweep
-    bool hdr_ahead = false;      // hdr_host already holds the header of the state on the device (no k_header needed)
-    float hdr_ahead_rest_density = 0.f;
-    // An entry point that writes particle state between two steps: neither the header nor the build the last step left behind for the
-    // next one describes the state any more (the step adopts the build only while that header is in force: sph_step.hip).  sph_classify
-    // writes the classes alone -- the header does not read them, the queued build carries a copy of them -- and drops the build only.
-    void drop_ahead() { hdr_ahead = false; ahead.valid = false; }
+    float hdr_ahead_rest_density = 0.f;   // (of the header computed ahead: hdr_ahead)
     DevBuf h2n[2];     // ParticleVec::h2_next (FromDistribution* support-length estimation), ping-pong across the reorder
     DevBuf lam_prev;   // lambda_sum of the previous step in this step's order (estimate_h_next_from_distribution)
     // level estimation (simulation.rs:539-927), sorted order
     DevBuf lvl_queue;   // the propagation's compacted frontier: two transposed candidate maps, one byte per particle (sph_sweeps.hip: k_level_frontier)
     DevBuf lvl_tmp, lvl_nrm, lvl_state, lvl_when, lvl_mark, flag_surface, flag_insufficient, stash, nl_ext, nlx_ext;
     DevBuf con_thr, con_consumed, con_h, flag_reduced;   // constrain_neighborhood_count
-    bool have_reduced = false;
-    bool lists_after = false;        // the cache holds the extended lists of the advected positions (level_estimation_after_advection)
     float lists_after_k = 0.f, lists_after_slack = 0.f;
     float h_max_step = 0.f;   // largest smoothing length of the current step (all ranks)
     float last_dmax = 0.f;    // slab decomposition, level estimation after advection: largest displacement of the previous step (all ranks)
@@ -270,7 +257,6 @@ struct sph_ctx {
     DevBuf omega;      // IISPH2 (simulation.rs:2262-2311)
     DevBuf split_patterns;            // SplitPatterns::pos_s of every pattern, concatenated float2 (sph_set_split_patterns)
     uint32_t n_split_patterns = 0;
-    bool have_level = false;            // the level-estimation outputs above are those of the last step
     DevBuf lvl_changed_d;               // per-sweep "assigned something" words of a batch (device), published once per batch
     uint32_t* lvl_changed = nullptr;    // mapped pinned host copy
     uint32_t last_level_sweeps = 0;     // effective propagation sweeps of the previous step (length of the next first batch)
@@ -283,7 +269,6 @@ struct sph_ctx {
     // positions kept for an interpolated frame (sph_render_snapshot) -- allocated on first use, kept across frames, freed by sph_destroy
     DevBuf rnd_rec, rnd_keys, rnd_out, rnd_max, rnd_prev;
     uint64_t rnd_prev_n = 0;
-    bool rnd_have_prev = false;
     // frames from slab contexts (sph_slab_render.hip): this rank's layer -- rnd_layer_hs rows of the sample columns [rnd_layer_sx0,
     // rnd_layer_sx1), one 64-bit word per sample -- kept until the next layer call; the three words of the band reduction; the
     // WS x HS words a compose merges the layers into, and the staging of layers that arrive from the host
@@ -302,6 +287,7 @@ struct sph_ctx {
         err = buf;
         return code;
     }
+    int refuse_poisoned() { return fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload"); }
 };
 
 #define HIPCHK(ctx, call)                                                                                  \
@@ -322,9 +308,9 @@ void launch_publish(sph_ctx* c);
 void launch_profile_calibration(sph_ctx* c);   // Profiler mode 1: one spin kernel of known duration per step (sph_api.hip)
 void launch_check_neighborhood(sph_ctx* c, const SweepArgs& a);
 // The CSR of the last step's lists (the rows of sph_download_neighbors) into export_d_off / export_d_idx without a host copy of the
-// counts or the indices; sets export_valid / export_tot.  One context, grid_valid (sph_candidates.hip checks both).
+// counts or the indices; sets export_valid / export_tot (a rebuild: it closes the open problem).  One context, grid_valid (sph_candidates.hip checks both).
 int export_lists_on_device(sph_ctx* c);
-// The same on a slab context behind a step (dist.have_flags, grid_valid): slab_off / slab_idx / slab_row_slot, entries = slot indices;
+// The same on a slab context behind a step (have_flags, grid_valid): slab_off / slab_idx / slab_row_slot, entries = slot indices;
 // sets slab_lists_valid / slab_lists_rows / slab_lists_tot (sph_slab_candidates.hip checks the preconditions).
 int slab_lists_on_device(sph_ctx* c);
 void dist_release(sph_ctx* c);  // sph_step.hip

@@ -155,7 +155,6 @@ void prob_open_problem(sph_ctx* c, int kind, uint32_t K)
     c->prob_open = true;
     c->prob_kind = kind;
     c->prob_k = K;
-    c->prob_epoch = c->export_epoch;
     c->prob_serial++;   // (a solution of an earlier problem is not one of this problem: sph_partner_search.hip)
 }
 
@@ -207,7 +206,6 @@ static int apply_compact(sph_ctx* c, const sph_params* p, const sph_adapt_params
     if (!c || !p || !ap) return SPH_ERR_INVALID_ARGUMENT;
     if (int rc = cand_refuse_common(c, what)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->prob_open && (!c->export_valid || c->prob_epoch != c->export_epoch)) c->prob_open = false;   // the lists it was made from are gone
     if (!c->prob_open) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: no open problem (sph_download_partner_problem comes first; a step, an upload, an edit, a merge or a split closes it)", what);
     if (c->prob_kind != merging) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: the open problem is of kind %d", what, c->prob_kind);
     if (k != c->prob_k) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: k=%llu, the open problem has %u participants", what, (unsigned long long)k, c->prob_k);
@@ -218,7 +216,7 @@ static int apply_compact(sph_ctx* c, const sph_params* p, const sph_adapt_params
             return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: partner_c holds an id outside the problem (compact id %llu: %u)", what, (unsigned long long)i, partner_c[i]);
     c->prob_open = false;   // consumed
     const uint32_t n = (uint32_t)c->n, K = (uint32_t)k;
-    if (merging) c->export_valid = false;   // (as sph_merge_particles: the lists index the vector before the deletions)
+    if (merging) c->drop(DROPS_EXPORT_EARLY);   // (as sph_merge_particles: the lists index the vector before the deletions)
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
     TmpBuf d_partner, d_counter, d_pc, d_cc;

@@ -421,7 +421,6 @@ __global__ __launch_bounds__(256) void k_ps_validate(PsP P, const uint8_t* __res
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 static bool solution_open(sph_ctx* c)
 {
-    if (c->prob_open && (!c->export_valid || c->prob_epoch != c->export_epoch)) c->prob_open = false;   // the lists it was made from are gone
     return c->prob_open && c->sol_serial == c->prob_serial;
 }
 
@@ -578,7 +577,7 @@ static int apply_device(sph_ctx* c, const sph_params* p, const sph_adapt_params*
     if (c->prob_kind != merging) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: the open solution is of kind %d", what, c->prob_kind);
     c->prob_open = false;   // consumed, and the solution with it
     const uint32_t n = (uint32_t)c->n, K = c->prob_k;
-    if (merging) c->export_valid = false;   // (as sph_merge_particles: the lists index the vector before the deletions)
+    if (merging) c->drop(DROPS_EXPORT_EARLY);   // (as sph_merge_particles: the lists index the vector before the deletions)
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;
     TmpBuf d_partner, d_counter;

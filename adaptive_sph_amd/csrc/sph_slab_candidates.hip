@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_
 static int slab_cand_refuse(sph_ctx* c, const char* what)
 {
     if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (a plain context takes sph_download_partner_candidates / sph_sum_mass)", what);
-    if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+    if (c->poisoned) return c->refuse_poisoned();
     return SPH_OK;
 }
 
@@ -115,7 +115,7 @@ static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_
     for (size_t i = 0; i < nm && !local_rc; i++) {
         sph_ctx* c = G.m[i];
         c->slab_rows_open = false;   // (a slab context, not poisoned: both entry points and the loop above have seen to it)
-        if (!c->dist.have_flags) {
+        if (!c->have_flags) {
             local_rc = c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare follows a step (it filters that step's lists and reads the neighbours across a cut from its ghost layer)");
             break;
         }
@@ -279,6 +279,6 @@ extern "C" int sph_slab_sum_mass(sph_ctx* c, double* total)
     if (int rc = slab_cand_refuse(c, "sph_slab_sum_mass")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // (behind a step the arrays also hold the ghosts: k_sum_mass's tree over all slots, a ghost adding 0.0)
-    const bool flags = c->dist.have_flags;
+    const bool flags = c->have_flags;
     return cand_sum_mass(c, flags ? c->dist.n_tot : (uint32_t)c->n, flags ? c->dist.owned.as<uint8_t>() : nullptr, total);
 }

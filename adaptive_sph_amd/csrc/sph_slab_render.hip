@@ -138,13 +138,13 @@ __global__ __launch_bounds__(256) void k_slab_frame_resolve(const u64* __restric
 int slab_refuse(sph_ctx* c, const char* what)
 {
     if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (sph_render draws a plain context)", what);
-    if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+    if (c->poisoned) return c->refuse_poisoned();
     return SPH_OK;
 }
 
 // slots in the arrays and their ownership flags: behind a step owned + ghosts, else the owned particles alone
-uint32_t slab_slots(const sph_ctx* c) { return c->dist.have_flags ? c->dist.n_tot : (uint32_t)c->n; }
-const uint8_t* slab_owned(const sph_ctx* c) { return c->dist.have_flags ? c->dist.owned.as<uint8_t>() : nullptr; }
+uint32_t slab_slots(const sph_ctx* c) { return c->have_flags ? c->dist.n_tot : (uint32_t)c->n; }
+const uint8_t* slab_owned(const sph_ctx* c) { return c->have_flags ? c->dist.owned.as<uint8_t>() : nullptr; }
 
 // everything a layer call refuses, in sph_render's order where it refuses the same
 int check_layer(sph_ctx* c, const char* what, const sph_params* p, const sph_render_params* rp)
@@ -156,7 +156,7 @@ int check_layer(sph_ctx* c, const char* what, const sph_params* p, const sph_ren
     if (int rc = check_attribute(c, rp)) return rc;
     if (rp->attribute == SPH_VIS_MIN_DISTANCE_TO_NEIGHBOR) {
         // (the guards of sph_download_neighbors on a slab context)
-        if (!c->grid_valid || !c->dist.have_flags)
+        if (!c->grid_valid || !c->have_flags)
             return c->fail(SPH_ERR_INVALID_ARGUMENT, "render: MinDistanceToNeighbor needs the neighbour lists of a step (none since the last change of the particle set)");
         // the ghost lanes do not integrate: their advected records are their owners' only where the step's level estimation refreshed them
         if (!c->have_level)

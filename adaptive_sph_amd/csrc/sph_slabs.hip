@@ -601,13 +601,13 @@ int partition_and_migrate(Group& G, std::vector<Member>& M, std::vector<int>* mo
         auto& d = c->dist;
         (void)hipSetDevice(c->device);
         if ((rc = ensure_dist_buffers(c, m.n))) return rc;
-        const uint32_t n_prev = d.have_flags ? d.n_tot : (uint32_t)c->n;
+        const uint32_t n_prev = c->have_flags ? d.n_tot : (uint32_t)c->n;
         n_prev_of.push_back(n_prev);
         (void)hipMemsetAsync(d.counts.p, 0, 64, c->stream);
         if (n_prev) {
             ProfScope ps(&c->prof, "slab_partition", c->stream);
             hipLaunchKernelGGL(k_classify_migrate, dim3((n_prev + 255) / 256), dim3(256), 0, c->stream, n_prev, c->pm[c->pcur].as<float4>(),
-                               d.have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, d.cut_lo, d.cut_hi, d.rank > 0 ? 1 : 0,
+                               c->have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, d.cut_lo, d.cut_hi, d.rank > 0 ? 1 : 0,
                                d.rank + 1 < d.nranks ? 1 : 0, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), d.counts.as<uint32_t>(),
                                d.halo_w[0], d.halo_w[1]);   // the x-neighbour's slab is at least as wide as its ghost layer at the shared cut -- the previous layer's width (0: unknown, every migrant may need another hand-over)
             int res = radix_sort_pairs(c->stream, &c->prof, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), c->key[1].as<uint32_t>(),
@@ -679,7 +679,7 @@ int partition_and_migrate(Group& G, std::vector<Member>& M, std::vector<int>* mo
                                    c->lvl[k].as<float>(), c->lvlold[k].as<float>(), c->h2n[k].as<float>(), c->lam_sum.as<float>(),
                                    c->szc[k].as<uint8_t>());
         c->n = n_stay + cnt[0] + cnt[1];
-        d.have_flags = false;
+        c->have_flags = false;
         d.n_tot = (uint32_t)c->n;
         M[i].n = (uint32_t)c->n;
     }
@@ -701,13 +701,13 @@ int rebalance_cuts(Group& G, std::vector<Member>& M, bool* applied)
         (void)hipSetDevice(c->device);
         if ((rc = ensure_dist_buffers(c, m.n))) return rc;
         HIPCHK(c, d.hist.ensure(REBALANCE_BINS * 4));
-        const uint32_t n_prev = d.have_flags ? d.n_tot : (uint32_t)c->n;
+        const uint32_t n_prev = c->have_flags ? d.n_tot : (uint32_t)c->n;
         uint32_t* mm = d.counts.as<uint32_t>() + 8;
         const uint32_t init[2] = {0xffffffffu, 0u};
         HIPCHK(c, hipMemcpyAsync(mm, init, 8, hipMemcpyHostToDevice, c->stream));
         if (n_prev)
             hipLaunchKernelGGL(k_minmax_x, dim3((n_prev + 255) / 256), dim3(256), 0, c->stream, n_prev, c->pm[c->pcur].as<float4>(),
-                               d.have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, mm);
+                               c->have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, mm);
         HIPCHK(c, hipMemcpyAsync(d.counts_host + 8, mm, 8, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = agree(G, wait_all(G)))) return rc;
@@ -729,11 +729,11 @@ int rebalance_cuts(Group& G, std::vector<Member>& M, bool* applied)
         auto& d = c->dist;
         (void)hipSetDevice(c->device);
         ProfScope ps(&c->prof, "slab_rebalance", c->stream);
-        const uint32_t n_prev = d.have_flags ? d.n_tot : (uint32_t)c->n;
+        const uint32_t n_prev = c->have_flags ? d.n_tot : (uint32_t)c->n;
         (void)hipMemsetAsync(d.hist.p, 0, REBALANCE_BINS * 4, c->stream);
         if (n_prev)
             hipLaunchKernelGGL(k_hist_x, dim3((n_prev + 255) / 256), dim3(256), 0, c->stream, n_prev, c->pm[c->pcur].as<float4>(),
-                               d.have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, gmin, binw, d.hist.as<uint32_t>());
+                               c->have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, gmin, binw, d.hist.as<uint32_t>());
         HIPCHK(c, hipMemcpyAsync(hist[i].data(), d.hist.p, REBALANCE_BINS * 4, hipMemcpyDeviceToHost, c->stream));
     }
     if ((rc = agree(G, wait_all(G)))) return rc;
@@ -916,7 +916,7 @@ int slab_refresh_fused(Group& G, std::vector<Member>& M, std::vector<std::vector
         auto& d = c->dist;
         (void)hipSetDevice(c->device);
         if ((rc = ensure_dist_buffers(c, M[i].n))) return rc;
-        const uint32_t n_prev = d.have_flags ? d.n_tot : (uint32_t)c->n;
+        const uint32_t n_prev = c->have_flags ? d.n_tot : (uint32_t)c->n;
         n_prev_of[i] = n_prev;
         if (!(c->h_max_step > 0.f) || c->h_max_step != h_pred) fallback = 1;
         // the layer widths as the previous step's H per cut predicts them (agreed with the neighbours then; compared with this step's
@@ -936,7 +936,7 @@ int slab_refresh_fused(Group& G, std::vector<Member>& M, std::vector<std::vector
         ProfScope ps(&c->prof, "slab_refresh", c->stream);
         if (n_prev)
             hipLaunchKernelGGL(k_slab_classify, dim3(nb), dim3(256), 0, c->stream, n_prev, c->pm[c->pcur].as<float4>(),
-                               d.have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, d.cut_lo, d.cut_hi, w_l, w_r, region, has_l ? 1 : 0, has_r ? 1 : 0,
+                               c->have_flags ? d.owned.as<uint8_t>() : (const uint8_t*)nullptr, d.cut_lo, d.cut_hi, w_l, w_r, region, has_l ? 1 : 0, has_r ? 1 : 0,
                                d.cls.as<uint8_t>(), d.blk.as<uint32_t>(), d.counts.as<uint32_t>());
         hipLaunchKernelGGL(k_slab_scan, dim3(1), dim3(1024), 0, c->stream, nb, d.blk.as<uint32_t>(), d.blk.as<uint32_t>() + (size_t)nb * 4,
                            d.counts.as<uint32_t>(), d.counts.as<uint32_t>() + 16, rs);
@@ -1075,7 +1075,7 @@ int slab_refresh_fused(Group& G, std::vector<Member>& M, std::vector<std::vector
         d.pre_n = own_end + ng_slots;
         c->n = n_stay + n_in;
         d.n_tot = (uint32_t)c->n + ng_slots;
-        d.have_flags = false;
+        c->have_flags = false;
         M[i].n = d.n_tot;
         M[i].n_sort = d.pre_n;
         // (halo_pos is not cleared: k_build_maps consults it for halo members only -- class byte 1 / 2, or an arrival)
@@ -1118,7 +1118,7 @@ int slab_maps_after_sort(sph_ctx* c, uint32_t n, bool pre, hipStream_t s)
     if (n && ng_seed)
         hipLaunchKernelGGL(k_seed_ghost_records, dim3((ng_seed + 255) / 256), dim3(256), 0, s, d.ghost_dst.as<uint32_t>(), ng_seed,
                            c->pm[c->pcur].as<float4>(), c->pacc.as<float4>(), c->prec0.as<float4>(), c->prec1.as<float4>());
-    d.have_flags = true;
+    c->have_flags = true;
     return SPH_OK;
 }
 

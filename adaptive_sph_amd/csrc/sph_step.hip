@@ -802,7 +802,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         return c0->fail(SPH_ERR_UNSUPPORTED, "level_estimation_range / 1.9 = %g < 2: the reference then steps on lists narrower than the SPH support, which this build does not cover",
                         (double)(p->level_estimation_range / SPH_ETA));
     for (auto c : G.m)
-        if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+        if (c->poisoned) return c->refuse_poisoned();
     *started = true;   // from here on a failure leaves the state half-stepped
     // measurement / test switches of the solves, read ONCE per step (never inside the iteration path)
     const bool no_records = c0->opt.accel_generic != 0;   // sweep A through the generic form
@@ -867,8 +867,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             sph_ctx* c = m.c;
             if (header_ready(c)) continue;
             (void)hipSetDevice(c->device);
-            const uint32_t n_prev = c->dist.have_flags ? c->dist.n_tot : (uint32_t)c->n;
-            launch_header(c, n_prev, p->rest_density, h_from_mass_mode ? 1 : 2, c->hdr_host_dev, c->dist.have_flags ? c->dist.owned.as<uint8_t>() : nullptr);
+            const uint32_t n_prev = c->have_flags ? c->dist.n_tot : (uint32_t)c->n;
+            launch_header(c, n_prev, p->rest_density, h_from_mass_mode ? 1 : 2, c->hdr_host_dev, c->have_flags ? c->dist.owned.as<uint8_t>() : nullptr);
             launched = true;
         }
         if (launched) hdr_rc = wait_all_hinted(G);   // (first step, after uploads, FromDistribution*: the values must be on the host before the all-reduce)
@@ -1008,12 +1008,11 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // arrivals follow unsorted -- the stable sort is the merge of sph_sort.hip (incremental_cell_sort_perm) with the arrivals as
         // movers, if they and the particles that changed cell last time are few; same keys, permutation and cell ranges as the radix sort.
         const uint32_t n_prev = pre ? c->dist.pre_cls_n : 0u;
-        uint32_t* movers_host = (uint32_t*)(c->ctrl_host + 2) + 1;
         bool merge = pre && c->opt.inc_sort && prev_valid && prev_grid.cs == g.cs && prev_grid.ncells > 0 && n_prev > 0 && n_prev <= n_sort && !c->exact &&
                      inc_sort_fits(g.ncells, n_sort);
         if (merge) {   // (the arrivals are movers of THIS build, whatever the last count was: too many of them do not touch the streak)
             const uint32_t limit = inc_sort_mover_limit(n_sort, c->opt.inc_sort);
-            merge = n_sort - n_prev <= limit && inc_sort_worthwhile(c->inc_count_valid, *movers_host, limit, c->inc_radix_streak);
+            merge = n_sort - n_prev <= limit && inc_sort_worthwhile(c->inc_count_valid, *c->movers_host, limit, c->inc_radix_streak);
         }
         if (!merge) HIPCHK(c, c->cell_start.ensure(((size_t)g.ncells + 1) * sizeof(uint32_t)));
         // the build the previous step queued ahead (queue_ahead_build): adopted if nothing touched the state since (the header that
@@ -1022,11 +1021,11 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // (a multi-resolution scene: the same smoothing lengths, hence the same cell size and tile side; its tiles then lie on the
         //  predicted grid -- another tiling bounds the neighbours' h as well, and the visiting order of a list does not depend on the
         //  stencil width it was gathered with)
-        const bool adopt = ahead_usable && c->ahead.valid && !c->dist.on && c->ahead.n == c->n && n == (uint32_t)c->n && c->ahead.h_max == h_max_g &&
+        const bool adopt = ahead_usable && c->ahead_valid && !c->dist.on && c->ahead.n == c->n && n == (uint32_t)c->n && c->ahead.h_max == h_max_g &&
                            c->ahead.h_min == h_min_g && c->ahead.rest_density == p->rest_density && (c->uniform_h ? c->tile_ts == 0 : c->tile_ts > 0) &&
                            c->ahead.tile_ts == c->tile_ts && !c->exact && ag.cs == g.cs && g.minx >= ag.minx && g.miny >= ag.miny &&
                            g.minx + g.sx <= ag.minx + ag.sx && g.miny + g.sy <= ag.miny + ag.sy;
-        c->ahead.valid = false;
+        c->ahead_valid = false;
         if (adopt) {
             if (c->tile_ts > 0) {
                 c->tile_tsx = c->ahead.tile_tsx;
@@ -1403,7 +1402,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         for (auto& m : M) {
             sph_ctx* c = m.c;
             (void)hipSetDevice(c->device);
-            if (m.n) launch_header(c, m.n, p->rest_density, 0, c->hdr_host_dev, c->dist.on && c->dist.have_flags ? c->dist.owned.as<uint8_t>() : nullptr);
+            if (m.n) launch_header(c, m.n, p->rest_density, 0, c->hdr_host_dev, c->dist.on && c->have_flags ? c->dist.owned.as<uint8_t>() : nullptr);
         }
         if ((rc = sync_ctrl(G))) return rc;
         for (size_t i = 0; i < M.size(); i++)
@@ -1523,9 +1522,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // merge of the ones that stay with the ones that do not (sph_sort.hip: incremental_cell_sort_reorder) -- the same keys, order
         // and cell ranges as the radix sort, whatever the number of movers; its cost grows with them, so a large count (the last one
         // the device reported: a step or two old) sends the build through the radix sort, and every eighth such build probes again.
-        const uint32_t* movers_host = (const uint32_t*)(c->ctrl_host + 2) + 1;   // (second word of the mapped block whose first word is the paced solves' progress)
         if (!(c->opt.inc_sort && c->grid_valid && c->fgrid.cs == cs && c->fgrid.ncells > 0 && inc_sort_fits(g.ncells, n) &&
-              inc_sort_worthwhile(c->inc_count_valid, *movers_host, inc_sort_mover_limit(n, c->opt.inc_sort), c->inc_radix_streak)))
+              inc_sort_worthwhile(c->inc_count_valid, *c->movers_host, inc_sort_mover_limit(n, c->opt.inc_sort), c->inc_radix_streak)))
             return SPH_OK;
         if ((rc = ensure_inc_sort_scratch(c, g.ncells))) return rc;
         plan.incremental = true;
@@ -1540,7 +1538,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     const std::function<int()> queue_ahead_build = [&]() -> int {
         sph_ctx* c = c0;
         if (ahead_deferred) return SPH_OK;
-        c->ahead.valid = false;
+        c->ahead_valid = false;
         if (!plan.on) return SPH_OK;
         const uint32_t n = M[0].n;
         const GridP g = plan.g;
@@ -1560,7 +1558,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         if (plan.tile_ts > 0)
             launch_tile_hmax(s, &c->prof, n, c->pm2.as<float4>(), g, plan.tile_ts, plan.tile_tsx, plan.tile_tsy, c->atile_raw.as<uint32_t>(), c->atile_h.as<uint32_t>(),
                              nullptr, 1);
-        c->ahead.valid = true;
+        c->ahead_valid = true;
         c->ahead.g = g;
         c->ahead.h_max = h_max_g;
         c->ahead.h_min = h_min_g;
@@ -1860,15 +1858,12 @@ static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool*
         }
     }
     bool started = false;
-    for (auto c : G.m) {   // (sph_candidates.hip, sph_slab_candidates.hip: the exported CSR holds the lists of the step before this one)
-        c->export_valid = false;
-        c->drop_slab_lists();
-    }
+    for (auto c : G.m) c->drop(DROPS_STEP_START);   // (sph_candidates.hip, sph_slab_candidates.hip: the exported CSR holds the lists of the step before this one)
     const int rc = group_step_inner(G, p, outs, &started);
     if (rc && started)
         for (auto c : G.m) {
             c->poisoned = true;
-            c->hdr_ahead = false;
+            c->drop(DROPS_STEP_FAILED);
             (void)hipSetDevice(c->device);
             if (c->stream2) (void)hipStreamSynchronize(c->stream2);   // a level estimation may still be running on the side stream
             if (c->dist.xstream) (void)hipStreamSynchronize(c->dist.xstream);   // ... or the interior half of a split sweep A
@@ -1897,15 +1892,15 @@ extern "C" int sph_step(sph_ctx* c, const sph_params* p, sph_step_stats* out)
 extern "C" int sph_classify(sph_ctx* c, const sph_params* p)
 {
     if (!c || !p) return SPH_ERR_INVALID_ARGUMENT;
-    if (c->poisoned) return c->fail(SPH_ERR_POISONED, "an earlier step failed inside the step: the particle state is undefined until sph_upload");
+    if (c->poisoned) return c->refuse_poisoned();
     HIPCHK(c, hipSetDevice(c->device));
-    const bool flags = c->dist.on && c->dist.have_flags;
+    const bool flags = c->dist.on && c->have_flags;
     const uint32_t n = flags ? c->dist.n_tot : (uint32_t)c->n;
     launch_classify(c->stream, &c->prof, n, c->pm[c->pcur].as<float4>(), c->lvl[c->cur].as<float>(), c->szc[c->cur].as<uint8_t>(),
                     flags ? c->dist.owned.as<uint8_t>() : nullptr, c->orig[c->cur].as<uint32_t>(), c->status.as<DeviceStatus>(), p);
     // The build the last step queued for the next one (queue_ahead_build) has already copied the classes as they were BEFORE this call
     // into the other half of the ping-pong set: a step that adopted it would flip to that half and lose the ones written here.
-    c->ahead.valid = false;
+    c->drop(DROPS_CLASSIFY);
     Group G;
     G.m.push_back(c);
     int rc = sync_ctrl(G);   // surfaces the unreachable!() of a particle without a level value
@@ -1936,8 +1931,7 @@ extern "C" int sph_dist_configure(sph_ctx* c, int rank, int n_ranks, float cut_l
     c->dist.nranks = n_ranks;
     c->dist.cut_lo = cut_lo;
     c->dist.cut_hi = cut_hi;
-    c->dist.have_flags = false;
-    c->drop_ahead();
+    c->drop(DROPS_DIST_CONFIGURE);
     c->dist.n_tot = (uint32_t)c->n;
     if (c->dist.on) {
         HIPCHK(c, hipSetDevice(c->device));
