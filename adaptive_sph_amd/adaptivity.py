@@ -321,6 +321,31 @@ def expand_partner_decisions(n: int, ids, mp_c, mc_c) -> Tuple[np.ndarray, np.nd
     return merge_partner, merge_counter
 
 
+def slab_partner_problem_reference(owned_ids, cand_offsets, cand_indices, size_class, mass, level, position, h2) -> dict:
+    """The contract of ONE RANK's local problem (include/sph_slab_partner_problem.h) in numpy: `owned_ids` the rank's particles in the
+    order of download("particle_id"), `cand_offsets` / `cand_indices` its candidate rows (one per owned particle, entries in global ids:
+    sph_slab_candidates_download, or `partner_candidates_reference` on the whole vector restricted to the rank's rows), the five fields
+    of the WHOLE vector by global id (what every particle's owner holds).  Participants: the owned particles with a non-empty row or
+    named by an entry, in the order of `owned_ids`; behind them the entries' particles of other ranks -- here in ascending id, the
+    library's order among them is its own.  -> the dict Context.slab_partner_problem_download returns."""
+    owned_ids = np.asarray(owned_ids, np.int64)
+    off = np.asarray(cand_offsets, np.int64)
+    idx = np.asarray(cand_indices, np.uint32)
+    n = len(np.asarray(mass))
+    named = np.zeros(n, bool)
+    named[idx] = True
+    is_owned = np.zeros(n, bool)
+    is_owned[owned_ids] = True
+    part = (np.diff(off) > 0) | named[owned_ids]                      # by row
+    foreign = np.nonzero(named & ~is_owned)[0]
+    ids = np.concatenate([owned_ids[part], foreign]).astype(np.uint32)
+    position = np.asarray(position, np.float32).reshape(-1, 2)
+    return {"ids": ids, "n_owned": int(part.sum()), "particle_size_class": np.asarray(size_class)[ids], "mass": np.asarray(mass, np.float32)[ids],
+            "level_estimation": np.asarray(level, np.float32)[ids], "position": position[ids], "h2": np.asarray(h2, np.float32)[ids],
+            "offsets": np.append(off[:-1][part], off[-1]).astype(np.uint32),   # every row between two owned participants is empty
+            "indices": idx.copy()}
+
+
 def validate_partners(kind: str, size_class, merge_partner, merge_counter, offsets, indices) -> int:
     """validate_share_partners (particle_sharing.rs:119-150) / validate_merge_partners (particle_merging.rs:226-268)."""
     n = len(merge_counter)

@@ -20,10 +20,13 @@
 #include <vector>
 
 #include "sph_dist.hpp"
+#include "sph_slab_partner_problem.h"
 #include "sph_target_mass.hpp"
 
 // (a slab context takes the slab form below: slab_adapt)
-static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter);
+struct SlabCompact;
+static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter,
+                           const SlabCompact* cd = nullptr);
 #define ADAPT_CHECK(c, OP, PARTNER, COUNTER)                                                                                    \
     if (!(c) || !p || !ap) return SPH_ERR_INVALID_ARGUMENT;                                                                     \
     if ((c)->poisoned) return (c)->refuse_poisoned();                                                                           \
@@ -694,6 +697,57 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
     c->drop(DROPS_REGATHER);
 }
 
+// The decisions of a COMPACT problem (include/sph_slab_partner_problem.h): k participants by ascending global id, a partner named by its
+// compact id.  k_slab_expand is the slab form of k_prob_expand (sph_partner_problem.hip): one thread per participant scatters its pair
+// into merge_partner / merge_counter of the whole vector (pre-filled with AVAILABLE / 0), the partner mapped through ids.
+struct SlabCompact {
+    uint64_t k;
+    const uint32_t* ids;
+    const uint32_t* partner_c;
+    const uint16_t* counter_c;
+};
+__global__ __launch_bounds__(256) void k_slab_expand(uint32_t K, uint32_t n_global, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ partner_c,
+                                                      const uint16_t* __restrict__ counter_c, uint32_t* __restrict__ partner, uint16_t* __restrict__ counter)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= K) return;
+    const uint32_t i = ids[c];
+    if (i >= n_global) return;   // (the host check refused it)
+    uint32_t pc = partner_c[c];
+    if (pc != SPH_MERGE_PARTNER_AVAILABLE && pc != SPH_MERGE_PARTNER_DELETE) {
+        pc = pc < K ? ids[pc] : SPH_MERGE_PARTNER_AVAILABLE;   // (the host check refused pc >= K)
+        if (pc >= n_global) pc = SPH_MERGE_PARTNER_AVAILABLE;
+    }
+    partner[i] = pc;
+    counter[i] = counter_c[c];
+}
+// merge_partner / merge_counter of the whole vector on a member's device: copied from the host's arrays, or (cd) filled with AVAILABLE / 0
+// and scattered from the k decisions -- 10 B per participant go up instead of 6 B per particle.  Everything behind this point reads the
+// two arrays and does not know which form they came in.  up_*: staging that lives as long as the arrays
+static int slab_decisions_to_device(sph_ctx* c, hipStream_t s, uint32_t n_global, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd,
+                                    uint32_t* d_partner, uint16_t* d_counter, TmpBuf& up_ids, TmpBuf& up_partner, TmpBuf& up_counter)
+{
+    if (!cd) {
+        HIPCHK(c, hipMemcpyAsync(d_partner, partner, (size_t)n_global * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_counter, counter, (size_t)n_global * 2, hipMemcpyHostToDevice, s));
+        return SPH_OK;
+    }
+    ProfScope ps(&c->prof, "slab_problem_expand", s);
+    HIPCHK(c, hipMemsetAsync(d_partner, 0xff, (size_t)n_global * 4, s));   // SPH_MERGE_PARTNER_AVAILABLE
+    HIPCHK(c, hipMemsetAsync(d_counter, 0, (size_t)n_global * 2, s));
+    const size_t k = (size_t)cd->k;
+    if (!k) return SPH_OK;
+    HIPCHK(c, up_ids.ensure(k * 4));
+    HIPCHK(c, up_partner.ensure(k * 4));
+    HIPCHK(c, up_counter.ensure(k * 2));
+    HIPCHK(c, hipMemcpyAsync(up_ids.p, cd->ids, k * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(up_partner.p, cd->partner_c, k * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(up_counter.p, cd->counter_c, k * 2, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_slab_expand, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, s, (uint32_t)k, n_global, (const uint32_t*)up_ids.as<uint32_t>(),
+                       (const uint32_t*)up_partner.as<uint32_t>(), (const uint16_t*)up_counter.as<uint16_t>(), d_partner, d_counter);
+    return SPH_OK;
+}
+
 // op: 0 share, 1 merge, 2 split -- for every member of the group (collective over ALL ranks of the decomposition)
 // A HIP failure INSIDE one of slab_adapt's per-member loops must not return before the collective that follows (agree, an all-reduce): under
 // a per-rank transport the other ranks would wait in it for ever (advisor r4).  It becomes this rank's local_rc and leaves the loop;
@@ -706,7 +760,10 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
             break;                                                                                                   \
         }                                                                                                            \
     }
-static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter)
+// cd: the decisions come as a compact problem (partner / counter unused).  *alike (optional): the refusal is every rank's alike and came
+// between two collectives -- nobody is left waiting, the transport stays usable
+static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd = nullptr,
+                      bool* alike = nullptr)
 {
     const size_t nm = G.m.size();
     int rc = SPH_OK;
@@ -716,7 +773,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             return c->fail(SPH_ERR_INVALID_ARGUMENT, "the adaptivity apply on a slab context follows a step (it reads the donors across a cut from that step's ghost layer)");
         if (op == 2 && c->n_split_patterns + 1u < 2u) return c->fail(SPH_ERR_NO_SPLIT_PATTERN, "no split pattern for a 1-to-2 split (sph_set_split_patterns was not called)");
     }
-    if (op != 2 && (!partner || !counter)) return SPH_ERR_INVALID_ARGUMENT;
+    if (op != 2 && !cd && (!partner || !counter)) return SPH_ERR_INVALID_ARGUMENT;
     // ---- n_global: the vector the indices refer to
     uint32_t n_global = 0;
     {
@@ -724,6 +781,10 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
         for (size_t i = 0; i < nm; i++) rows[i][0] = (uint32_t)G.m[i]->n;
         if ((rc = G.comm->allreduce_sum_u32(G, rows))) return rc;
         n_global = rows[0][0];
+    }
+    if (cd && cd->k && cd->ids[cd->k - 1] >= n_global) {   // (ascending: the last id is the largest.  Every rank holds the same ids and the same sum)
+        if (alike) *alike = true;
+        return G.m[0]->fail(SPH_ERR_INVALID_ARGUMENT, "ids holds %u, the vector has %u particles", cd->ids[cd->k - 1], n_global);
     }
     if (n_global == 0) return SPH_OK;
     // ---- the ghosts' records as their owners hold them now
@@ -742,9 +803,9 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
     const TargetP tp = target_params(p);
     const dim3 blk(256);
     int local_rc = SPH_OK;
-    std::vector<TmpBuf> B(nm * 12);
-    auto buf = [&](size_t i, int k) -> TmpBuf& { return B[i * 12 + (size_t)k]; };
-    enum { B_PARTNER, B_COUNTER, B_SLOT, B_DEL, B_BEFORE, B_SCRATCH, B_HOLES, B_SRC, B_NEWID, B_KEEP, B_POS, B_EXTRA };
+    std::vector<TmpBuf> B(nm * 15);
+    auto buf = [&](size_t i, int k) -> TmpBuf& { return B[i * 15 + (size_t)k]; };
+    enum { B_PARTNER, B_COUNTER, B_SLOT, B_DEL, B_BEFORE, B_SCRATCH, B_HOLES, B_SRC, B_NEWID, B_KEEP, B_POS, B_EXTRA, B_UP_IDS, B_UP_PARTNER, B_UP_COUNTER };
     auto need = [&](sph_ctx* c, TmpBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 4) == hipSuccess ? SPH_OK : c->fail(SPH_ERR_DEVICE, "out of device memory"); };
     if (op != 2) {
         const int merging = op == 1;
@@ -759,8 +820,9 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             if ((local_rc = need(c, buf(i, B_PARTNER), (size_t)n_global * 4)) || (local_rc = need(c, buf(i, B_COUNTER), (size_t)n_global * 2)) ||
                 (local_rc = need(c, buf(i, B_SLOT), (size_t)n_global * 4)))
                 break;
-            HIPLOC(c, hipMemcpyAsync(buf(i, B_PARTNER).p, partner, (size_t)n_global * 4, hipMemcpyHostToDevice, s));
-            HIPLOC(c, hipMemcpyAsync(buf(i, B_COUNTER).p, counter, (size_t)n_global * 2, hipMemcpyHostToDevice, s));
+            if ((local_rc = slab_decisions_to_device(c, s, n_global, partner, counter, cd, buf(i, B_PARTNER).as<uint32_t>(), buf(i, B_COUNTER).as<uint16_t>(), buf(i, B_UP_IDS),
+                                                     buf(i, B_UP_PARTNER), buf(i, B_UP_COUNTER))))
+                break;
             HIPLOC(c, hipMemsetAsync(buf(i, B_SLOT).p, 0xff, (size_t)n_global * 4, s));
             if (!nt) continue;
             const dim3 grid((nt + 255) / 256);
@@ -902,7 +964,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
     return agree(G, local_rc);
 }
 
-static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter)
+static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd)
 {
     HIPCHK(c, hipSetDevice(c->device));
     Group G;
@@ -910,8 +972,9 @@ static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_ad
     int rc = comm_for_rank(c, &G.comm);
     if (rc) return rc;
     if (!G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes sph_group_adapt");
-    rc = slab_adapt(G, op, p, ap, partner, counter);
-    if (rc) comm_abandon(c);
+    bool alike = false;
+    rc = slab_adapt(G, op, p, ap, partner, counter, cd, &alike);
+    if (rc && !alike) comm_abandon(c);
     return rc;
 }
 
@@ -929,6 +992,67 @@ extern "C" int sph_group_adapt(sph_ctx** ctxs, int n, int op, const sph_params* 
     }
     G.comm = comm_loopback();
     return slab_adapt(G, op, p, ap, merge_partner, merge_counter);
+}
+
+// ---- include/sph_slab_partner_problem.h: the same apply from the K decisions of a compact problem ----------------------------
+// on the host, before any collective and before anything on the device is written (the id >= n_global check follows in slab_adapt)
+static int slab_compact_check(sph_ctx* c, const char* what, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids, const uint32_t* partner_c,
+                              const uint16_t* counter_c)
+{
+    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params and ap must be given", what);
+    if (k >= 0xfffffff0ull) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: k=%llu", what, (unsigned long long)k);
+    if (k && (!ids || !partner_c || !counter_c)) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: ids, partner_c and counter_c must be given", what);
+    for (uint64_t i = 0; i < k; i++) {
+        if (i && ids[i] <= ids[i - 1]) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: ids is not strictly ascending (entry %llu: %u after %u)", what, (unsigned long long)i, ids[i], ids[i - 1]);
+        if (partner_c[i] >= k && partner_c[i] != SPH_MERGE_PARTNER_AVAILABLE && partner_c[i] != SPH_MERGE_PARTNER_DELETE)
+            return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: partner_c holds an id outside the problem (compact id %llu: %u)", what, (unsigned long long)i, partner_c[i]);
+    }
+    return SPH_OK;
+}
+
+static int slab_apply_compact_rank(sph_ctx* c, int op, const char* what, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids,
+                                   const uint32_t* partner_c, const uint16_t* counter_c)
+{
+    if (!c) return SPH_ERR_INVALID_ARGUMENT;
+    if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (a plain context takes sph_download_partner_problem and sph_share_particles_compact / sph_merge_particles_compact)", what);
+    if (c->poisoned) return c->refuse_poisoned();
+    if (int rc = slab_compact_check(c, what, p, ap, k, ids, partner_c, counter_c)) return rc;
+    const SlabCompact cd{k, ids, partner_c, counter_c};
+    return slab_adapt_rank(c, op, p, ap, nullptr, nullptr, &cd);
+}
+
+extern "C" int sph_slab_share_particles_compact(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids, const uint32_t* partner_c,
+                                                const uint16_t* counter_c)
+{
+    return slab_apply_compact_rank(c, 0, "sph_slab_share_particles_compact", p, ap, k, ids, partner_c, counter_c);
+}
+
+extern "C" int sph_slab_merge_particles_compact(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids, const uint32_t* partner_c,
+                                                const uint16_t* counter_c)
+{
+    return slab_apply_compact_rank(c, 1, "sph_slab_merge_particles_compact", p, ap, k, ids, partner_c, counter_c);
+}
+
+extern "C" int sph_group_adapt_compact(sph_ctx** ctxs, int n, int op, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids,
+                                       const uint32_t* partner_c, const uint16_t* counter_c)
+{
+    if (!ctxs || n <= 0) return SPH_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++)
+        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
+    if (op != 0 && op != 1) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_adapt_compact: op %d is neither 0 (share) nor 1 (merge)", op);
+    Group G;
+    for (int i = 0; i < n; i++) {
+        if (!ctxs[i]->dist.on) return ctxs[i]->fail(SPH_ERR_UNSUPPORTED, "sph_group_adapt_compact: context %d is not a slab context", i);
+        if (ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
+            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
+        G.m.push_back(ctxs[i]);
+    }
+    for (auto c : G.m)
+        if (c->poisoned) return c->refuse_poisoned();
+    if (int rc = slab_compact_check(ctxs[0], "sph_group_adapt_compact", p, ap, k, ids, partner_c, counter_c)) return rc;
+    G.comm = comm_loopback();
+    const SlabCompact cd{k, ids, partner_c, counter_c};
+    return slab_adapt(G, op, p, ap, nullptr, nullptr, &cd);
 }
 
 // ---- the partner searches as host code (sph_ffi.h: sph_host_find_partners) ------------------------------------------------

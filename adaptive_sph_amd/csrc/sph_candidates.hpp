@@ -56,3 +56,12 @@ int prob_build_on_device(sph_ctx* c, int kind, const sph_adapt_params* ap, const
 void prob_open_problem(sph_ctx* c, int kind, uint32_t K);
 // queues k_prob_expand: K decisions in compact ids -> merge_partner / merge_counter of the whole vector (pre-filled with AVAILABLE / 0)
 void prob_expand_launch(sph_ctx* c, uint32_t K, const uint32_t* d_partner_c, const uint16_t* d_counter_c, uint32_t* d_partner, uint16_t* d_counter);
+
+// sph_slab_candidates.hip, shared with sph_slab_partner_problem.hip.  slab_cand_refuse: a plain context -> SPH_ERR_UNSUPPORTED, a poisoned
+// one -> SPH_ERR_POISONED.  slab_cand_prepare: the collective prepare of sph_slab_candidates.h for the members of G; *together: the status
+// came out of an agree() -- every rank leaves with it, the transport stays usable.  slab_cand_mark_launch: the walk of the rows prepared
+// last once more, setting flag[slot] (owned slots) / flag[n_tot + slot] (ghost slots) of every donor with a candidate and every candidate.
+struct Group;
+int slab_cand_refuse(sph_ctx* c, const char* what);
+int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together);
+void slab_cand_mark_launch(sph_ctx* c, const CandP& q, uint32_t* flag);

@@ -13,7 +13,7 @@ enum : unsigned {
     CARRY_BUILD = 1u << 1,         // ahead_valid: the neighbour build queued on the predicted grid
     CARRY_LISTS = 1u << 2,         // grid_valid: the lists and cell indices of the last step
     CARRY_EXPORT = 1u << 3,        // export_valid: the CSR of those lists; prob_open: the partner problem made from it, and its solution
-    CARRY_SLAB_LISTS = 1u << 4,    // slab_lists_valid, slab_rows_open: the same CSR and the prepared rows of a slab context
+    CARRY_SLAB_LISTS = 1u << 4,    // slab_lists_valid, slab_rows_open, slab_prob_open: the same CSR, the prepared rows and the problem packed from them on a slab context
     CARRY_LEVEL = 1u << 5,         // have_level, have_reduced: level outputs that do not travel with a particle (stash, flags)
     CARRY_LISTS_AFTER = 1u << 6,   // lists_after: the cache holds the extended lists of the advected positions
     CARRY_MOVERS = 1u << 7,        // inc_count_valid: the mapped mover-count word was written by a merge queued SINCE the state was last replaced
@@ -48,6 +48,7 @@ constexpr unsigned DROPS_STEP_FAILED = CARRY_HEADER;   // ... and one that faile
 
 struct Carry {
     bool hdr_ahead = false, ahead_valid = false, grid_valid = false, export_valid = false, prob_open = false, slab_lists_valid = false, slab_rows_open = false;
+    bool slab_prob_open = false;   // (sph_slab_partner_problem.hip: valid exactly as long as the prepared rows are)
     bool have_level = false, have_reduced = false, lists_after = false, inc_count_valid = false, have_flags = false, rnd_have_prev = false;
     volatile uint32_t* movers_host = nullptr;   // the mapped mover-count word (sph_create; null until the mapped block exists)
 
@@ -57,7 +58,7 @@ struct Carry {
         if (what & CARRY_BUILD) ahead_valid = false;
         if (what & CARRY_LISTS) grid_valid = false;
         if (what & CARRY_EXPORT) export_valid = prob_open = false;
-        if (what & CARRY_SLAB_LISTS) slab_lists_valid = slab_rows_open = false;
+        if (what & CARRY_SLAB_LISTS) slab_lists_valid = slab_rows_open = slab_prob_open = false;
         if (what & CARRY_LEVEL) have_level = have_reduced = false;
         if (what & CARRY_LISTS_AFTER) lists_after = false;
         if (what & CARRY_MOVERS) inc_count_valid = false;   // (a build still in flight may write its stale count after the reset below)

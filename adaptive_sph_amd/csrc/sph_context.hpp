@@ -135,7 +135,13 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     uint32_t slab_lists_rows = 0, slab_rows_n = 0;
     uint64_t slab_lists_tot = 0, slab_rows_tot = 0;
     DevBuf slab_row_slot, slab_slot_row, slab_off, slab_idx;   // (slab_slot_row: the row of every slot, 0xffffffff for a ghost)
-    std::array<DevBuf*, 4> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx}; }
+    // sph_slab_partner_problem.hip: the rank's local partner problem packed from those rows (slab_prob_open; slab_prob_k participants, the
+    // first slab_prob_ko of them owned): a flag and a rank word per slot, twice (owned slots, then ghost slots), and the packed arrays.
+    // The entries stay in cand_idx.
+    uint32_t slab_prob_k = 0, slab_prob_ko = 0;
+    DevBuf slab_prob_flag, slab_prob_rank, slab_prob_ids, slab_prob_cls, slab_prob_mass, slab_prob_level, slab_prob_pos, slab_prob_h2, slab_prob_off;
+    std::array<DevBuf*, 13> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob_ids, &slab_prob_cls,
+                                                  &slab_prob_mass, &slab_prob_level, &slab_prob_pos, &slab_prob_h2, &slab_prob_off}; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];

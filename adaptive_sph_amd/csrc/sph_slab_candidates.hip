@@ -44,13 +44,17 @@ __global__ __launch_bounds__(256) void k_slab_cand_classes(uint32_t nt, const ui
     }
 }
 
-// FILL = false: cnt[r] = candidates of row r.  FILL = true: their global ids at out_off[r] (out_off: the scanned counts).
-template <bool FILL>
+// ROWS_COUNT: cnt[r] = candidates of row r.  ROWS_FILL: their global ids at out_off[r] (out_off: the scanned counts).  ROWS_MARK
+// (sph_slab_partner_problem.hip): the same walk over the same rows; flag[] holds a word per owned slot and, behind those nt words, a word
+// per ghost slot -- the donor of a row that is not empty sets its own and every survivor sets its slot's (slot_row: 0xffffffff for a
+// ghost).  Many lanes store the same 1 to the same word: plain stores, nobody reads a flag in that launch (as k_prob_mark).
+enum { ROWS_COUNT = 0, ROWS_FILL = 1, ROWS_MARK = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_t nt, CandP q, const uint8_t* __restrict__ row_cls,
                                                          const uint32_t* __restrict__ row_slot, const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx,
                                                          uint64_t tot, const float4* __restrict__ pm, const uint8_t* __restrict__ cls,
                                                          const uint32_t* __restrict__ orig, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ out_off,
-                                                         uint32_t* __restrict__ out_idx)
+                                                         uint32_t* __restrict__ out_idx, const uint32_t* __restrict__ slot_row, uint32_t* __restrict__ flag)
 {
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     if (r >= n_rows) return;
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_
             const uint32_t b = off[r];
             const uint64_t e = min((uint64_t)off[r + 1], tot);
             uint32_t w = 0, w_end = 0;
-            if (FILL) {
+            if (MODE == ROWS_FILL) {
                 w = out_off[r];
                 w_end = out_off[r + 1];
             }
@@ -70,17 +74,21 @@ __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_
                 const uint32_t j = idx[p];
                 if (j == s || j >= nt) continue;
                 if (!cand_pass(q, Ai, j, pm, cls)) continue;
-                if (FILL) {
+                if (MODE == ROWS_FILL) {
                     if (w < w_end) out_idx[w] = orig[j];
                     w++;
+                } else if (MODE == ROWS_MARK) {
+                    flag[slot_row[j] == 0xffffffffu ? nt + j : j] = 1u;
+                    c++;
                 } else c++;
             }
+            if (MODE == ROWS_MARK && c) flag[s] = 1u;
         }
     }
-    if (!FILL) cnt[r] = c;
+    if (MODE == ROWS_COUNT) cnt[r] = c;
 }
 
-static int slab_cand_refuse(sph_ctx* c, const char* what)
+int slab_cand_refuse(sph_ctx* c, const char* what)
 {
     if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (a plain context takes sph_download_partner_candidates / sph_sum_mass)", what);
     if (c->poisoned) return c->refuse_poisoned();
@@ -100,7 +108,7 @@ static float* sel_cand_lvl(Member& m) { return m.lv_level; }
     }
 
 // *together: the status came out of an agree() -- every rank leaves with a failure, the transport stays usable
-static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together)
+int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together)
 {
     const size_t nm = G.m.size();
     int rc = SPH_OK, local_rc = SPH_OK;
@@ -114,7 +122,7 @@ static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_
     // ---- lists: the CSR of the step's lists, built once per step
     for (size_t i = 0; i < nm && !local_rc; i++) {
         sph_ctx* c = G.m[i];
-        c->slab_rows_open = false;   // (a slab context, not poisoned: both entry points and the loop above have seen to it)
+        c->slab_rows_open = c->slab_prob_open = false;   // (a slab context, not poisoned: both entry points and the loop above have seen to it)
         if (!c->have_flags) {
             local_rc = c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare follows a step (it filters that step's lists and reads the neighbours across a cut from its ghost layer)");
             break;
@@ -169,9 +177,9 @@ static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_
         {
             ProfScope ps(&c->prof, "slab_candidates_count", s);
             if (n)
-                hipLaunchKernelGGL(k_slab_cand_rows<false>, grid_r, blk, 0, s, n, nt, q, row_cls, c->slab_row_slot.as<uint32_t>(), c->slab_off.as<uint32_t>(),
+                hipLaunchKernelGGL(k_slab_cand_rows<ROWS_COUNT>, grid_r, blk, 0, s, n, nt, q, row_cls, c->slab_row_slot.as<uint32_t>(), c->slab_off.as<uint32_t>(),
                                    c->slab_idx.as<uint32_t>(), c->slab_lists_tot, c->pm[c->pcur].as<float4>(), cls, c->orig[k].as<uint32_t>(),
-                                   c->cand_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint32_t*)nullptr);
+                                   c->cand_cnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
             device_exclusive_scan_u32(s, c->cand_cnt.as<uint32_t>(), out_off, n, c->cand_scan.as<uint32_t>(), out_off + n);
         }
         uint32_t tot = 0;
@@ -187,9 +195,9 @@ static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_
         HIPLOC(c, c->cand_idx.ensure((size_t)tot * 4 + 4));
         if (n && tot) {
             ProfScope ps(&c->prof, "slab_candidates_fill", s);
-            hipLaunchKernelGGL(k_slab_cand_rows<true>, grid_r, blk, 0, s, n, nt, q, row_cls, c->slab_row_slot.as<uint32_t>(), c->slab_off.as<uint32_t>(),
+            hipLaunchKernelGGL(k_slab_cand_rows<ROWS_FILL>, grid_r, blk, 0, s, n, nt, q, row_cls, c->slab_row_slot.as<uint32_t>(), c->slab_off.as<uint32_t>(),
                                c->slab_idx.as<uint32_t>(), c->slab_lists_tot, c->pm[c->pcur].as<float4>(), cls, c->orig[k].as<uint32_t>(), (uint32_t*)nullptr,
-                               (const uint32_t*)out_off, c->cand_idx.as<uint32_t>());
+                               (const uint32_t*)out_off, c->cand_idx.as<uint32_t>(), (const uint32_t*)nullptr, (uint32_t*)nullptr);
         }
         c->slab_rows_open = true;
         c->slab_rows_n = n;
@@ -202,6 +210,18 @@ static int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_
     if (rc)
         for (auto c : G.m) c->slab_rows_open = false;
     return rc;
+}
+
+// the walk of the rows prepared last, in ROWS_MARK mode (sph_slab_partner_problem.hip; q: the CandP they were prepared with): queued on the
+// context's stream.  flag[2 nt], zeroed by the caller
+void slab_cand_mark_launch(sph_ctx* c, const CandP& q, uint32_t* flag)
+{
+    const uint32_t nt = c->dist.n_tot, n = c->slab_rows_n;
+    if (!n || !nt) return;
+    const uint8_t* cls = c->cand_cls.as<uint8_t>();
+    hipLaunchKernelGGL(k_slab_cand_rows<ROWS_MARK>, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, nt, q, cls + nt, c->slab_row_slot.as<uint32_t>(),
+                       c->slab_off.as<uint32_t>(), c->slab_idx.as<uint32_t>(), c->slab_lists_tot, c->pm[c->pcur].as<float4>(), cls, c->orig[c->cur].as<uint32_t>(),
+                       (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, c->slab_slot_row.as<uint32_t>(), flag);
 }
 
 extern "C" int sph_slab_candidates_prepare(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices)

@@ -1,0 +1,230 @@
+// include/sph_slab_partner_problem.h: the rank's LOCAL partner problem of a slab context -- sph_partner_problem.hip's renumbering on the
+// rows of sph_slab_candidates.hip.  The prepare of sph_slab_candidates.h runs first, unchanged (lists, ghost refresh, classes, count, scan,
+// fill: cand_cls, cand_off, cand_idx); what is added here, per member and on its stream:
+//
+//   mark    2 n_tot flag words, zeroed: [0, n_tot) the owned slots, [n_tot, 2 n_tot) the ghost slots.  The row walk once more
+//           (k_slab_cand_rows<ROWS_MARK>: the fill writes global ids, the survivors' SLOTS are known only inside the walk): a donor with a
+//           survivor flags itself and every survivor.  Plain stores, nobody reads a flag in that launch
+//   scan    device_exclusive_scan_u32 over the 2 n_tot words: rank[t] is the local id.  Owned participants come first in slot order -- the
+//           rows are the owned slots in slot order (slab_lists_on_device), so that is row order -- and the ghosts behind them in slot
+//           order.  rank[n_tot] = the owned participants, the last word = all of them: the two words that cross the bus
+//   pack    one thread per flag word, a non-participant leaves after one load: global id (orig), class (the per-slot scratch of the
+//           prepare: szc for an owned slot, k_classify on the refreshed record for a ghost), mass / position / h2 from the slot's record
+//           -- the words sph_download reads --, level from lvl.  An owned participant also writes offsets[c] = cand_off[row]: every row
+//           between two owned participants is empty, so the prepared offsets restricted to them are the local CSR's (as k_prob_pack)
+//
+// The entries stay in cand_idx (global ids).  A few words per slot, coalesced except for the scatter through rank: thread per element,
+// 256-thread blocks, like sph_partner_problem.hip.  Collective pattern: that of slab_cand_prepare (local_rc -> agree).
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "sph_slab_partner_problem.h"
+#include "sph_candidates.hpp"
+#include "sph_dist.hpp"
+
+struct SlabProbOut {
+    uint32_t* ids;
+    uint8_t* cls;
+    float* mass;
+    float* level;
+    float2* pos;
+    float* h2;
+    uint32_t* off;
+};
+
+__global__ __launch_bounds__(256) void k_slab_prob_pack(uint32_t nt, uint32_t K, uint32_t Ko, uint32_t n_rows, uint32_t tot, const uint32_t* __restrict__ flag,
+                                                         const uint32_t* __restrict__ rank, const uint32_t* __restrict__ orig, const uint8_t* __restrict__ cls,
+                                                         const float4* __restrict__ pm, const float* __restrict__ lvl, const uint32_t* __restrict__ slot_row,
+                                                         const uint32_t* __restrict__ cand_off, SlabProbOut o)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2u * nt) return;
+    if (t == 0) o.off[Ko] = tot;
+    if (!flag[t]) return;
+    const uint32_t c = rank[t];
+    if (c >= K) return;
+    const bool own = t < nt;
+    const uint32_t s = own ? t : t - nt;
+    const float4 A = pm[s];
+    o.ids[c] = orig[s];
+    o.cls[c] = cls[s];
+    o.mass[c] = A.z;
+    o.level[c] = lvl[s];
+    o.pos[c] = make_float2(A.x, A.y);
+    o.h2[c] = A.w;
+    if (own && c < Ko) {
+        const uint32_t r = slot_row[s];
+        o.off[c] = r < n_rows ? cand_off[r] : tot;
+    }
+}
+
+#define HIPLOC(ctx, call)                                                                                            \
+    {                                                                                                                \
+        hipError_t e_ = (call);                                                                                      \
+        if (e_ != hipSuccess) {                                                                                      \
+            local_rc = (ctx)->fail(SPH_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));                   \
+            break;                                                                                                   \
+        }                                                                                                            \
+    }
+
+static int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_part, uint64_t* n_owned, uint64_t* n_indices, bool* together)
+{
+    const size_t nm = G.m.size();
+    std::vector<uint64_t> rows(nm, 0), tots(nm, 0);
+    int rc = slab_cand_prepare(G, kind, p, ap, rows.data(), tots.data(), together);   // (it closes the members' problems first)
+    if (rc) return rc;
+    *together = false;
+    int local_rc = SPH_OK;
+    const CandP q = cand_params(kind, ap);
+    for (size_t i = 0; i < nm && !local_rc; i++) {
+        sph_ctx* c = G.m[i];
+        HIPLOC(c, hipSetDevice(c->device));
+        hipStream_t s = c->stream;
+        const uint32_t nt = c->dist.n_tot, n = c->slab_rows_n, tot = (uint32_t)c->slab_rows_tot;
+        uint32_t K = 0, Ko = 0;
+        if (n && nt && tot) {
+            const size_t words = 2 * (size_t)nt;
+            HIPLOC(c, c->slab_prob_flag.ensure(words * 4));
+            HIPLOC(c, c->slab_prob_rank.ensure((words + 1) * 4));
+            HIPLOC(c, c->cand_scan.ensure((words / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+            uint32_t* rank = c->slab_prob_rank.as<uint32_t>();
+            {
+                ProfScope ps(&c->prof, "slab_problem_mark", s);
+                HIPLOC(c, hipMemsetAsync(c->slab_prob_flag.p, 0, words * 4, s));
+                slab_cand_mark_launch(c, q, c->slab_prob_flag.as<uint32_t>());
+                device_exclusive_scan_u32(s, c->slab_prob_flag.as<uint32_t>(), rank, (uint32_t)words, c->cand_scan.as<uint32_t>(), rank + words);
+            }
+            HIPLOC(c, hipMemcpyAsync(&Ko, rank + nt, 4, hipMemcpyDeviceToHost, s));
+            HIPLOC(c, hipMemcpyAsync(&K, rank + words, 4, hipMemcpyDeviceToHost, s));
+            HIPLOC(c, hipStreamSynchronize(s));
+            if (K == 0 || Ko == 0 || Ko > K || Ko > n || K > words) {
+                local_rc = c->fail(SPH_ERR_DEVICE, "sph_slab_partner_problem_prepare: %u candidates but %u participants (%u owned) of %u slots", tot, K, Ko, nt);
+                break;
+            }
+            const size_t k = K;
+            HIPLOC(c, c->slab_prob_ids.ensure(k * 4));
+            HIPLOC(c, c->slab_prob_cls.ensure(k));
+            HIPLOC(c, c->slab_prob_mass.ensure(k * 4));
+            HIPLOC(c, c->slab_prob_level.ensure(k * 4));
+            HIPLOC(c, c->slab_prob_pos.ensure(k * 8));
+            HIPLOC(c, c->slab_prob_h2.ensure(k * 4));
+            HIPLOC(c, c->slab_prob_off.ensure(((size_t)Ko + 1) * 4));
+            ProfScope ps(&c->prof, "slab_problem_pack", s);
+            hipLaunchKernelGGL(k_slab_prob_pack, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, s, nt, K, Ko, n, tot, (const uint32_t*)c->slab_prob_flag.as<uint32_t>(),
+                               (const uint32_t*)rank, (const uint32_t*)c->orig[c->cur].as<uint32_t>(), (const uint8_t*)c->cand_cls.as<uint8_t>(),
+                               (const float4*)c->pm[c->pcur].as<float4>(), (const float*)c->lvl[c->cur].as<float>(), (const uint32_t*)c->slab_slot_row.as<uint32_t>(),
+                               (const uint32_t*)c->cand_off.as<uint32_t>(),
+                               SlabProbOut{c->slab_prob_ids.as<uint32_t>(), c->slab_prob_cls.as<uint8_t>(), c->slab_prob_mass.as<float>(), c->slab_prob_level.as<float>(),
+                                           c->slab_prob_pos.as<float2>(), c->slab_prob_h2.as<float>(), c->slab_prob_off.as<uint32_t>()});
+            HIPLOC(c, hipStreamSynchronize(s));   // (the snapshot is complete before anybody changes the records it was packed from)
+        }
+        c->slab_prob_open = true;
+        c->slab_prob_k = K;
+        c->slab_prob_ko = Ko;
+        n_part[i] = K;
+        n_owned[i] = Ko;
+        n_indices[i] = tot;
+    }
+    *together = true;
+    rc = agree(G, local_rc);
+    if (rc)
+        for (auto c : G.m) c->slab_prob_open = false;   // (the rows of sph_slab_candidates_prepare stay: they are complete)
+    return rc;
+}
+
+extern "C" int sph_slab_partner_problem_prepare(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_participants,
+                                                uint64_t* n_owned_participants, uint64_t* n_indices)
+{
+    if (!c) return SPH_ERR_INVALID_ARGUMENT;
+    uint64_t K = 0, Ko = 0, tot = 0;
+    if (n_participants) *n_participants = 0;
+    if (n_owned_participants) *n_owned_participants = 0;
+    if (n_indices) *n_indices = 0;
+    // (argument refusals are every rank's alike -- the ranks make the same call -- and come before any collective)
+    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_partner_problem_prepare: params and ap must be given");
+    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_partner_problem_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    if (int rc = slab_cand_refuse(c, "sph_slab_partner_problem_prepare")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    Group G;
+    G.m.push_back(c);
+    int rc = comm_for_rank(c, &G.comm);
+    if (rc) return rc;
+    if (!G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes sph_group_slab_partner_problem_prepare");
+    bool together = false;
+    rc = slab_prob_prepare(G, kind, p, ap, &K, &Ko, &tot, &together);
+    if (rc && !together) comm_abandon(c);   // (as sph_slab_candidates_prepare)
+    if (rc) return rc;
+    if (n_participants) *n_participants = K;
+    if (n_owned_participants) *n_owned_participants = Ko;
+    if (n_indices) *n_indices = tot;
+    return SPH_OK;
+}
+
+extern "C" int sph_group_slab_partner_problem_prepare(sph_ctx** ctxs, int n, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_participants,
+                                                      uint64_t* n_owned_participants, uint64_t* n_indices)
+{
+    if (!ctxs || n <= 0) return SPH_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++)
+        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++) {
+        if (n_participants) n_participants[i] = 0;
+        if (n_owned_participants) n_owned_participants[i] = 0;
+        if (n_indices) n_indices[i] = 0;
+    }
+    if (!p || !ap) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_partner_problem_prepare: params and ap must be given");
+    if (kind != 0 && kind != 1) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_partner_problem_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    Group G;
+    for (int i = 0; i < n; i++) {
+        if (!ctxs[i]->dist.on) return slab_cand_refuse(ctxs[i], "sph_group_slab_partner_problem_prepare");
+        if (ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
+            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
+        G.m.push_back(ctxs[i]);
+    }
+    G.comm = comm_loopback();
+    std::vector<uint64_t> K((size_t)n, 0), Ko((size_t)n, 0), tot((size_t)n, 0);
+    bool together = false;
+    const int rc = slab_prob_prepare(G, kind, p, ap, K.data(), Ko.data(), tot.data(), &together);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        if (n_participants) n_participants[i] = K[(size_t)i];
+        if (n_owned_participants) n_owned_participants[i] = Ko[(size_t)i];
+        if (n_indices) n_indices[i] = tot[(size_t)i];
+    }
+    return SPH_OK;
+}
+
+extern "C" int sph_slab_partner_problem_download(sph_ctx* c, uint32_t* ids, uint8_t* size_class, float* mass, float* level, float* position, float* h2,
+                                                 uint32_t* offsets, uint64_t pcap, uint32_t* indices, uint64_t icap, uint64_t* n_participants,
+                                                 uint64_t* n_owned_participants, uint64_t* n_indices)
+{
+    if (!c) return SPH_ERR_INVALID_ARGUMENT;
+    if (n_participants) *n_participants = 0;
+    if (n_owned_participants) *n_owned_participants = 0;
+    if (n_indices) *n_indices = 0;
+    if (int rc = slab_cand_refuse(c, "sph_slab_partner_problem_download")) return rc;
+    if (!c->slab_prob_open || !c->slab_rows_open || !c->slab_lists_valid || c->slab_rows_n != (uint32_t)c->n)
+        return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_partner_problem_download: no prepared problem (sph_slab_partner_problem_prepare comes first; a step, an upload, an edit, a merge, a split or sph_slab_candidates_prepare drops it)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = c->slab_prob_k, Ko = c->slab_prob_ko;
+    const uint64_t tot = c->slab_rows_tot;
+    if (n_participants) *n_participants = K;
+    if (n_owned_participants) *n_owned_participants = Ko;
+    if (n_indices) *n_indices = tot;
+    if ((ids || size_class || mass || level || position || h2 || offsets) && pcap < K)
+        return c->fail(SPH_ERR_INVALID_ARGUMENT, "participant buffers too small (%llu participants prepared)", (unsigned long long)K);
+    if (indices && icap < tot) return c->fail(SPH_ERR_INVALID_ARGUMENT, "indices buffer too small (%llu entries prepared)", (unsigned long long)tot);
+    hipStream_t s = c->stream;
+    if (K) {
+        if (ids) HIPCHK(c, hipMemcpyAsync(ids, c->slab_prob_ids.p, K * 4, hipMemcpyDeviceToHost, s));
+        if (size_class) HIPCHK(c, hipMemcpyAsync(size_class, c->slab_prob_cls.p, K, hipMemcpyDeviceToHost, s));
+        if (mass) HIPCHK(c, hipMemcpyAsync(mass, c->slab_prob_mass.p, K * 4, hipMemcpyDeviceToHost, s));
+        if (level) HIPCHK(c, hipMemcpyAsync(level, c->slab_prob_level.p, K * 4, hipMemcpyDeviceToHost, s));
+        if (position) HIPCHK(c, hipMemcpyAsync(position, c->slab_prob_pos.p, K * 8, hipMemcpyDeviceToHost, s));
+        if (h2) HIPCHK(c, hipMemcpyAsync(h2, c->slab_prob_h2.p, K * 4, hipMemcpyDeviceToHost, s));
+        if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, c->slab_prob_off.p, (Ko + 1) * 4, hipMemcpyDeviceToHost, s));
+        if (indices && tot) HIPCHK(c, hipMemcpyAsync(indices, c->cand_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    } else if (offsets) offsets[0] = 0;
+    return SPH_OK;
+}

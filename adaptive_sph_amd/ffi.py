@@ -180,6 +180,10 @@ class SphPartnerSearchInfo(C.Structure):
 # include/sph_slab_candidates.h: the candidate rows of a slab context, in global ids, + the owned particles' mass sum (product only)
 SLAB_CANDIDATE_SYMBOLS = ["slab_candidates_prepare", "group_slab_candidates_prepare", "slab_candidates_download", "slab_sum_mass"]
 
+# include/sph_slab_partner_problem.h: the compact partner problem of a slab context -- the rank's local problem, the apply from K decisions
+SLAB_PROBLEM_SYMBOLS = ["slab_partner_problem_prepare", "group_slab_partner_problem_prepare", "slab_partner_problem_download",
+                        "slab_share_particles_compact", "slab_merge_particles_compact", "group_adapt_compact"]
+
 
 # include/sph_slab_render.h: frames drawn from slab contexts -- rank layers composed on the device (product only)
 SLAB_RENDER_SYMBOLS = ["slab_render_pressure_max", "slab_render_layer", "slab_render_layer_download", "render_compose", "group_render"]
@@ -358,6 +362,14 @@ class SphLibrary:
                                                                                        C.POINTER(u64)], required=False)
         self.slab_candidates_download = sig("slab_candidates_download", i32, [vp, vp, vp, u64], required=False)
         self.slab_sum_mass = sig("slab_sum_mass", i32, [vp, C.POINTER(C.c_double)], required=False)
+        pu64 = C.POINTER(u64)
+        self.slab_partner_problem_prepare = sig("slab_partner_problem_prepare", i32, [vp, i32, C.POINTER(SphParams), ap, pu64, pu64, pu64], required=False)
+        self.group_slab_partner_problem_prepare = sig("group_slab_partner_problem_prepare", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, pu64, pu64, pu64],
+                                                      required=False)
+        self.slab_partner_problem_download = sig("slab_partner_problem_download", i32, [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, pu64, pu64, pu64], required=False)
+        self.slab_share_particles_compact = sig("slab_share_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
+        self.slab_merge_particles_compact = sig("slab_merge_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
+        self.group_adapt_compact = sig("group_adapt_compact", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
         bp = C.POINTER(SphRenderBand)
         self.slab_render_pressure_max = sig("slab_render_pressure_max", i32, [vp, C.POINTER(C.c_float)], required=False)
         self.slab_render_layer = sig("slab_render_layer", i32, [vp, C.POINTER(SphParams), rpp, C.c_float, bp], required=False)
@@ -733,6 +745,55 @@ class Context:
         self._check(self._slab_candidate_lib().slab_sum_mass(self.handle, C.byref(v)))
         return float(v.value)
 
+    # ---- compact partner problem of a slab context (include/sph_slab_partner_problem.h) ----
+    def _slab_problem_lib(self):
+        return _slab_problem_lib(self.lib)
+
+    def slab_partner_problem_prepare(self, kind, params: SphParams, ap: "SphAdaptParams"):
+        """sph_slab_partner_problem_prepare: COLLECTIVE through the context's own transport, like slab_candidates_prepare (which it runs
+        first): pack this rank's local problem of the `kind` ("share" / 0, "merge" / 1) search on the device.
+        -> (n_participants, n_owned_participants, n_indices)."""
+        lib = self._slab_problem_lib()
+        kind = {"share": 0, "merge": 1}.get(kind, kind)
+        k, ko, tot = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(lib.slab_partner_problem_prepare(self.handle, int(kind), C.byref(params) if params is not None else None,
+                                                     C.byref(ap) if ap is not None else None, C.byref(k), C.byref(ko), C.byref(tot)))
+        return int(k.value), int(ko.value), int(tot.value)
+
+    def slab_partner_problem_download(self) -> dict:
+        """sph_slab_partner_problem_download (local): the problem packed by the last prepare, as the dict
+        distributed.merge_slab_partner_problems takes and adaptivity.slab_partner_problem_reference returns: "ids" (global ids; the
+        "n_owned" owned participants first, in the order of download("particle_id"), the foreign ones behind them), the five decision
+        fields at ids, "offsets"[n_owned + 1] / "indices": the owned participants' candidate rows, entries in global ids.  A sizing call,
+        then the filling one."""
+        lib = self._slab_problem_lib()
+        k, ko, tot = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(lib.slab_partner_problem_download(self.handle, None, None, None, None, None, None, None, 0, None, 0, C.byref(k), C.byref(ko), C.byref(tot)))
+        K, Ko, T = int(k.value), int(ko.value), int(tot.value)
+        v = {"ids": np.empty(K, np.uint32), "offsets": np.empty(Ko + 1, np.uint32), "indices": np.empty(T, np.uint32)}
+        for name in PROBLEM_FIELDS:
+            fid, dt, w = FIELDS[name]
+            v[name] = np.empty(K * w, dt)
+        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+        self._check(lib.slab_partner_problem_download(self.handle, ptr(v["ids"]), *[ptr(v[f]) for f in PROBLEM_FIELDS], v["offsets"].ctypes.data, K, ptr(v["indices"]), T,
+                                                      None, None, None))
+        v["position"] = v["position"].reshape(K, 2)
+        v["n_owned"] = Ko
+        return v
+
+    def slab_share_particles_compact(self, params: SphParams, ap: "SphAdaptParams", ids, partner_c, counter_c) -> None:
+        """sph_slab_share_particles_compact: COLLECTIVE like share_particles on a slab context; the K decisions of the merged problem,
+        `ids` its global ids (strictly ascending), the same arrays on every rank."""
+        ids, mp, mc = _slab_compact_arrays(ids, partner_c, counter_c)
+        self._check(self._slab_problem_lib().slab_share_particles_compact(self.handle, C.byref(params) if params is not None else None, C.byref(ap) if ap is not None else None,
+                                                                          len(ids), ids.ctypes.data, mp.ctypes.data, mc.ctypes.data))
+
+    def slab_merge_particles_compact(self, params: SphParams, ap: "SphAdaptParams", ids, partner_c, counter_c) -> None:
+        """sph_slab_merge_particles_compact: the same for merge_particles."""
+        ids, mp, mc = _slab_compact_arrays(ids, partner_c, counter_c)
+        self._check(self._slab_problem_lib().slab_merge_particles_compact(self.handle, C.byref(params) if params is not None else None, C.byref(ap) if ap is not None else None,
+                                                                          len(ids), ids.ctypes.data, mp.ctypes.data, mc.ctypes.data))
+
     # ---- frames (include/sph_render.h; adaptive_sph_amd/render.py builds the parameters) ----
     def _render_lib(self):
         if self.lib.render is None:
@@ -951,6 +1012,51 @@ def group_slab_candidates_prepare(contexts, kind, params: SphParams, ap):
     for c, v in zip(contexts, out):
         c._slab_rows = v
     return out
+
+
+def _slab_problem_lib(lib):
+    if any(getattr(lib, s, None) is None for s in SLAB_PROBLEM_SYMBOLS):
+        raise SphError(30, f"{lib.path.name} has no compact partner problem for slab contexts (sph_slab_partner_problem.h)")
+    return lib
+
+
+def _slab_compact_arrays(ids, partner_c, counter_c):
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    mp = np.ascontiguousarray(partner_c, dtype=np.uint32)
+    mc = np.ascontiguousarray(counter_c, dtype=np.uint16)
+    if not (ids.shape == mp.shape == mc.shape) or ids.ndim != 1:
+        raise ValueError("ids / partner_c / counter_c must have one entry per participant")
+    return ids, mp, mc
+
+
+def group_slab_partner_problem_prepare(contexts, kind, params: SphParams, ap):
+    """sph_group_slab_partner_problem_prepare: Context.slab_partner_problem_prepare for the k slab contexts of this process (loopback
+    transport); returns the ranks' (n_participants, n_owned_participants, n_indices)."""
+    lib = _slab_problem_lib(contexts[0].lib)
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    K, Ko, tot = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint64 * k)()
+    rc = lib.group_slab_partner_problem_prepare(handles, k, int({"share": 0, "merge": 1}.get(kind, kind)), C.byref(params) if params is not None else None,
+                                                C.byref(ap) if ap is not None else None, K, Ko, tot)
+    if rc != 0:
+        msgs = [c.lib.last_error(c.handle) for c in contexts]
+        raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+    return [(int(K[i]), int(Ko[i]), int(tot[i])) for i in range(k)]
+
+
+def group_adapt_compact(contexts, op: str, params: SphParams, ap, ids, partner_c, counter_c):
+    """sph_group_adapt_compact: share / merge on the k slab contexts of this process from the K decisions of the merged compact problem
+    (`ids`: its global ids, strictly ascending; `partner_c`: sentinels or compact ids)."""
+    lib = _slab_problem_lib(contexts[0].lib)
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    code = {"share": 0, "merge": 1}.get(op, op)
+    ids, mp, mc = _slab_compact_arrays(ids, partner_c, counter_c)
+    rc = lib.group_adapt_compact(handles, k, int(code), C.byref(params) if params is not None else None, C.byref(ap) if ap is not None else None, len(ids), ids.ctypes.data,
+                                 mp.ctypes.data, mc.ctypes.data)
+    if rc != 0:
+        msgs = [c.lib.last_error(c.handle) for c in contexts]
+        raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
 
 
 def group_render(contexts, params: SphParams, rp: "SphRenderParams") -> np.ndarray:
