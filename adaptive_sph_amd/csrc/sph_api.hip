@@ -249,62 +249,8 @@ __global__ __launch_bounds__(256) void k_header_final(const HeaderOut* __restric
 // sweep and, like it, only once the stop decision has been taken
 // `h_ctrl` != nullptr: the launch is the last one before a host wait and does k_publish's job as well (control block + guard
 // word to mapped host memory, the sequence number last) -- one launch less on the step's critical path
-// (1024 threads, four partials per thread requested together: the launch sits on the step's critical path -- the host waits for its
-//  last store -- and 16 dependent load round trips per thread were most of its 8 us)
-__global__ __launch_bounds__(1024) void k_header_ahead(const HeaderOut* __restrict__ partials, uint32_t nparts, const SolverCtrl* __restrict__ ctrl,
-                                                       HeaderOut* __restrict__ out, const DeviceStatus* __restrict__ status, SolverCtrl* __restrict__ h_ctrl,
-                                                       DeviceStatus* __restrict__ h_status, uint32_t seq)
-{
-    if (ctrl->done == 0u) {
-        if (h_ctrl && threadIdx.x == 0) {
-            SolverCtrl v = *ctrl;
-            v.seq = seq - 1u;
-            *h_ctrl = v;
-            *h_status = *status;
-            __threadfence_system();
-            ((volatile SolverCtrl*)h_ctrl)->seq = seq;
-        }
-        return;
-    }
-    const float INF = __uint_as_float(0x7f800000u);
-    HeaderOut o{INF, INF, -INF, -INF, 0.f, INF, INF, 0};
-    for (uint32_t k0 = threadIdx.x; k0 < nparts; k0 += 4096u) {
-        HeaderOut q[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4u; u++) q[u] = partials[min(k0 + 1024u * u, nparts - 1u)];   // (a repeated partial changes no min / max)
-#pragma unroll
-        for (uint32_t u = 0; u < 4u; u++) {
-            o.min_x = fminf(o.min_x, q[u].min_x); o.min_y = fminf(o.min_y, q[u].min_y);
-            o.max_x = fmaxf(o.max_x, q[u].max_x); o.max_y = fmaxf(o.max_y, q[u].max_y);
-            o.h_max = fmaxf(o.h_max, q[u].h_max); o.h_min = fminf(o.h_min, q[u].h_min);
-            o.min_cfl = fminf(o.min_cfl, q[u].min_cfl);
-        }
-    }
-    o.min_x = wave_min(o.min_x); o.min_y = wave_min(o.min_y); o.max_x = wave_max(o.max_x); o.max_y = wave_max(o.max_y);
-    o.h_max = wave_max(o.h_max); o.h_min = wave_min(o.h_min); o.min_cfl = wave_min(o.min_cfl);
-    __shared__ HeaderOut s[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s[w] = o;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        HeaderOut r = s[0];
-        for (int k = 1; k < 16; k++) {
-            r.min_x = fminf(r.min_x, s[k].min_x); r.min_y = fminf(r.min_y, s[k].min_y);
-            r.max_x = fmaxf(r.max_x, s[k].max_x); r.max_y = fmaxf(r.max_y, s[k].max_y);
-            r.h_max = fmaxf(r.h_max, s[k].h_max); r.h_min = fminf(r.h_min, s[k].h_min);
-            r.min_cfl = fminf(r.min_cfl, s[k].min_cfl);
-        }
-        *out = r;
-        if (h_ctrl) {
-            SolverCtrl v = *ctrl;
-            v.seq = seq - 1u;
-            *h_ctrl = v;
-            *h_status = *status;
-            __threadfence_system();
-            ((volatile SolverCtrl*)h_ctrl)->seq = seq;
-        }
-    }
-}
+// (the reduction itself: header_ahead_block, sph_internal.hpp -- shared with the header workgroup of the fused k_inc_count, sph_sort.hip)
+__global__ __launch_bounds__(HDR_AHEAD_THREADS) void k_header_ahead(HeaderAheadP a) { header_ahead_block(a); }
 
 __global__ __launch_bounds__(256) void k_pack_upload(uint32_t n, const float* __restrict__ mass, const float2* __restrict__ pos,
                                                       const float2* __restrict__ velin, float4* __restrict__ pm, float2* __restrict__ vel,
@@ -551,6 +497,7 @@ Options options_from_env()
     o.tile = num("SPH_TILE", 0);
     o.ahead_build = num("SPH_AHEAD_BUILD", 1) != 0 ? 1 : 0;
     o.inc_sort = num("SPH_INC_SORT", 1);
+    o.boundary_fused = num("SPH_BOUNDARY_FUSED", 1) != 0 ? 1 : 0;
     o.slab_paced = num("SPH_SLAB_PACED", 1) != 0 ? 1 : 0;
     o.slab_records = num("SPH_SLAB_RECORDS", 1) != 0 ? 1 : 0;
     o.side_cus = num("SPH_SIDE_CUS", 0);
@@ -563,7 +510,7 @@ Options options_from_env()
     // libsph_hip.so would otherwise run the defaults in every row and report nothing)
     static const char* const lab_only[] = {"SPH_PACED", "SPH_PACE_LEAD", "SPH_PACE_PRED", "SPH_CHAIN", "SPH_ACCEL_GENERIC", "SPH_JACOBI_GENERIC", "SPH_SOURCE_GENERIC",
                                            "SPH_SLAB_GENERAL", "SPH_SLAB_LEVEL_PLAIN", "SPH_LEVEL_SERIAL", "SPH_LEVEL_BATCH8", "SPH_LEVEL_QUEUE", "SPH_OFFSET_LISTS",
-                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
+                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_BOUNDARY_FUSED", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
                                            "SPH_SIDE_CUS", "SPH_MAIN_EXCLUDE", "SPH_IPC_FUSE_MAX_BYTES", "SPH_IPC_COPY_MIN_BYTES"};
     static bool warned = false;
     if (!warned)
@@ -697,7 +644,7 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
-                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage};
+                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->inc_local, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage};
     for (auto b : all) b->release();
     for (DevBuf* b : c->export_bufs()) b->release();
     for (DevBuf* b : c->prob_bufs()) b->release();
@@ -1659,9 +1606,10 @@ void launch_header(sph_ctx* c, uint32_t n, float rest_density, int from_mass /* 
     }
 }
 
-void launch_header_ahead(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool publish)
+// the arguments of the header reduction behind an integrating tail, for the launch that carries it: k_header_ahead, or the fused
+// k_inc_count of the build queued ahead (sph_sort.hip)
+HeaderAheadP header_ahead_args(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool publish)
 {
-    ProfScope ps(&c->prof, "header_ahead", c->stream);
     uint32_t seq = 0;
     if (publish) {   // the launch_publish that follows has nothing left to do
         c->publish_seq++;
@@ -1669,10 +1617,15 @@ void launch_header_ahead(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool 
         seq = c->publish_seq;
         c->publish_folded = true;
     }
-    hipLaunchKernelGGL(k_header_ahead, dim3(1), dim3(1024), 0, c->stream, c->hdr_ahead_partials.as<HeaderOut>(), nblocks, c->ctrl.as<SolverCtrl>(), out_dev,
-                       c->status.as<DeviceStatus>(), publish ? c->ctrl_host_dev : (SolverCtrl*)nullptr, publish ? c->status_host_dev : (DeviceStatus*)nullptr, seq);
+    return HeaderAheadP{c->hdr_ahead_partials.as<HeaderOut>(), nblocks, c->ctrl.as<SolverCtrl>(), out_dev, c->status.as<DeviceStatus>(),
+                        publish ? c->ctrl_host_dev : (SolverCtrl*)nullptr, publish ? c->status_host_dev : (DeviceStatus*)nullptr, seq};
 }
 
+void launch_header_ahead(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool publish)
+{
+    ProfScope ps(&c->prof, "header_ahead", c->stream);
+    hipLaunchKernelGGL(k_header_ahead, dim3(1), dim3(HDR_AHEAD_THREADS), 0, c->stream, header_ahead_args(c, nblocks, out_dev, publish));
+}
 void launch_publish(sph_ctx* c)
 {
     if (c->publish_folded) {   // k_header_ahead, queued just before, publishes

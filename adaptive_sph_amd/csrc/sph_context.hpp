@@ -75,6 +75,7 @@ struct Options {
     int tile = 0;               // SPH_TILE=<bits>          LDS-staged sweeps (sph_set_sweep_variant overrides, process-wide)
     int ahead_build = 1;        // SPH_AHEAD_BUILD=0        one context: never queue the next step's cell sort behind the integrating tail
     int inc_sort = 1;           // SPH_INC_SORT=0 | k       the cell sort queued ahead is always the radix sort (never the incremental merge); k > 1: the merge up to n / k movers (default n / 3: at 4M the merge still beats the radix sort with a third of the particles changing cell)
+    int boundary_fused = 1;     // SPH_BOUNDARY_FUSED=0     the merge queued ahead in five launches (tail, k_header_ahead, count, k_inc_scan, place) instead of three (tail, count with the header reduction, place with the block sums' prefix)
     int slab_paced = 1;         // SPH_SLAB_PACED=0         slabs: predicted queue instead of pacing
     int slab_records = 1;       // SPH_SLAB_RECORDS=0       slabs: sweep A through the generic form (p / rho^2 as a field of its own)
     int debug_sync = 0;         // SPH_DEBUG_SYNC=<mask>    synchronise and name the phases (fault hunting)
@@ -239,6 +240,7 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // the build queued ahead as a merge of the particles that stay in their cells with the few that do not (sph_sort.hip:
     // incremental_cell_sort): per-cell list heads (epoch-tagged, never cleared), list links, block sums, the mover counter
     DevBuf inc_head, inc_next, inc_bsum, inc_movers;
+    DevBuf inc_local;   // the fused build (IncFusedP): the cell-range table in its two-level form
     uint32_t inc_epoch = 0;     // tag of the current call's list heads
     int inc_radix_streak = 0;   // ahead builds in a row that took the radix sort because the last known mover count was large
     struct Ahead {   // the build queued while ahead_valid

@@ -77,11 +77,7 @@ struct ProfScope {
     }
 };
 
-// ---- step header: per-step scalars reduced on the device, read once by the host ---------------
-struct HeaderOut {
-    float min_x, min_y, max_x, max_y, h_max, h_min, min_cfl;
-    uint32_t pad;
-};
+#include "sph_boundary_fused.hpp"   // HeaderOut (the step header), the header reduction's visiting order, the two-level cell-range table
 
 // ---- Jacobi control block (device resident; copied to the host at sync points) ----------------
 struct SolverCtrl {
@@ -100,6 +96,65 @@ struct DeviceStatus {
     uint32_t error;  // SPH_ERR_* or 0
     uint32_t info;   // particle index (host order) or auxiliary value
 };
+
+// what the reduction behind an integrating tail works on (sph_api.hip: k_header_ahead; sph_sort.hip: the header workgroup of the fused
+// k_inc_count): the tail's partials, the solve's control block (nothing is reduced before the stop decision), the header's place in
+// mapped host memory and -- h_ctrl != nullptr -- k_publish's job: control block and guard word to the host, `seq` last
+struct HeaderAheadP {
+    const HeaderOut* partials;
+    uint32_t nparts;
+    const SolverCtrl* ctrl;
+    HeaderOut* out;
+    const DeviceStatus* status;
+    SolverCtrl* h_ctrl;
+    DeviceStatus* h_status;
+    uint32_t seq;
+};
+// ... by ONE workgroup of HDR_AHEAD_THREADS lanes in a fixed order (sph_boundary_fused.hpp: header_ahead_slot; lanes, then waves in
+// index order).  Four partials per lane requested together: the launch sits on the step's critical path -- the host waits for its last
+// store -- and 16 dependent load round trips per lane were most of its 8 us.  Every lane of the workgroup calls it; a __syncthreads()
+// sits inside.
+__device__ __forceinline__ void header_ahead_block(const HeaderAheadP& a)
+{
+    if (a.ctrl->done == 0u) {
+        if (a.h_ctrl && threadIdx.x == 0) {
+            SolverCtrl v = *a.ctrl;
+            v.seq = a.seq - 1u;
+            *a.h_ctrl = v;
+            *a.h_status = *a.status;
+            __threadfence_system();
+            ((volatile SolverCtrl*)a.h_ctrl)->seq = a.seq;
+        }
+        return;
+    }
+    HeaderOut o = header_neutral();
+    for (uint32_t k0 = threadIdx.x; k0 < a.nparts; k0 += 4u * HDR_AHEAD_THREADS) {
+        HeaderOut q[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) q[u] = a.partials[header_ahead_slot(k0, u, a.nparts)];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) header_merge(o, q[u]);
+    }
+    o.min_x = wave_min(o.min_x); o.min_y = wave_min(o.min_y); o.max_x = wave_max(o.max_x); o.max_y = wave_max(o.max_y);
+    o.h_max = wave_max(o.h_max); o.h_min = wave_min(o.h_min); o.min_cfl = wave_min(o.min_cfl);
+    __shared__ HeaderOut s_hdr[HDR_AHEAD_THREADS / 64u];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) s_hdr[w] = o;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        HeaderOut r = s_hdr[0];
+        for (uint32_t k = 1; k < HDR_AHEAD_THREADS / 64u; k++) header_merge(r, s_hdr[k]);
+        *a.out = r;
+        if (a.h_ctrl) {
+            SolverCtrl v = *a.ctrl;
+            v.seq = a.seq - 1u;
+            *a.h_ctrl = v;
+            *a.h_status = *a.status;
+            __threadfence_system();
+            ((volatile SolverCtrl*)a.h_ctrl)->seq = a.seq;
+        }
+    }
+}
 
 // ---- sph_sort.hip ------------------------------------------------------------------------------
 // Stable LSD radix sort of (key,val) pairs on `bits` key bits.  Returns 0 if the result is in
@@ -145,9 +200,17 @@ struct ReorderIO {   // the per-particle arrays a reorder moves (h2n, lam, szc: 
     uint8_t* szc_out;
 };
 size_t incremental_sort_block_sums(uint32_t ncells);
+// `fused` (the build a plain context queues ahead behind its integrating tail, classified by that tail): count and place in TWO
+// launches, and the count launch carries the reduction of the tail's header partials in a workgroup of its own -- no k_header_ahead
+// in front, no k_inc_scan between.  Scratch on top of the above: local[ncells + 1], the cell-range table in its two-level form
+// (sph_boundary_fused.hpp).
+struct IncFusedP {
+    uint32_t* local;
+    HeaderAheadP hdr;
+};
 void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, const float4* pm_new, const IncClassifyP& q, bool classified,
                                    const uint32_t* cell_start_cur, uint32_t* key_out, uint32_t* cell_start_out, const ReorderIO& io, uint32_t* bsum, uint32_t* movers,
-                                   uint32_t* movers_host);
+                                   uint32_t* movers_host, const IncFusedP* fused = nullptr);
 
 // ... for a slab rank behind its fused refresh: slots [0, n_prev) are last step's sorted array (those of class >= kg.gone_from in
 // kg.gone[0 .. kg.n_gone) left the rank and are not placed), [n_prev, n) this step's arrivals; sorted keys and the permutation
@@ -322,6 +385,8 @@ void launch_classify(hipStream_t s, Profiler* prof, uint32_t n, const float4* pm
                      const uint32_t* orig, DeviceStatus* status, const sph_params* p);
 // reduce the per-block header partials of the integrating final sweep into `out_dev` (skipped while the solve is not done)
 void launch_header_ahead(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool publish = false);   // publish: also k_publish's job (the next launch_publish is a no-op)
+// ... or its arguments, for the launch that carries the reduction instead (the fused k_inc_count: IncFusedP::hdr); the same bookkeeping
+HeaderAheadP header_ahead_args(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev, bool publish);
 // IISPH2: p /= sqrt(omega) on the current pressure buffer (+ p / rho^2), simulation.rs:2358-2360
 void launch_iisph2_scale(hipStream_t s, Profiler* prof, const SweepArgs& a);
 void launch_check_aii(hipStream_t s, Profiler* prof, const SweepArgs& a);   // after launch_aii_const when check_aii is set

@@ -313,13 +313,23 @@ __global__ __launch_bounds__(256) void k_inc_classify_slab(uint32_t n, uint32_t 
 
 // 2. new population of every cell = its stayers + the length of its list; per-block sums (INC_CELLS cells per block, one per thread:
 //    the chain range -> flags -> list is three dependent round trips, so the launch wants many short threads)
-#define INC_CELLS 1024
+//    FUSED (the build queued ahead behind the integrating tail: incremental_cell_sort_reorder with IncFusedP):
+//    - `count` receives the populations' exclusive prefix WITHIN the block (the two-level form of the table: sph_boundary_fused.hpp);
+//      the block sums and the mover counter are as in the other form, and nothing crosses from one workgroup to another inside the
+//      launch: the prefix of the block sums is taken behind the launch boundary, by the workgroups of k_inc_place_reorder that need it;
+//    - one more workgroup, the grid's last, reduces the header partials the tail in front left: k_header_ahead without its launch
+//      (header_ahead_block, sph_internal.hpp: it depends on that tail alone, and publishes where the caller waits behind it).
+template <bool FUSED>
 __global__ __launch_bounds__(INC_CELLS) void k_inc_count(IncGrid G, const uint32_t* __restrict__ cell_start_cur, const uint8_t* __restrict__ mv,
                                                           const uint32_t* __restrict__ next, const unsigned long long* __restrict__ head, uint32_t epoch,
-                                                          uint32_t* __restrict__ count /* cell_start of the next grid, used as scratch */, uint32_t* __restrict__ bsum,
-                                                          uint32_t* __restrict__ movers)
+                                                          uint32_t* __restrict__ count /* cell_start of the next grid, used as scratch (FUSED: the local prefixes) */,
+                                                          uint32_t* __restrict__ bsum, uint32_t* __restrict__ movers, HeaderAheadP hdr)
 {
     __shared__ uint32_t ws[INC_CELLS / 64], wm[INC_CELLS / 64];
+    if (FUSED && blockIdx.x + 1u == gridDim.x) {
+        header_ahead_block(hdr);
+        return;
+    }
     const uint32_t c = blockIdx.x * (uint32_t)INC_CELLS + threadIdx.x;
     uint32_t cnt = 0, listed = 0;
     if (c < G.nxt.ncells) {
@@ -330,18 +340,33 @@ __global__ __launch_bounds__(INC_CELLS) void k_inc_count(IncGrid G, const uint32
         if ((uint32_t)(h >> 32) == epoch)
             for (uint32_t m = (uint32_t)h; m; m = next[m - 1u]) listed++;
         cnt += listed;
-        count[c] = cnt;
+        if (!FUSED) count[c] = cnt;
     }
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     uint32_t x = cnt, y = listed;
-    for (int o = 32; o > 0; o >>= 1) {
-        x += (uint32_t)__shfl_xor((int)x, o, 64);
-        y += (uint32_t)__shfl_xor((int)y, o, 64);
+    if (FUSED) {   // x: inclusive prefix within the wave, lane 63 holds the wave's sum
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t u = __shfl_up(x, o, 64);
+            if (lane >= (uint32_t)o) x += u;
+        }
+        for (int o = 32; o > 0; o >>= 1) y += (uint32_t)__shfl_xor((int)y, o, 64);
+    } else {
+        for (int o = 32; o > 0; o >>= 1) {
+            x += (uint32_t)__shfl_xor((int)x, o, 64);
+            y += (uint32_t)__shfl_xor((int)y, o, 64);
+        }
     }
-    if ((threadIdx.x & 63) == 0) {
-        ws[threadIdx.x >> 6] = x;
-        wm[threadIdx.x >> 6] = y;
+    if (lane == 63u) {
+        ws[w] = x;
+        wm[w] = y;
     }
     __syncthreads();
+    if (FUSED && c < G.nxt.ncells) {
+        uint32_t base = 0;
+        for (uint32_t k = 0; k < w; k++) base += ws[k];
+        count[c] = base + x - cnt;
+    }
     if (threadIdx.x == 0) {
         uint32_t t = 0, m = 0;
         for (int k = 0; k < INC_CELLS / 64; k++) {
@@ -397,14 +422,50 @@ __global__ __launch_bounds__(256) void k_inc_scan(uint32_t ncells, uint32_t* __r
 //    coalesced reads -- a near-identity one -- and the permutation is never stored); the sorted keys as the radix sort leaves them
 //    PERM (a slab rank: the maps of its ghost layer are built from the permutation): slot -> current index instead of the reorder;
 //    slots that left the rank (flag 2) are not placed
-template <bool PERM>
+//    FUSED (behind k_inc_count<true>): cell_start_nxt is the table in its two-level form, first slot = local prefix + prefix of the
+//    block sums in front of the cell's count block (inc_cell_first).  Every workgroup takes that second level for itself, behind the
+//    launch boundary: every wave of the particles' workgroups scans the block sums in its registers, 256 at a time (a few hundred at
+//    2^20 particles: one 16-byte load per lane, no barrier), and the workgroups in front of them, one per count block, add up the sums in
+//    front of theirs as k_inc_scan does and write the finished table, [ncells] = the total, to cell_start_fin for the next step's
+//    BUILD (a buffer of its own: readers of the local form and finishers never touch the same words); the first of them hands the
+//    mover count to the host.  A lane past the last particle goes along with its wave's scan and stores nothing.
+template <bool PERM, bool FUSED>
 __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G, const uint32_t* __restrict__ cell_start_cur, const uint32_t* __restrict__ cell_start_nxt,
                                                             const uint32_t* __restrict__ nk, const uint8_t* __restrict__ mv, const uint32_t* __restrict__ next,
                                                             const unsigned long long* __restrict__ head, uint32_t epoch, const uint32_t* __restrict__ cxy_cur,
-                                                            uint32_t* __restrict__ key_out, ReorderIO io, uint32_t* __restrict__ perm_out)
+                                                            uint32_t* __restrict__ key_out, ReorderIO io, uint32_t* __restrict__ perm_out,
+                                                            const uint32_t* __restrict__ bsum, uint32_t* __restrict__ cell_start_fin, uint32_t* __restrict__ movers,
+                                                            uint32_t* __restrict__ movers_host)
 {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    __shared__ uint32_t s_w[4];
+    const uint32_t fin_blocks = FUSED ? inc_count_blocks(G.nxt.ncells) : 0u;   // (in FRONT of the particles': they run beside the first of them, not behind the last)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    if (FUSED && blockIdx.x < fin_blocks) {
+        const uint32_t ncells = G.nxt.ncells, blk = blockIdx.x, c0 = blk * (uint32_t)INC_CELLS + 4u * tid;
+        uint32_t pre = 0;
+        for (uint32_t k = tid; k < blk; k += 256u) pre += bsum[k];
+        for (int o = 32; o > 0; o >>= 1) pre += (uint32_t)__shfl_xor((int)pre, o, 64);
+        if (lane == 0) s_w[w] = pre;
+        __syncthreads();
+        pre = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        if (c0 + 3u < ncells) {
+            const uint4 l = *(const uint4*)(cell_start_nxt + c0);
+            *(uint4*)(cell_start_fin + c0) = make_uint4(l.x + pre, l.y + pre, l.z + pre, l.w + pre);
+        } else
+            for (uint32_t c = c0; c < ncells; c++) cell_start_fin[c] = cell_start_nxt[c] + pre;
+        if (tid == 0) {
+            if (blk + 1u == fin_blocks) cell_start_fin[ncells] = pre + bsum[blk];
+            if (blk == 0) {   // (as k_inc_scan's block 0)
+                *movers_host = *movers;
+                *movers = 0u;
+            }
+        }
+        return;
+    }
+    const uint32_t i_raw = (blockIdx.x - fin_blocks) * 256 + tid;
+    if (!FUSED && i_raw >= n) return;
+    const bool past = FUSED && i_raw >= n;
+    const uint32_t i = past ? n - 1u : i_raw;
     // (everything that does not depend on the slot is requested first)
     const uint32_t flag = mv[i];
     if (PERM && flag == 2u) return;
@@ -423,7 +484,34 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
         lvlold = io.lvlold_in[i];
     }
     const unsigned long long h = head[c];
-    const uint32_t first = cell_start_nxt[c];
+    uint32_t first = cell_start_nxt[c];
+    if (FUSED) {   // + the block sums in front of the cell's count block: every WAVE for itself, no barrier -- lane l takes the sums 4l .. 4l + 3 of a chunk of 256
+        const uint32_t cb = c >> INC_CELLS_LOG2;
+        uint32_t carry = 0, mine = 0;
+        for (uint32_t k0 = 0; k0 < fin_blocks; k0 += 256u) {   // (wave-uniform)
+            const uint32_t k = k0 + 4u * lane;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (k + 3u < fin_blocks) v = *(const uint4*)(bsum + k);
+            else {
+                if (k < fin_blocks) v.x = bsum[k];
+                if (k + 1u < fin_blocks) v.y = bsum[k + 1u];
+                if (k + 2u < fin_blocks) v.z = bsum[k + 2u];
+            }
+            const uint32_t own4 = v.x + v.y + v.z + v.w;
+            uint32_t z = own4;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t u = __shfl_up(z, o, 64);
+                if (lane >= (uint32_t)o) z += u;
+            }
+            const uint32_t excl = carry + z - own4;   // the sums in front of this lane's four
+            const uint32_t e = cb - k0, src = (e >> 2) & 63u, sub = e & 3u;   // the entry this lane's cell wants, if it lies in the chunk
+            const uint32_t ex = __shfl(excl, (int)src, 64), x0 = __shfl(v.x, (int)src, 64), x1 = __shfl(v.y, (int)src, 64), x2 = __shfl(v.z, (int)src, 64);
+            if (e < 256u) mine = ex + (sub > 0u ? x0 : 0u) + (sub > 1u ? x1 : 0u) + (sub > 2u ? x2 : 0u);
+            carry += __shfl(z, 63, 64);
+        }
+        first += mine;
+    }
     uint32_t b, e, r = 0;
     if (!mover) {   // the particle's own cell: no division
         const uint32_t k = (own & 0xffffu) + (own >> 16) * (uint32_t)G.cur.sx;
@@ -438,6 +526,7 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
     if ((uint32_t)(h >> 32) == epoch)
         for (uint32_t m = (uint32_t)h; m; m = next[m - 1u]) r += (m - 1u < i) ? 1u : 0u;
     const uint32_t dst = first + r;
+    if (past) return;
     key_out[dst] = c;
     if (PERM) {
         perm_out[dst] = i;
@@ -455,21 +544,35 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
     io.cxy_out[dst] = (c - cy * (uint32_t)G.nxt.sx) | (cy << 16);
 }
 
-size_t incremental_sort_block_sums(uint32_t ncells) { return ((size_t)ncells + INC_CELLS - 1) / INC_CELLS; }
+size_t incremental_sort_block_sums(uint32_t ncells) { return inc_count_blocks(ncells); }
 
 void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, const float4* pm_new, const IncClassifyP& q, bool classified,
                                    const uint32_t* cell_start_cur, uint32_t* key_out, uint32_t* cell_start_out, const ReorderIO& io, uint32_t* bsum, uint32_t* movers,
-                                   uint32_t* movers_host)
+                                   uint32_t* movers_host, const IncFusedP* fused)
 {
     const IncGrid G{q.cur, q.nxt};
     const uint32_t ncells = q.nxt.ncells, cblocks = (uint32_t)incremental_sort_block_sums(ncells);
+    if (fused && classified) {   // two launches; the header of the tail in front rides in the first
+        {
+            ProfScope ps(prof, "inc_count", s);
+            hipLaunchKernelGGL(k_inc_count<true>, dim3(cblocks + 1u), dim3(INC_CELLS), 0, s, G, cell_start_cur, q.mv, q.next, q.head, q.epoch, fused->local, bsum, movers,
+                               fused->hdr);
+        }
+        {
+            ProfScope ps(prof, "inc_reorder", s);
+            hipLaunchKernelGGL((k_inc_place_reorder<false, true>), dim3((n + 255) / 256 + cblocks), dim3(256), 0, s, n, G, cell_start_cur, (const uint32_t*)fused->local,
+                               q.nk, q.mv, q.next, q.head, q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)bsum, cell_start_out, movers, movers_host);
+        }
+        return;
+    }
     if (!classified) {
         ProfScope ps(prof, "inc_classify", s);
         hipLaunchKernelGGL(k_inc_classify, dim3((n + 255) / 256), dim3(256), 0, s, n, pm_new, q);
     }
     {
         ProfScope ps(prof, "inc_count", s);
-        hipLaunchKernelGGL(k_inc_count, dim3(cblocks), dim3(INC_CELLS), 0, s, G, cell_start_cur, q.mv, q.next, q.head, q.epoch, cell_start_out, bsum, movers);
+        hipLaunchKernelGGL(k_inc_count<false>, dim3(cblocks), dim3(INC_CELLS), 0, s, G, cell_start_cur, q.mv, q.next, q.head, q.epoch, cell_start_out, bsum, movers,
+                           HeaderAheadP{});
     }
     {
         ProfScope ps(prof, "inc_scan", s);
@@ -477,8 +580,8 @@ void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, co
     }
     {
         ProfScope ps(prof, "inc_reorder", s);
-        hipLaunchKernelGGL(k_inc_place_reorder<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head,
-                           q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_inc_place_reorder<false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head,
+                           q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     }
 }
 
@@ -493,7 +596,8 @@ void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint3
     }
     {
         ProfScope ps(prof, "inc_count", s);
-        hipLaunchKernelGGL(k_inc_count, dim3(cblocks), dim3(INC_CELLS), 0, s, G, cell_start_cur, q.mv, q.next, q.head, q.epoch, cell_start_out, bsum, movers);
+        hipLaunchKernelGGL(k_inc_count<false>, dim3(cblocks), dim3(INC_CELLS), 0, s, G, cell_start_cur, q.mv, q.next, q.head, q.epoch, cell_start_out, bsum, movers,
+                           HeaderAheadP{});
     }
     {
         ProfScope ps(prof, "inc_scan", s);
@@ -501,8 +605,8 @@ void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint3
     }
     {
         ProfScope ps(prof, "inc_place", s);
-        hipLaunchKernelGGL(k_inc_place_reorder<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head, q.epoch,
-                           q.cxy_cur, key_out, ReorderIO{}, perm_out);
+        hipLaunchKernelGGL((k_inc_place_reorder<true, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head,
+                           q.epoch, q.cxy_cur, key_out, ReorderIO{}, perm_out, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     }
 }
 

@@ -362,6 +362,7 @@ struct SolveQ {
     bool density_solver;
     int tot_slot = 0;   // slab decomposition: which totals buffer the solve all-reduces (1: the gated solve of a chained pair)
     uint32_t k = 1, upto = 2;
+    bool header_in_build = false;   // the build the caller queues right behind this solve's integrating tail reduces the tail's header partials (the fused merge: no k_header_ahead)
     void extend() { upto = k + std::max(1u, k / 4u); }   // a quarter more iterations per wait, at least one: a skipped
                                                          // iteration costs two empty launches (~9 us), a wait the round trip to the host
                                                          // (measured on the driver window, 5 runs each: k/4 1.279-1.295 ms per step, k/2 1.284-1.292, k 1.300-1.311)
@@ -497,7 +498,8 @@ static int solve_queue(Group& G, std::vector<Member>& M, SolveQ& q, bool handoff
         launch_solver_tail(m.c->stream, &m.c->prof, m.a, q.tail, m.c->pm[m.c->pcur ^ 1].as<float4>(), -1, q.residual_density,
                            q.max_avg_error, q.max_iters, hand_host, gate_out);
         if (q.tail == 1 /* TAIL_VEL */ && source_term_on_records(m.a)) m.a.xv_ok = true;   // (the tail rewrote the {x, y, v} record with the velocities it left)
-        if (q.tail >= 2 /* TAIL_VX, TAIL_HYBRID */ && m.a.hdr_partials) launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev, publish_next && !multi);
+        if (q.tail >= 2 /* TAIL_VX, TAIL_HYBRID */ && m.a.hdr_partials && !q.header_in_build)
+            launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev, publish_next && !multi);
     }
     return SPH_OK;
 }
@@ -607,11 +609,13 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
 // iisph_pressure_iterations (simulation.rs:1377-1516) with a host wait of its own
 static int pressure_iterations(Group& G, std::vector<Member>& M, float max_avg_error, int residual_density, uint32_t max_iters,
                                uint32_t predicted_iters, int tail, bool density_solver, bool final_solve,
-                               const std::function<int()>* behind_tail = nullptr /* paced: queued behind the solve's tail, in front of the wait */)
+                               const std::function<int()>* behind_tail = nullptr /* paced: queued behind the solve's tail, in front of the wait */,
+                               bool header_in_build = false /* SolveQ::header_in_build: `behind_tail` queues the fused merge */)
 {
     int rc;
     const int multi = G.multi() ? 1 : 0;
     SolveQ q{max_avg_error, residual_density, max_iters, tail, density_solver};
+    q.header_in_build = header_in_build && behind_tail != nullptr;
     // (a slab decomposition paces whether or not THIS rank has particles: every rank must queue the same collectives -- an empty
     //  slab's progress word is published by a launch of its own, launch_solver_progress)
     if ((multi || M[0].n > 0) && M[0].c->paced_step) {
@@ -669,8 +673,8 @@ static void radix_cell_build(sph_ctx* c, const CellSortBufs& v, const CellKeyGen
 }
 
 // scratch of the incremental sort for a grid of `ncells`: per-cell list heads (zeroed when allocated, never cleared: every call tags its
-// lists with a new epoch, never 0), list links, block sums, the mover counter
-static int ensure_inc_sort_scratch(sph_ctx* c, uint32_t ncells)
+// lists with a new epoch, never 0), list links, block sums, the mover counter; `fused`: what the two-launch form adds
+static int ensure_inc_sort_scratch(sph_ctx* c, uint32_t ncells, bool fused = false)
 {
     const size_t head_before = c->inc_head.bytes;
     HIPCHK(c, c->inc_head.ensure((size_t)ncells * 8));
@@ -680,6 +684,9 @@ static int ensure_inc_sort_scratch(sph_ctx* c, uint32_t ncells)
     if (!c->inc_movers.p) {
         HIPCHK(c, c->inc_movers.ensure(4));
         HIPCHK(c, hipMemsetAsync(c->inc_movers.p, 0, 4, c->stream));
+    }
+    if (fused) {   // (IncFusedP, sph_internal.hpp)
+        HIPCHK(c, c->inc_local.ensure(((size_t)ncells + 1) * 4));
     }
     if (++c->inc_epoch == 0u) c->inc_epoch = 1u;
     return SPH_OK;
@@ -1480,7 +1487,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     // tail of that solve classifies the particles for the incremental sort while it holds their new positions -- and
     // queue_ahead_build() behind the tail.
     struct AheadPlan {
-        bool on = false, incremental = false;
+        bool on = false, incremental = false, fused = false;
         GridP g{};
         int tile_ts = 0, tile_tsx = 0, tile_tsy = 0;
         IncClassifyP q{};
@@ -1525,7 +1532,12 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         if (!(c->opt.inc_sort && c->grid_valid && c->fgrid.cs == cs && c->fgrid.ncells > 0 && inc_sort_fits(g.ncells, n) &&
               inc_sort_worthwhile(c->inc_count_valid, *c->movers_host, inc_sort_mover_limit(n, c->opt.inc_sort), c->inc_radix_streak)))
             return SPH_OK;
-        if ((rc = ensure_inc_sort_scratch(c, g.ncells))) return rc;
+        // Fused (the default): the merge right behind the tail that classifies for it -- every step without the level estimation, whose
+        // build waits for the smoothing -- takes the tail's header reduction into its count launch and the block-sum scan with it:
+        // tail, count, place where there were tail, k_header_ahead, count, k_inc_scan, place (sph_sort.hip).  solve_queue() then
+        // launches no k_header_ahead behind that tail (SolveQ::header_in_build), and queue_ahead_build() is the next thing queued.
+        plan.fused = c->opt.boundary_fused != 0 && !level_on && M[0].a.hdr_partials != nullptr;
+        if ((rc = ensure_inc_sort_scratch(c, g.ncells, plan.fused))) return rc;
         plan.incremental = true;
         plan.q = IncClassifyP{c->fgrid, g, c->cxy.as<uint32_t>(), c->akey[1].as<uint32_t>(), c->aval[1].as<uint8_t>(), c->inc_next.as<uint32_t>(),
                               c->inc_head.as<unsigned long long>(), c->inc_epoch};
@@ -1546,9 +1558,14 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const float4* integrated = c->pm[c->pcur ^ 1].as<float4>();   // (the tail's output; the step's end flips pcur)
         if (plan.incremental) {
             // (without the lambda sums of this step: only FromDistribution* reads them next step, and a step in that mode does not adopt this build)
+            // (fused: the header of the tail just queued, published to the wait that follows -- what solve_queue() left out)
+            IncFusedP fused{};
+            if (plan.fused) {
+                fused = IncFusedP{c->inc_local.as<uint32_t>(), header_ahead_args(c, (n + 255u) / 256u, c->hdr_host_dev, true)};
+            }
             incremental_cell_sort_reorder(s, &c->prof, n, integrated, plan.q, /* classified by the tail */ true, c->cell_start.as<uint32_t>(), c->akey[0].as<uint32_t>(),
                                           c->acell_start.as<uint32_t>(), reorder_io(c, integrated, c->pm2.as<float4>(), c->acxy.as<uint32_t>(), false),
-                                          c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1);
+                                          c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1, plan.fused ? &fused : nullptr);
             c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
         } else {
             const CellKeyGen kg{integrated, g, nullptr, 0u, (uint32_t)SC_GONE_FROM, 1};   // (clamped keys: the grid is a prediction)
@@ -1576,7 +1593,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         rec(4);
         begin_solve(1, 1);
         if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, p->iisph_max_avg_density_error, 1, p->max_iters, c0->last_dens_iters, T_VX, true, !level_on, &queue_ahead_build))) return rc;
+        if ((rc = pressure_iterations(G, M, p->iisph_max_avg_density_error, 1, p->max_iters, c0->last_dens_iters, T_VX, true, !level_on, &queue_ahead_build, plan.fused))) return rc;
         rec(5);
         break;
     case SPH_SOLVER_IISPH2:  // simulation.rs:2262-2387: omega rides in the source-term sweep; p /= sqrt(omega) before the last a^p
@@ -1605,7 +1622,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         rec(2);
         begin_solve(0, 0);
         if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, c0->last_div_iters, T_VX, false, !level_on, &queue_ahead_build))) return rc;
+        if ((rc = pressure_iterations(G, M, p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, c0->last_div_iters, T_VX, false, !level_on, &queue_ahead_build, plan.fused))) return rc;
         rec(3);
         break;
     default: {  // HybridDFSPH, simulation.rs:2502-2670
@@ -1639,6 +1656,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             rec(4);
             begin_solve(p->hybrid_dfsph_density_source_term == SPH_ONLY_DENSITY ? 2 : 1, 1);
             if ((rc = plan_ahead_build())) return rc;
+            qs.header_in_build = plan.fused;   // (queue_ahead_build() right behind the tail)
             if ((rc = solve_paced(G, M, qs, pace_prediction(c0, M[0].n, c0->last_dens_iters, c0->prev_dens_iters)))) return rc;
             if ((rc = solve_queue(G, M, qs, false, true))) return rc;
             if ((rc = queue_ahead_build())) return rc;
