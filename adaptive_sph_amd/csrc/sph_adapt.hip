@@ -19,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "sph_candidates.hpp"
 #include "sph_dist.hpp"
 #include "sph_slab_partner_problem.h"
 #include "sph_target_mass.hpp"
@@ -673,9 +674,22 @@ __global__ __launch_bounds__(256) void k_slab_split_apply(uint32_t n_tot, uint32
     g.szc_out[f] = g.szc_in[s];
 }
 
-static float* sel_adapt_pm(Member& m) { return m.lv_pmnew; }
-static float* sel_adapt_vel(Member& m) { return (float*)m.a.vel; }
-static float* sel_adapt_lvl(Member& m) { return m.lv_level; }
+int refresh_ghost_state(Group& G, bool with_velocity)
+{
+    std::vector<Member> M(G.m.size());
+    for (size_t i = 0; i < M.size(); i++) {
+        sph_ctx* c = G.m[i];
+        M[i].c = c;
+        M[i].n = c->dist.n_tot;
+        M[i].lv_pmnew = (float*)c->pm[c->pcur].as<float4>();
+        M[i].lv_level = c->lvl[c->cur].as<float>();
+        M[i].a.vel = c->vel[c->cur].as<float2>();
+    }
+    if (int rc = refresh_ghosts(G, M, [](Member& m) { return m.lv_pmnew; }, 4, "pm")) return rc;
+    if (with_velocity)
+        if (int rc = refresh_ghosts(G, M, [](Member& m) { return (float*)m.a.vel; }, 2, "vel")) return rc;
+    return refresh_ghosts(G, M, [](Member& m) { return m.lv_level; }, 1, "level");
+}
 
 static SlabGather slab_gather_of(sph_ctx* c)
 {
@@ -698,72 +712,31 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
 }
 
 // The decisions of a COMPACT problem (include/sph_slab_partner_problem.h): k participants by ascending global id, a partner named by its
-// compact id.  k_slab_expand is the slab form of k_prob_expand (sph_partner_problem.hip): one thread per participant scatters its pair
-// into merge_partner / merge_counter of the whole vector (pre-filled with AVAILABLE / 0), the partner mapped through ids.
+// compact id.
 struct SlabCompact {
     uint64_t k;
     const uint32_t* ids;
     const uint32_t* partner_c;
     const uint16_t* counter_c;
 };
-__global__ __launch_bounds__(256) void k_slab_expand(uint32_t K, uint32_t n_global, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ partner_c,
-                                                      const uint16_t* __restrict__ counter_c, uint32_t* __restrict__ partner, uint16_t* __restrict__ counter)
-{
-    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= K) return;
-    const uint32_t i = ids[c];
-    if (i >= n_global) return;   // (the host check refused it)
-    uint32_t pc = partner_c[c];
-    if (pc != SPH_MERGE_PARTNER_AVAILABLE && pc != SPH_MERGE_PARTNER_DELETE) {
-        pc = pc < K ? ids[pc] : SPH_MERGE_PARTNER_AVAILABLE;   // (the host check refused pc >= K)
-        if (pc >= n_global) pc = SPH_MERGE_PARTNER_AVAILABLE;
-    }
-    partner[i] = pc;
-    counter[i] = counter_c[c];
-}
-// merge_partner / merge_counter of the whole vector on a member's device: copied from the host's arrays, or (cd) filled with AVAILABLE / 0
-// and scattered from the k decisions -- 10 B per participant go up instead of 6 B per particle.  Everything behind this point reads the
-// two arrays and does not know which form they came in.  up_*: staging that lives as long as the arrays
+// merge_partner / merge_counter of the whole vector on a member's device: copied from the host's arrays, or (cd) expanded from the k
+// decisions (prob_expand, sph_partner_problem.hip) -- 10 B per participant go up instead of 6 B per particle.  Everything behind this
+// point reads the two arrays and does not know which form they came in.  up_*: staging that lives as long as the arrays
 static int slab_decisions_to_device(sph_ctx* c, hipStream_t s, uint32_t n_global, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd,
                                     uint32_t* d_partner, uint16_t* d_counter, TmpBuf& up_ids, TmpBuf& up_partner, TmpBuf& up_counter)
 {
-    if (!cd) {
-        HIPCHK(c, hipMemcpyAsync(d_partner, partner, (size_t)n_global * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(d_counter, counter, (size_t)n_global * 2, hipMemcpyHostToDevice, s));
-        return SPH_OK;
-    }
-    ProfScope ps(&c->prof, "slab_problem_expand", s);
-    HIPCHK(c, hipMemsetAsync(d_partner, 0xff, (size_t)n_global * 4, s));   // SPH_MERGE_PARTNER_AVAILABLE
-    HIPCHK(c, hipMemsetAsync(d_counter, 0, (size_t)n_global * 2, s));
-    const size_t k = (size_t)cd->k;
-    if (!k) return SPH_OK;
-    HIPCHK(c, up_ids.ensure(k * 4));
-    HIPCHK(c, up_partner.ensure(k * 4));
-    HIPCHK(c, up_counter.ensure(k * 2));
-    HIPCHK(c, hipMemcpyAsync(up_ids.p, cd->ids, k * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(up_partner.p, cd->partner_c, k * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(up_counter.p, cd->counter_c, k * 2, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_slab_expand, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, s, (uint32_t)k, n_global, (const uint32_t*)up_ids.as<uint32_t>(),
-                       (const uint32_t*)up_partner.as<uint32_t>(), (const uint16_t*)up_counter.as<uint16_t>(), d_partner, d_counter);
+    if (cd) return prob_expand(c, "slab_problem_expand", n_global, (uint32_t)cd->k, cd->ids, cd->partner_c, cd->counter_c, d_partner, d_counter, ExpandStage{&up_ids, &up_partner, &up_counter});
+    HIPCHK(c, hipMemcpyAsync(d_partner, partner, (size_t)n_global * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_counter, counter, (size_t)n_global * 2, hipMemcpyHostToDevice, s));
     return SPH_OK;
 }
 
-// op: 0 share, 1 merge, 2 split -- for every member of the group (collective over ALL ranks of the decomposition)
-// A HIP failure INSIDE one of slab_adapt's per-member loops must not return before the collective that follows (agree, an all-reduce): under
-// a per-rank transport the other ranks would wait in it for ever (advisor r4).  It becomes this rank's local_rc and leaves the loop;
-// agree() then ends the call on every rank together.
-#define HIPLOC(ctx, call)                                                                                            \
-    {                                                                                                                \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) {                                                                                      \
-            local_rc = (ctx)->fail(SPH_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));                   \
-            break;                                                                                                   \
-        }                                                                                                            \
-    }
-// cd: the decisions come as a compact problem (partner / counter unused).  *alike (optional): the refusal is every rank's alike and came
-// between two collectives -- nobody is left waiting, the transport stays usable
+// op: 0 share, 1 merge, 2 split -- for every member of the group (collective over ALL ranks of the decomposition; the work on the
+// members is the body of each_member: the collective rule, sph_dist.hpp)
+// cd: the decisions come as a compact problem (partner / counter unused).  *together (optional): as rank_entry reads it -- here the one
+// refusal every rank takes alike between two collectives
 static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd = nullptr,
-                      bool* alike = nullptr)
+                      bool* together = nullptr)
 {
     const size_t nm = G.m.size();
     int rc = SPH_OK;
@@ -783,26 +756,14 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
         n_global = rows[0][0];
     }
     if (cd && cd->k && cd->ids[cd->k - 1] >= n_global) {   // (ascending: the last id is the largest.  Every rank holds the same ids and the same sum)
-        if (alike) *alike = true;
+        if (together) *together = true;
         return G.m[0]->fail(SPH_ERR_INVALID_ARGUMENT, "ids holds %u, the vector has %u particles", cd->ids[cd->k - 1], n_global);
     }
     if (n_global == 0) return SPH_OK;
     // ---- the ghosts' records as their owners hold them now
-    std::vector<Member> M(nm);
-    for (size_t i = 0; i < nm; i++) {
-        sph_ctx* c = G.m[i];
-        M[i].c = c;
-        M[i].n = c->dist.n_tot;
-        M[i].lv_pmnew = (float*)c->pm[c->pcur].as<float4>();
-        M[i].lv_level = c->lvl[c->cur].as<float>();
-        M[i].a.vel = c->vel[c->cur].as<float2>();
-    }
-    if ((rc = refresh_ghosts(G, M, sel_adapt_pm, 4, "pm"))) return rc;
-    if ((rc = refresh_ghosts(G, M, sel_adapt_vel, 2, "vel"))) return rc;
-    if ((rc = refresh_ghosts(G, M, sel_adapt_lvl, 1, "level"))) return rc;
+    if ((rc = refresh_ghost_state(G, true))) return rc;
     const TargetP tp = target_params(p);
     const dim3 blk(256);
-    int local_rc = SPH_OK;
     std::vector<TmpBuf> B(nm * 15);
     auto buf = [&](size_t i, int k) -> TmpBuf& { return B[i * 15 + (size_t)k]; };
     enum { B_PARTNER, B_COUNTER, B_SLOT, B_DEL, B_BEFORE, B_SCRATCH, B_HOLES, B_SRC, B_NEWID, B_KEEP, B_POS, B_EXTRA, B_UP_IDS, B_UP_PARTNER, B_UP_COUNTER };
@@ -811,25 +772,23 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
         const int merging = op == 1;
         const uint32_t min_partners = merging ? ap->minimum_merge_partners : ap->minimum_share_partners;
         uint32_t n_del = 0, n_new_global = n_global;
-        for (size_t i = 0; i < nm && !local_rc; i++) {
-            sph_ctx* c = G.m[i];
-            HIPLOC(c, hipSetDevice(c->device));
+        rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
             hipStream_t s = c->stream;
             const uint32_t nt = c->dist.n_tot;
             const int k = c->cur;
-            if ((local_rc = need(c, buf(i, B_PARTNER), (size_t)n_global * 4)) || (local_rc = need(c, buf(i, B_COUNTER), (size_t)n_global * 2)) ||
-                (local_rc = need(c, buf(i, B_SLOT), (size_t)n_global * 4)))
-                break;
-            if ((local_rc = slab_decisions_to_device(c, s, n_global, partner, counter, cd, buf(i, B_PARTNER).as<uint32_t>(), buf(i, B_COUNTER).as<uint16_t>(), buf(i, B_UP_IDS),
-                                                     buf(i, B_UP_PARTNER), buf(i, B_UP_COUNTER))))
-                break;
-            HIPLOC(c, hipMemsetAsync(buf(i, B_SLOT).p, 0xff, (size_t)n_global * 4, s));
-            if (!nt) continue;
+            int r;
+            if ((r = need(c, buf(i, B_PARTNER), (size_t)n_global * 4)) || (r = need(c, buf(i, B_COUNTER), (size_t)n_global * 2)) || (r = need(c, buf(i, B_SLOT), (size_t)n_global * 4)))
+                return r;
+            if ((r = slab_decisions_to_device(c, s, n_global, partner, counter, cd, buf(i, B_PARTNER).as<uint32_t>(), buf(i, B_COUNTER).as<uint16_t>(), buf(i, B_UP_IDS),
+                                              buf(i, B_UP_PARTNER), buf(i, B_UP_COUNTER))))
+                return r;
+            HIPCHK(c, hipMemsetAsync(buf(i, B_SLOT).p, 0xff, (size_t)n_global * 4, s));
+            if (!nt) return SPH_OK;
             const dim3 grid((nt + 255) / 256);
             hipLaunchKernelGGL(k_slab_slot_of, grid, blk, 0, s, nt, c->orig[k].as<uint32_t>(), n_global, buf(i, B_SLOT).as<uint32_t>(), c->status.as<DeviceStatus>());
             // receivers write the other record / velocity buffers, which first take a copy of the current ones (donors, bystanders)
-            HIPLOC(c, hipMemcpyAsync(c->pm[c->pcur ^ 1].p, c->pm[c->pcur].p, (size_t)nt * sizeof(float4), hipMemcpyDeviceToDevice, s));
-            HIPLOC(c, hipMemcpyAsync(c->vel[k ^ 1].p, c->vel[k].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(c->pm[c->pcur ^ 1].p, c->pm[c->pcur].p, (size_t)nt * sizeof(float4), hipMemcpyDeviceToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(c->vel[k ^ 1].p, c->vel[k].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
             hipLaunchKernelGGL(k_slab_receive, grid, blk, 0, s, nt, merging, c->dist.owned.as<uint8_t>(), c->orig[k].as<uint32_t>(), buf(i, B_SLOT).as<uint32_t>(), n_global,
                                buf(i, B_PARTNER).as<uint32_t>(), buf(i, B_COUNTER).as<uint16_t>(), min_partners, ap->dt, ap->max_mass_transfer_sharing, tp,
                                c->pm[c->pcur].as<float4>(), c->vel[k].as<float2>(), c->pm[c->pcur ^ 1].as<float4>(), c->vel[k ^ 1].as<float2>(), c->lvl[k].as<float>(),
@@ -838,42 +797,41 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
                                buf(i, B_COUNTER).as<uint16_t>(), min_partners, ap->dt, ap->max_mass_transfer_sharing, tp, c->pm[c->pcur ^ 1].as<float4>(), c->lvl[k].as<float>(),
                                c->h2n[k].as<float>());
             // the updated records become the current ones (velocities likewise); the slots stay where they are
-            HIPLOC(c, hipMemcpyAsync(c->pm[c->pcur].p, c->pm[c->pcur ^ 1].p, (size_t)nt * sizeof(float4), hipMemcpyDeviceToDevice, s));
-            HIPLOC(c, hipMemcpyAsync(c->vel[k].p, c->vel[k ^ 1].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
-            int r2 = check_status(c, "merge_partner holds an index outside the particle vector, or a donor that is not a neighbour of its receiver");
-            if (r2) local_rc = r2;
-            c->drop(DROPS_TRANSFER);
-        }
-        if ((rc = agree(G, local_rc))) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->pm[c->pcur].p, c->pm[c->pcur ^ 1].p, (size_t)nt * sizeof(float4), hipMemcpyDeviceToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(c->vel[k].p, c->vel[k ^ 1].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
+            r = check_status(c, "merge_partner holds an index outside the particle vector, or a donor that is not a neighbour of its receiver");
+            c->drop(DROPS_TRANSFER);   // (also behind a failed check: the records were written)
+            return r;
+        });
+        if (rc) return rc;
         if (!merging) return SPH_OK;
         // ---- delete: every rank derives the new index of every id from the two global arrays
-        for (size_t i = 0; i < nm && !local_rc; i++) {
-            sph_ctx* c = G.m[i];
-            HIPLOC(c, hipSetDevice(c->device));
+        rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
             hipStream_t s = c->stream;
-            if ((local_rc = need(c, buf(i, B_DEL), (size_t)n_global * 4)) || (local_rc = need(c, buf(i, B_BEFORE), (size_t)n_global * 4 + 4)) ||
-                (local_rc = need(c, buf(i, B_SCRATCH), ((size_t)n_global / SCAN_TILE + 4) * 4)) || (local_rc = need(c, buf(i, B_HOLES), (size_t)n_global * 4)))
-                break;
+            int r;
+            if ((r = need(c, buf(i, B_DEL), (size_t)n_global * 4)) || (r = need(c, buf(i, B_BEFORE), (size_t)n_global * 4 + 4)) ||
+                (r = need(c, buf(i, B_SCRATCH), ((size_t)n_global / SCAN_TILE + 4) * 4)) || (r = need(c, buf(i, B_HOLES), (size_t)n_global * 4)))
+                return r;
             hipLaunchKernelGGL(k_slab_del_flags, dim3((n_global + 255) / 256), blk, 0, s, n_global, buf(i, B_PARTNER).as<uint32_t>(), buf(i, B_COUNTER).as<uint16_t>(),
                                min_partners, buf(i, B_DEL).as<uint32_t>());
             uint32_t* d_total = buf(i, B_BEFORE).as<uint32_t>() + n_global;
             device_exclusive_scan_u32(s, buf(i, B_DEL).as<uint32_t>(), buf(i, B_BEFORE).as<uint32_t>(), n_global, buf(i, B_SCRATCH).as<uint32_t>(), d_total);
             uint32_t nd = 0;
-            HIPLOC(c, hipMemcpyAsync(&nd, d_total, 4, hipMemcpyDeviceToHost, s));
-            HIPLOC(c, hipStreamSynchronize(s));
+            HIPCHK(c, hipMemcpyAsync(&nd, d_total, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
             n_del = nd;   // (the same on every member: the same arrays)
-        }
-        if ((rc = agree(G, local_rc))) return rc;
+            return SPH_OK;
+        });
+        if (rc) return rc;
         if (n_del == 0) return SPH_OK;
         n_new_global = n_global - n_del;
-        for (size_t i = 0; i < nm && !local_rc; i++) {
-            sph_ctx* c = G.m[i];
-            HIPLOC(c, hipSetDevice(c->device));
+        return each_member(G, [&](size_t i, sph_ctx* c) -> int {
             hipStream_t s = c->stream;
             const uint32_t nt = c->dist.n_tot;
-            if ((local_rc = need(c, buf(i, B_SRC), ((size_t)n_new_global + 1) * sizeof(EditSrc))) || (local_rc = need(c, buf(i, B_NEWID), (size_t)n_global * 4)) ||
-                (local_rc = need(c, buf(i, B_KEEP), (size_t)nt * 4 + 4)) || (local_rc = need(c, buf(i, B_POS), (size_t)nt * 4 + 8)))
-                break;
+            int r;
+            if ((r = need(c, buf(i, B_SRC), ((size_t)n_new_global + 1) * sizeof(EditSrc))) || (r = need(c, buf(i, B_NEWID), (size_t)n_global * 4)) ||
+                (r = need(c, buf(i, B_KEEP), (size_t)nt * 4 + 4)) || (r = need(c, buf(i, B_POS), (size_t)nt * 4 + 8)))
+                return r;
             if (n_new_global) {
                 hipLaunchKernelGGL(k_merge_holes, dim3((n_new_global + 255) / 256), blk, 0, s, n_global, n_new_global, buf(i, B_DEL).as<uint32_t>(), buf(i, B_BEFORE).as<uint32_t>(),
                                    buf(i, B_HOLES).as<uint32_t>(), buf(i, B_SRC).as<EditSrc>());
@@ -888,58 +846,53 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
                 uint32_t* d_tot = buf(i, B_POS).as<uint32_t>() + nt;
                 device_exclusive_scan_u32(s, buf(i, B_KEEP).as<uint32_t>(), buf(i, B_POS).as<uint32_t>(), nt, buf(i, B_SCRATCH).as<uint32_t>(), d_tot);
                 hipLaunchKernelGGL(k_slab_compact, grid, blk, 0, s, nt, buf(i, B_KEEP).as<uint32_t>(), buf(i, B_POS).as<uint32_t>(), buf(i, B_NEWID).as<uint32_t>(), slab_gather_of(c));
-                HIPLOC(c, hipMemcpyAsync(&n_keep, d_tot, 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(c, hipMemcpyAsync(&n_keep, d_tot, 4, hipMemcpyDeviceToHost, s));
             }
-            HIPLOC(c, hipStreamSynchronize(s));
+            HIPCHK(c, hipStreamSynchronize(s));
             slab_after_regather(c, n_keep);
-        }
-        return agree(G, local_rc);
+            return SPH_OK;
+        });
     }
     // ---- split
     uint32_t n_extra_global = 0;
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        HIPLOC(c, hipSetDevice(c->device));
+    rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
         hipStream_t s = c->stream;
         const uint32_t nt = c->dist.n_tot;
-        if ((local_rc = need(c, buf(i, B_EXTRA), (size_t)nt * 4 + 4)) || (local_rc = need(c, buf(i, B_DEL), (size_t)n_global * 4)) ||
-            (local_rc = need(c, buf(i, B_BEFORE), (size_t)n_global * 4 + 4)) || (local_rc = need(c, buf(i, B_SCRATCH), ((size_t)std::max(n_global, nt) / SCAN_TILE + 4) * 4)))
-            break;
-        HIPLOC(c, hipMemsetAsync(buf(i, B_DEL).p, 0, (size_t)n_global * 4, s));   // (B_DEL: the child counts - 1 of the whole vector, by id)
+        int r;
+        if ((r = need(c, buf(i, B_EXTRA), (size_t)nt * 4 + 4)) || (r = need(c, buf(i, B_DEL), (size_t)n_global * 4)) || (r = need(c, buf(i, B_BEFORE), (size_t)n_global * 4 + 4)) ||
+            (r = need(c, buf(i, B_SCRATCH), ((size_t)std::max(n_global, nt) / SCAN_TILE + 4) * 4)))
+            return r;
+        HIPCHK(c, hipMemsetAsync(buf(i, B_DEL).p, 0, (size_t)n_global * 4, s));   // (B_DEL: the child counts - 1 of the whole vector, by id)
         if (nt)
             hipLaunchKernelGGL(k_slab_split_count, dim3((nt + 255) / 256), blk, 0, s, nt, c->dist.owned.as<uint8_t>(), c->orig[c->cur].as<uint32_t>(), c->pm[c->pcur].as<float4>(),
                                c->lvl[c->cur].as<float>(), c->szc[c->cur].as<uint8_t>(), tp, c->n_split_patterns + 1u, ap->fail_on_missing_split_pattern,
                                buf(i, B_EXTRA).as<uint32_t>(), buf(i, B_DEL).as<uint32_t>(), c->status.as<DeviceStatus>());
-        int r2 = check_status(c, "no split pattern for this split, or num_children <= 1");
-        if (r2) local_rc = r2;
-    }
-    if ((rc = agree(G, local_rc))) return rc;
+        return check_status(c, "no split pattern for this split, or num_children <= 1");
+    });
+    if (rc) return rc;
     {
         std::vector<uint32_t*> bufs(nm);
         for (size_t i = 0; i < nm; i++) bufs[i] = buf(i, B_DEL).as<uint32_t>();
         if ((rc = G.comm->allreduce_sum_u32_dev(G, bufs, n_global))) return rc;
     }
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        HIPLOC(c, hipSetDevice(c->device));
+    rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
         hipStream_t s = c->stream;
         uint32_t* d_total = buf(i, B_BEFORE).as<uint32_t>() + n_global;
         device_exclusive_scan_u32(s, buf(i, B_DEL).as<uint32_t>(), buf(i, B_BEFORE).as<uint32_t>(), n_global, buf(i, B_SCRATCH).as<uint32_t>(), d_total);
         uint32_t ne = 0;
-        HIPLOC(c, hipMemcpyAsync(&ne, d_total, 4, hipMemcpyDeviceToHost, s));
-        HIPLOC(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipMemcpyAsync(&ne, d_total, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
         n_extra_global = ne;
-    }
-    if ((rc = agree(G, local_rc))) return rc;
+        return SPH_OK;
+    });
+    if (rc) return rc;
     if (n_extra_global == 0) return SPH_OK;
     if ((uint64_t)n_global + n_extra_global >= 0xfffffff0ull) return G.m[0]->fail(SPH_ERR_CAPACITY, "splitting needs %llu particle ids", (unsigned long long)n_global + n_extra_global);
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        HIPLOC(c, hipSetDevice(c->device));
+    return each_member(G, [&](size_t i, sph_ctx* c) -> int {
         hipStream_t s = c->stream;
         const uint32_t nt = c->dist.n_tot, n_own = (uint32_t)c->n;
-        if ((local_rc = need(c, buf(i, B_KEEP), (size_t)nt * 4 + 4)) || (local_rc = need(c, buf(i, B_POS), (size_t)nt * 4 + 8)) || (local_rc = need(c, buf(i, B_HOLES), (size_t)nt * 4 + 8)))
-            break;
+        int r;
+        if ((r = need(c, buf(i, B_KEEP), (size_t)nt * 4 + 4)) || (r = need(c, buf(i, B_POS), (size_t)nt * 4 + 8)) || (r = need(c, buf(i, B_HOLES), (size_t)nt * 4 + 8))) return r;
         uint32_t n_children = 0, n_keep = 0;
         if (nt) {
             const dim3 grid((nt + 255) / 256);
@@ -948,49 +901,34 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             device_exclusive_scan_u32(s, buf(i, B_KEEP).as<uint32_t>(), buf(i, B_POS).as<uint32_t>(), nt, buf(i, B_SCRATCH).as<uint32_t>(), d_tot);
             uint32_t* d_tot2 = buf(i, B_HOLES).as<uint32_t>() + nt;   // (B_HOLES: exclusive prefix of the children over the slots)
             device_exclusive_scan_u32(s, buf(i, B_EXTRA).as<uint32_t>(), buf(i, B_HOLES).as<uint32_t>(), nt, buf(i, B_SCRATCH).as<uint32_t>(), d_tot2);
-            HIPLOC(c, hipMemcpyAsync(&n_keep, d_tot, 4, hipMemcpyDeviceToHost, s));
-            HIPLOC(c, hipMemcpyAsync(&n_children, d_tot2, 4, hipMemcpyDeviceToHost, s));
-            HIPLOC(c, hipStreamSynchronize(s));
-            if (n_keep != n_own) local_rc = c->fail(SPH_ERR_DEVICE, "owned-particle count mismatch");
+            HIPCHK(c, hipMemcpyAsync(&n_keep, d_tot, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(&n_children, d_tot2, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (n_keep != n_own) r = c->fail(SPH_ERR_DEVICE, "owned-particle count mismatch");
             else if ((uint64_t)n_own + n_children > c->cap)
-                local_rc = c->fail(SPH_ERR_CAPACITY, "splitting needs %llu particles on rank %d, capacity %llu", (unsigned long long)n_own + n_children, c->dist.rank, (unsigned long long)c->cap);
+                r = c->fail(SPH_ERR_CAPACITY, "splitting needs %llu particles on rank %d, capacity %llu", (unsigned long long)n_own + n_children, c->dist.rank, (unsigned long long)c->cap);
             else
                 hipLaunchKernelGGL(k_slab_split_apply, grid, blk, 0, s, nt, n_own, n_global, buf(i, B_KEEP).as<uint32_t>(), buf(i, B_POS).as<uint32_t>(), buf(i, B_EXTRA).as<uint32_t>(),
                                    buf(i, B_HOLES).as<uint32_t>(), buf(i, B_BEFORE).as<uint32_t>(), c->split_patterns.as<float2>(), p->rest_density, slab_gather_of(c));
         }
-        HIPLOC(c, hipStreamSynchronize(s));
-        if (!local_rc) slab_after_regather(c, n_own + n_children);
-    }
-    return agree(G, local_rc);
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!r) slab_after_regather(c, n_own + n_children);
+        return r;
+    });
 }
 
 static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd)
 {
-    HIPCHK(c, hipSetDevice(c->device));
-    Group G;
-    G.m.push_back(c);
-    int rc = comm_for_rank(c, &G.comm);
-    if (rc) return rc;
-    if (!G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes sph_group_adapt");
-    bool alike = false;
-    rc = slab_adapt(G, op, p, ap, partner, counter, cd, &alike);
-    if (rc && !alike) comm_abandon(c);
-    return rc;
+    return rank_entry(c, "sph_group_adapt", [&](Group& G, bool* together) -> int { return slab_adapt(G, op, p, ap, partner, counter, cd, together); });
 }
 
 // share (op 0) / merge (1) / split (2) for the k contexts of ONE process that sph_group_step steps as ranks 0 .. k-1
 extern "C" int sph_group_adapt(sph_ctx** ctxs, int n, int op, const sph_params* p, const sph_adapt_params* ap, const uint32_t* merge_partner,
                                const uint16_t* merge_counter)
 {
-    if (!ctxs || n <= 0 || !p || !ap || op < 0 || op > 2) return SPH_ERR_INVALID_ARGUMENT;
+    if (!p || !ap || op < 0 || op > 2) return SPH_ERR_INVALID_ARGUMENT;
     Group G;
-    for (int i = 0; i < n; i++) {
-        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
-        if (!ctxs[i]->dist.on || ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
-            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
-        G.m.push_back(ctxs[i]);
-    }
-    G.comm = comm_loopback();
+    if (int rc = group_entry(G, ctxs, n)) return rc;
     return slab_adapt(G, op, p, ap, merge_partner, merge_counter);
 }
 
@@ -1002,12 +940,7 @@ static int slab_compact_check(sph_ctx* c, const char* what, const sph_params* p,
     if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params and ap must be given", what);
     if (k >= 0xfffffff0ull) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: k=%llu", what, (unsigned long long)k);
     if (k && (!ids || !partner_c || !counter_c)) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: ids, partner_c and counter_c must be given", what);
-    for (uint64_t i = 0; i < k; i++) {
-        if (i && ids[i] <= ids[i - 1]) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: ids is not strictly ascending (entry %llu: %u after %u)", what, (unsigned long long)i, ids[i], ids[i - 1]);
-        if (partner_c[i] >= k && partner_c[i] != SPH_MERGE_PARTNER_AVAILABLE && partner_c[i] != SPH_MERGE_PARTNER_DELETE)
-            return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: partner_c holds an id outside the problem (compact id %llu: %u)", what, (unsigned long long)i, partner_c[i]);
-    }
-    return SPH_OK;
+    return prob_check_decisions(c, what, k, ids, partner_c);
 }
 
 static int slab_apply_compact_rank(sph_ctx* c, int op, const char* what, const sph_params* p, const sph_adapt_params* ap, uint64_t k, const uint32_t* ids,
@@ -1040,17 +973,13 @@ extern "C" int sph_group_adapt_compact(sph_ctx** ctxs, int n, int op, const sph_
     for (int i = 0; i < n; i++)
         if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
     if (op != 0 && op != 1) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_adapt_compact: op %d is neither 0 (share) nor 1 (merge)", op);
-    Group G;
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++)
         if (!ctxs[i]->dist.on) return ctxs[i]->fail(SPH_ERR_UNSUPPORTED, "sph_group_adapt_compact: context %d is not a slab context", i);
-        if (ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
-            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
-        G.m.push_back(ctxs[i]);
-    }
+    Group G;
+    if (int rc = group_entry(G, ctxs, n)) return rc;
     for (auto c : G.m)
         if (c->poisoned) return c->refuse_poisoned();
     if (int rc = slab_compact_check(ctxs[0], "sph_group_adapt_compact", p, ap, k, ids, partner_c, counter_c)) return rc;
-    G.comm = comm_loopback();
     const SlabCompact cd{k, ids, partner_c, counter_c};
     return slab_adapt(G, op, p, ap, nullptr, nullptr, &cd);
 }

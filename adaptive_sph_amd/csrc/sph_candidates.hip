@@ -44,23 +44,17 @@ __global__ __launch_bounds__(256) void k_cand_rows(uint32_t n, CandP q, const ui
     if (i >= n) return;
     uint32_t c = 0;
     if (cls[i] == q.donor_class) {
-        const float4 Ai = rec[i];
-        const uint32_t b = off[i];
-        const uint64_t e = min((uint64_t)off[i + 1], tot);
         uint32_t w = 0, w_end = 0;
         if (FILL) {
             w = out_off[i];
             w_end = out_off[i + 1];
         }
-        for (uint64_t p = b; p < e; p++) {
-            const uint32_t j = idx[p];
-            if (j == i || j >= n) continue;
-            if (!cand_pass(q, Ai, j, rec, cls)) continue;
+        cand_walk_row(q, i, i, n, rec[i], off, idx, tot, rec, cls, [&](uint32_t j) {
             if (FILL) {
                 if (w < w_end) out_idx[w] = j;
                 w++;
             } else c++;
-        }
+        });
     }
     if (!FILL) cnt[i] = c;
 }
@@ -70,6 +64,13 @@ int cand_refuse_common(sph_ctx* c, const char* what)
     if (c->poisoned) return c->refuse_poisoned();
     if (c->dist.on)
         return c->fail(SPH_ERR_UNSUPPORTED, "%s: a slab context holds a slab of the particles (assemble the full lists: sph_download_neighbors per rank)", what);
+    return SPH_OK;
+}
+
+int cand_check_args(sph_ctx* c, const char* what, int kind, const sph_params* p, const sph_adapt_params* ap)
+{
+    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params and ap must be given", what);
+    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: kind %d is neither 0 (share) nor 1 (merge)", what, kind);
     return SPH_OK;
 }
 
@@ -133,8 +134,7 @@ extern "C" int sph_download_partner_candidates(sph_ctx* c, int kind, const sph_p
 {
     if (!c) return SPH_ERR_INVALID_ARGUMENT;
     if (n_indices) *n_indices = 0;
-    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_candidates: params and ap must be given");
-    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_download_partner_candidates: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    if (int rc = cand_check_args(c, "sph_download_partner_candidates", kind, p, ap)) return rc;
     if (int rc = cand_refuse_common(c, "sph_download_partner_candidates")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = cand_need_lists(c)) return rc;

@@ -1,5 +1,6 @@
-// The candidate rows on the device, shared by sph_candidates.hip (which hands them to the host as they are) and
-// sph_partner_problem.hip (which renumbers their participants): one definition of the rows, two exports.
+// The candidate rows on the device and the plumbing of the partner problems made from them, shared by sph_candidates.hip (which hands
+// the rows to the host as they are), sph_partner_problem.hip (which renumbers their participants), sph_partner_search.hip and the slab
+// forms of the first two: one definition of the tests, of the row walk, of the packed arrays and of the way decisions come back.
 #pragma once
 
 #include "sph_context.hpp"
@@ -13,6 +14,8 @@ struct CandP {
     int allow_size_diff;   // allow_merge_on_size_difference
 };
 CandP cand_params(int kind, const sph_adapt_params* ap);
+// what every entry point that takes a search's `kind` and parameters refuses first: SPH_ERR_INVALID_ARGUMENT
+int cand_check_args(sph_ctx* c, const char* what, int kind, const sph_params* p, const sph_adapt_params* ap);
 
 // particle_sharing.rs:50-67 / particle_merging.rs:57-78 for the pair (i, j): true = j stays in row i.  rec / cls: the {x, y, mass, h2}
 // records and class bytes in the index space of j (host order in sph_candidates.hip, slots in sph_slab_candidates.hip).
@@ -30,6 +33,23 @@ __device__ __forceinline__ bool cand_pass(const CandP& q, const float4 Ai, uint3
     return !(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) > __fmul_rn(max_dist, max_dist));
 }
 
+// The walk of ONE donor's row r of the step's lists (off / idx, `tot` entries in all; the entries live in [0, n): host indices or
+// slots): the row ends at min(off[r + 1], tot), the donor itself (`self`) and an entry outside the index space are skipped, and
+// survivor(j) is called, in list order, for every j that passes cand_pass against the donor's record Ai.  Counting, filling and
+// marking differ only in what they do with a survivor.
+template <class F>
+__device__ __forceinline__ void cand_walk_row(const CandP& q, uint32_t r, uint32_t self, uint32_t n, const float4 Ai, const uint32_t* __restrict__ off,
+                                              const uint32_t* __restrict__ idx, uint64_t tot, const float4* __restrict__ rec, const uint8_t* __restrict__ cls,
+                                              F&& survivor)
+{
+    const uint64_t e = min((uint64_t)off[r + 1], tot);
+    for (uint64_t p = off[r]; p < e; p++) {
+        const uint32_t j = idx[p];
+        if (j == self || j >= n) continue;
+        if (cand_pass(q, Ai, j, rec, cls)) survivor(j);
+    }
+}
+
 // poisoned -> SPH_ERR_POISONED, a slab context -> SPH_ERR_UNSUPPORTED
 int cand_refuse_common(sph_ctx* c, const char* what);
 // the CSR of the last step's lists on the device (export_valid), built here if neither export has built it yet
@@ -43,8 +63,37 @@ int cand_fill_rows(sph_ctx* c, const CandP& q, uint32_t tot);
 // Synchronises the stream.
 int cand_sum_mass(sph_ctx* c, uint32_t n, const uint8_t* owned, double* total);
 
-// sph_partner_problem.hip, shared with sph_partner_search.hip.  prob_build_on_device: the compact problem of `kind` into prob_ids ..
-// prob_idx without a bulk copy (lists present: cand_need_lists came first); `caps` (may be null): the host buffers a download was given.
+// ---- sph_partner_problem.hip: the compact problem's plumbing, for the plain and the slab problem alike --------------------------------
+// what a pack kernel writes through: the arrays of a ProbBufs (sph_context.hpp)
+struct ProbOut {
+    uint32_t* ids;
+    uint8_t* cls;
+    float* mass;
+    float* level;
+    float2* pos;
+    float* h2;
+    uint32_t* off;
+};
+// room for K participants and n_off + 1 offsets in b; *o: its arrays
+int prob_out(sph_ctx* c, ProbBufs& b, size_t K, size_t n_off, ProbOut* o);
+// the download of a packed problem: whatever host pointer was given is filled -- K entries each, n_off + 1 offsets, the `tot` entries of
+// d_indices -- and the stream is synchronised; K == 0: offsets[0] = 0 and no copy
+int prob_download(sph_ctx* c, const ProbBufs& b, size_t K, size_t n_off, uint64_t tot, const void* d_indices, uint32_t* ids, uint8_t* size_class, float* mass,
+                  float* level, float* position, float* h2, uint32_t* offsets, uint32_t* indices);
+// the host check of K compact decisions, before anything is launched (a bad id must not leave some receivers and donors already modified):
+// a partner is a compact id < K or one of the two sentinels; ids (may be null: the problem's own, on the device) strictly ascending
+int prob_check_decisions(sph_ctx* c, const char* what, uint64_t K, const uint32_t* ids, const uint32_t* partner_c);
+// K decisions in compact ids -> merge_partner / merge_counter of the WHOLE vector (n entries) in d_partner / d_counter: AVAILABLE / 0
+// everywhere, then one thread per compact id scatters its pair, the partner mapped through ids (k_prob_expand).  ids / partner_c /
+// counter_c are device arrays, except where ExpandStage names a buffer: then that one is the host's and is staged there first.  `scope`:
+// the ProfScope all of it runs in.  Queued on the context's stream.
+struct ExpandStage {
+    DevBuf *ids, *partner_c, *counter_c;
+};
+int prob_expand(sph_ctx* c, const char* scope, uint32_t n, uint32_t K, const uint32_t* ids, const uint32_t* partner_c, const uint16_t* counter_c, uint32_t* d_partner,
+                uint16_t* d_counter, ExpandStage stage = {nullptr, nullptr, nullptr});
+// prob_build_on_device: the compact problem of `kind` into prob .. prob_idx without a bulk copy (lists present: cand_need_lists came
+// first); `caps` (may be null): the host buffers a download was given.
 struct ProbCaps {
     bool participants_given;
     uint64_t participants;
@@ -54,13 +103,14 @@ struct ProbCaps {
 int prob_build_on_device(sph_ctx* c, int kind, const sph_adapt_params* ap, const char* what, const ProbCaps* caps, uint32_t* K, uint32_t* tot);
 // the problem just built becomes THE OPEN PROBLEM of the context
 void prob_open_problem(sph_ctx* c, int kind, uint32_t K);
-// queues k_prob_expand: K decisions in compact ids -> merge_partner / merge_counter of the whole vector (pre-filled with AVAILABLE / 0)
-void prob_expand_launch(sph_ctx* c, uint32_t K, const uint32_t* d_partner_c, const uint16_t* d_counter_c, uint32_t* d_partner, uint16_t* d_counter);
+// the open problem is consumed: its prob_k decisions -- the host's (on_host: staged here) or the open solution's on the device -- are
+// expanded over the vector and applied (transfer_on_device).  What sph_*_particles_compact and sph_*_particles_device share.
+int prob_apply(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, int merging, const uint32_t* partner_c, const uint16_t* counter_c, bool on_host);
 
 // sph_slab_candidates.hip, shared with sph_slab_partner_problem.hip.  slab_cand_refuse: a plain context -> SPH_ERR_UNSUPPORTED, a poisoned
-// one -> SPH_ERR_POISONED.  slab_cand_prepare: the collective prepare of sph_slab_candidates.h for the members of G; *together: the status
-// came out of an agree() -- every rank leaves with it, the transport stays usable.  slab_cand_mark_launch: the walk of the rows prepared
-// last once more, setting flag[slot] (owned slots) / flag[n_tot + slot] (ghost slots) of every donor with a candidate and every candidate.
+// one -> SPH_ERR_POISONED.  slab_cand_prepare: the collective prepare of sph_slab_candidates.h for the members of G; *together: as
+// rank_entry (sph_dist.hpp) reads it.  slab_cand_mark_launch: the walk of the rows prepared last once more, setting flag[slot] (owned
+// slots) / flag[n_tot + slot] (ghost slots) of every donor with a candidate and every candidate.
 struct Group;
 int slab_cand_refuse(sph_ctx* c, const char* what);
 int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together);

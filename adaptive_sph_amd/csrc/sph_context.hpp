@@ -90,6 +90,13 @@ struct Options {
 };
 Options options_from_env();   // sph_api.hip
 
+// The packed arrays of a compact partner problem, one entry per participant (off: one per participant with a row, and the total): what
+// the pack kernels write (ProbOut, sph_candidates.hpp) and prob_download copies.  The plain problem and the slab problem of a context
+// are two of these: they are opened and dropped by different rows of sph_carry.hpp.
+struct ProbBufs {
+    DevBuf ids, cls, mass, level, pos, h2, off;
+};
+
 struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its validity flags and what each entry point drops of them)
     int device = 0;
     Options opt;
@@ -115,17 +122,18 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     uint64_t export_tot = 0;
     DevBuf cand_rec, cand_cls, cand_cnt, cand_off, cand_idx, cand_scan, cand_red;   // host-order records / classes, counts, offsets, indices, scan and reduction scratch
     std::array<DevBuf*, 8> export_bufs() { return {&export_d_off, &export_d_idx, &cand_rec, &cand_cls, &cand_cnt, &cand_off, &cand_idx, &cand_scan}; }   // (released by sph_upload)
-    // sph_partner_problem.hip: the compact partner problem.  prob_ids[prob_k] (host indices, ascending) and prob_kind are the OPEN
+    // sph_partner_problem.hip: the compact partner problem.  prob.ids[prob_k] (host indices, ascending) and prob_kind are the OPEN
     // problem (prob_open: opened with export_valid, closed by whatever drops the export).
     int prob_kind = 0;
     uint32_t prob_k = 0;
-    DevBuf prob_flag, prob_rank, prob_lvl, prob_ids, prob_cls, prob_mass, prob_level, prob_pos, prob_h2, prob_off, prob_idx;
+    ProbBufs prob;
+    DevBuf prob_flag, prob_rank, prob_lvl, prob_idx;
     // sph_partner_search.hip: the decisions taken on the device for the open problem (compact ids), THE OPEN SOLUTION while the problem
     // it belongs to is open (prob_open && sol_serial == prob_serial: prob_serial counts the problems opened), and the search's work
     // arrays -- the writers CSR, head positions, donor states, dedupe stamps, the round lists and the progress record.
     uint64_t prob_serial = 0, sol_serial = 0;
     DevBuf sol_partner, sol_counter, ps_w, ps_words, ps_state, ps_rec;
-    std::array<DevBuf*, 17> prob_bufs() { return {&prob_flag, &prob_rank, &prob_lvl, &prob_ids, &prob_cls, &prob_mass, &prob_level, &prob_pos, &prob_h2, &prob_off, &prob_idx,
+    std::array<DevBuf*, 17> prob_bufs() { return {&prob_flag, &prob_rank, &prob_lvl, &prob.ids, &prob.cls, &prob.mass, &prob.level, &prob.pos, &prob.h2, &prob.off, &prob_idx,
                                                   &sol_partner, &sol_counter, &ps_w, &ps_words, &ps_state, &ps_rec}; }
     // sph_slab_candidates.hip: the same rows on a SLAB context, which the exports above refuse.  slab_off / slab_idx hold the CSR of the
     // last step's lists over the OWNED rows (the order of sph_download(SPH_F_PARTICLE_ID)) with SLOT indices as entries, slab_row_slot
@@ -137,12 +145,13 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     uint64_t slab_lists_tot = 0, slab_rows_tot = 0;
     DevBuf slab_row_slot, slab_slot_row, slab_off, slab_idx;   // (slab_slot_row: the row of every slot, 0xffffffff for a ghost)
     // sph_slab_partner_problem.hip: the rank's local partner problem packed from those rows (slab_prob_open; slab_prob_k participants, the
-    // first slab_prob_ko of them owned): a flag and a rank word per slot, twice (owned slots, then ghost slots), and the packed arrays.
-    // The entries stay in cand_idx.
+    // first slab_prob_ko of them owned): a flag and a rank word per slot, twice (owned slots, then ghost slots), and the packed arrays
+    // (slab_prob).  The entries stay in cand_idx.
     uint32_t slab_prob_k = 0, slab_prob_ko = 0;
-    DevBuf slab_prob_flag, slab_prob_rank, slab_prob_ids, slab_prob_cls, slab_prob_mass, slab_prob_level, slab_prob_pos, slab_prob_h2, slab_prob_off;
-    std::array<DevBuf*, 13> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob_ids, &slab_prob_cls,
-                                                  &slab_prob_mass, &slab_prob_level, &slab_prob_pos, &slab_prob_h2, &slab_prob_off}; }
+    ProbBufs slab_prob;
+    DevBuf slab_prob_flag, slab_prob_rank;
+    std::array<DevBuf*, 13> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob.ids, &slab_prob.cls,
+                                                  &slab_prob.mass, &slab_prob.level, &slab_prob.pos, &slab_prob.h2, &slab_prob.off}; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];

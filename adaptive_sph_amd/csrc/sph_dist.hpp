@@ -1,5 +1,7 @@
 // What the step driver (sph_step.hip) and the transports between ranks (sph_transport.hip) share: the transport interface, the
-// group of contexts a step is driven for, and the few wait / staging helpers both sides use.
+// group of contexts a step is driven for, and the few wait / staging helpers both sides use.  Also THE COLLECTIVE RULE of everything that
+// works on the members of a group -- each_member, rank_entry, group_entry, below -- which the step's entry points, the slab apply
+// (sph_adapt.hip) and the slab prepares (sph_slab_candidates.hip, sph_slab_partner_problem.hip) go through.
 #pragma once
 
 #include <cstdint>
@@ -124,6 +126,57 @@ int agree(Group& G, int local_rc);
 enum { SYNC_AGREE = 0, SYNC_DEFER = 1, SYNC_FINAL = 2 };
 int sync_ctrl(Group& G, int mode = SYNC_AGREE);
 void dbg_sync(sph_ctx* c, const char* what, int id = 0);   // SPH_DEBUG_SYNC: synchronise and name the phase just queued
+
+// ---- THE COLLECTIVE RULE of everything that works on the members of a group between two steps (slab_adapt, slab_cand_prepare,
+// slab_prob_prepare), stated here and nowhere else.  Under a per-rank transport every rank runs the same sequence of collectives; a rank
+// that returned in front of one would leave the others waiting in it for ever.  So the work on the members is the body of each_member:
+// whatever fails in there -- HIPCHK, `return c->fail(...)`: they leave the lambda, not the collective -- becomes this rank's status, ends
+// the loop and is handed to agree(), which ends the call on every rank together.  body(i, c) -> int runs with c's device current.
+template <class Body>
+int each_member(Group& G, Body&& body)
+{
+    int local_rc = SPH_OK;
+    for (size_t i = 0; i < G.m.size() && !local_rc; i++) {
+        sph_ctx* c = G.m[i];
+        const hipError_t e = hipSetDevice(c->device);
+        local_rc = e != hipSuccess ? c->fail(SPH_ERR_DEVICE, "hipSetDevice(c->device) failed: %s", hipGetErrorString(e)) : body(i, c);
+    }
+    return agree(G, local_rc);
+}
+// A RANK ENTRY: body(G, &together) -> int for the one context of this rank over its own transport.  `together` (false on entry) is set
+// by the body while its status comes out of a collective, or is a refusal every rank takes alike between two collectives: every rank
+// then leaves with a failure and the transport stays usable.  Any other failure abandons the transport -- the other ranks' next
+// collective reports that instead of waiting (thread / shared-memory transports).  group_entry_name: the entry point a member of a
+// loopback group (no transport of its own) is sent to; nullptr where such a context is served as it is (sph_step: a plain context).
+template <class Body>
+int rank_entry(sph_ctx* c, const char* group_entry_name, Body&& body)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    Group G;
+    G.m.push_back(c);
+    if (int rc = comm_for_rank(c, &G.comm)) return rc;
+    if (group_entry_name && !G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes %s", group_entry_name);
+    bool together = false;
+    const int rc = body(G, &together);
+    if (rc && !together) comm_abandon(c);
+    return rc;
+}
+// A GROUP ENTRY: ctxs[0 .. n) of ONE process, context i configured as rank i of n, on the loopback transport.  (An entry point that
+// answers a plain context with another status than this one's does so before it calls.)
+inline int group_entry(Group& G, sph_ctx** ctxs, int n)
+{
+    if (!ctxs || n <= 0) return SPH_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n; i++) {
+        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
+        if (!ctxs[i]->dist.on || ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
+            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
+        G.m.push_back(ctxs[i]);
+    }
+    G.comm = comm_loopback();
+    return SPH_OK;
+}
+// (sph_adapt.hip) the ghosts hold what their owners hold NOW (stale behind a share): the records, the velocities if asked for, the level
+int refresh_ghost_state(Group& G, bool with_velocity);
 // the arrays a reorder of the context's state moves: records pm_in -> pm_out, cells to `cxy`, everything else from the buffers of c->cur
 // to the other ones (the caller flips c->cur); `lam`: also this step's lambda sums into lam_prev (FromDistribution* reads them next step)
 ReorderIO reorder_io(sph_ctx* c, const float4* pm_in, float4* pm_out, uint32_t* cxy, bool lam);

@@ -442,7 +442,7 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
     if (info) *info = sph_partner_search_info{};
     c->prob_open = false;   // (this call replaces the open problem, or closes it)
     if (!p || !ap || !info) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params, ap and info must be given", what);
-    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: kind %d is neither 0 (share) nor 1 (merge)", what, kind);
+    if (int rc = cand_check_args(c, what, kind, p, ap)) return rc;
     if (int rc = cand_refuse_common(c, what)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = cand_need_lists(c)) return rc;
@@ -469,7 +469,7 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
     PsRec* rec = c->ps_rec.as<PsRec>();
     PsP P{};
     P.K = K;
-    P.off = c->prob_off.as<uint32_t>();
+    P.off = c->prob.off.as<uint32_t>();
     P.idx = c->prob_idx.as<uint32_t>();
     P.tot = tot;
     P.woff = woff;
@@ -478,8 +478,8 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
     P.state = c->ps_state.as<uint8_t>();
     P.partner = c->sol_partner.as<uint32_t>();
     P.counter = c->sol_counter.as<uint16_t>();
-    P.mass = c->prob_mass.as<float>();
-    P.level = c->prob_level.as<float>();
+    P.mass = c->prob.mass.as<float>();
+    P.level = c->prob.level.as<float>();
     P.stamp_x = stamp_x;
     P.stamp_d = stamp_d;
     P.share = kind == 0;
@@ -531,7 +531,7 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
     PsRec r{};
     if (!prog[3]) {
         ProfScope ps(&c->prof, "search_validate", s);
-        hipLaunchKernelGGL(k_ps_validate, gk, blk, 0, s, P, (const uint8_t*)c->prob_cls.as<uint8_t>(), kind == 0 ? 3u : 0u, rec);
+        hipLaunchKernelGGL(k_ps_validate, gk, blk, 0, s, P, (const uint8_t*)c->prob.cls.as<uint8_t>(), kind == 0 ? 3u : 0u, rec);
         HIPCHK(c, hipMemcpyAsync(&r, rec, sizeof r, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         prog[3] = r.error;
@@ -559,11 +559,9 @@ extern "C" int sph_download_partner_decisions(sph_ctx* c, uint64_t k, uint32_t* 
     if (k != c->prob_k) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: k=%llu, the open solution has %u participants", what, (unsigned long long)k, c->prob_k);
     if (k == 0) return SPH_OK;
     hipStream_t s = c->stream;
-    if (ids) HIPCHK(c, hipMemcpyAsync(ids, c->prob_ids.p, (size_t)k * 4, hipMemcpyDeviceToHost, s));
     if (partner_c) HIPCHK(c, hipMemcpyAsync(partner_c, c->sol_partner.p, (size_t)k * 4, hipMemcpyDeviceToHost, s));
     if (counter_c) HIPCHK(c, hipMemcpyAsync(counter_c, c->sol_counter.p, (size_t)k * 2, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return SPH_OK;
+    return prob_download(c, c->prob, (size_t)k, 0, 0, nullptr, ids, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);   // (ids; it waits for all three)
 }
 
 static int apply_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap, int merging)
@@ -575,20 +573,7 @@ static int apply_device(sph_ctx* c, const sph_params* p, const sph_adapt_params*
     if (!solution_open(c))
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: no open solution (sph_find_partners_device comes first; a step, an upload, an edit, a merge, a split or a later problem closes it)", what);
     if (c->prob_kind != merging) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: the open solution is of kind %d", what, c->prob_kind);
-    c->prob_open = false;   // consumed, and the solution with it
-    const uint32_t n = (uint32_t)c->n, K = c->prob_k;
-    if (merging) c->drop(DROPS_EXPORT_EARLY);   // (as sph_merge_particles: the lists index the vector before the deletions)
-    if (n == 0) return SPH_OK;
-    hipStream_t s = c->stream;
-    TmpBuf d_partner, d_counter;
-    if (d_partner.ensure((size_t)n * 4) != hipSuccess || d_counter.ensure((size_t)n * 2) != hipSuccess) return c->fail(SPH_ERR_DEVICE, "out of device memory");
-    {
-        ProfScope ps(&c->prof, "problem_expand", s);
-        HIPCHK(c, hipMemsetAsync(d_partner.p, 0xff, (size_t)n * 4, s));   // SPH_MERGE_PARTNER_AVAILABLE
-        HIPCHK(c, hipMemsetAsync(d_counter.p, 0, (size_t)n * 2, s));
-        if (K) prob_expand_launch(c, K, c->sol_partner.as<uint32_t>(), c->sol_counter.as<uint16_t>(), d_partner.as<uint32_t>(), d_counter.as<uint16_t>());
-    }
-    return transfer_on_device(c, p, ap, d_partner.as<uint32_t>(), d_counter.as<uint16_t>(), merging);
+    return prob_apply(c, p, ap, merging, c->sol_partner.as<uint32_t>(), c->sol_counter.as<uint16_t>(), false);
 }
 
 extern "C" int sph_share_particles_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* ap) { return apply_device(c, p, ap, 0); }

@@ -16,8 +16,8 @@
 // The records are read in slot space (pm[pcur]): no gather into another order.  Only the two totals cross the bus before
 // sph_slab_candidates_download.  Arithmetic: cand_pass (sph_candidates.hpp), the one definition of the two tests.
 //
-// Collective pattern of slab_adapt (sph_adapt.hip): a failure inside a per-member loop becomes this rank's local_rc and reaches the
-// agree() that follows, so no rank waits in a collective for one that left.
+// The work on the members is the body of each_member, the entry points go through rank_entry / group_entry: the collective rule is
+// stated there (sph_dist.hpp).
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -62,18 +62,12 @@ __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_
     if (row_cls[r] == q.donor_class) {
         const uint32_t s = row_slot[r];
         if (s < nt) {
-            const float4 Ai = pm[s];
-            const uint32_t b = off[r];
-            const uint64_t e = min((uint64_t)off[r + 1], tot);
             uint32_t w = 0, w_end = 0;
             if (MODE == ROWS_FILL) {
                 w = out_off[r];
                 w_end = out_off[r + 1];
             }
-            for (uint64_t p = b; p < e; p++) {
-                const uint32_t j = idx[p];
-                if (j == s || j >= nt) continue;
-                if (!cand_pass(q, Ai, j, pm, cls)) continue;
+            cand_walk_row(q, r, s, nt, pm[s], off, idx, tot, pm, cls, [&](uint32_t j) {
                 if (MODE == ROWS_FILL) {
                     if (w < w_end) out_idx[w] = orig[j];
                     w++;
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256) void k_slab_cand_rows(uint32_t n_rows, uint32_
                     flag[slot_row[j] == 0xffffffffu ? nt + j : j] = 1u;
                     c++;
                 } else c++;
-            }
+            });
             if (MODE == ROWS_MARK && c) flag[s] = 1u;
         }
     }
@@ -95,23 +89,10 @@ int slab_cand_refuse(sph_ctx* c, const char* what)
     return SPH_OK;
 }
 
-static float* sel_cand_pm(Member& m) { return m.lv_pmnew; }
-static float* sel_cand_lvl(Member& m) { return m.lv_level; }
-
-#define HIPLOC(ctx, call)                                                                                            \
-    {                                                                                                                \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) {                                                                                      \
-            local_rc = (ctx)->fail(SPH_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));                   \
-            break;                                                                                                   \
-        }                                                                                                            \
-    }
-
-// *together: the status came out of an agree() -- every rank leaves with a failure, the transport stays usable
+// *together: as rank_entry reads it (sph_dist.hpp)
 int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together)
 {
-    const size_t nm = G.m.size();
-    int rc = SPH_OK, local_rc = SPH_OK;
+    int rc = SPH_OK;
     // (as slab_adapt: a poisoned member ends the call before any collective -- the step that poisoned it failed on every rank, and on a
     //  per-rank transport it abandoned the group, whose collectives report that instead of waiting)
     for (auto c : G.m)
@@ -120,50 +101,34 @@ int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_p
             return slab_cand_refuse(c, "sph_slab_candidates_prepare");
         }
     // ---- lists: the CSR of the step's lists, built once per step
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        c->slab_rows_open = c->slab_prob_open = false;   // (a slab context, not poisoned: both entry points and the loop above have seen to it)
-        if (!c->have_flags) {
-            local_rc = c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare follows a step (it filters that step's lists and reads the neighbours across a cut from its ghost layer)");
-            break;
-        }
-        HIPLOC(c, hipSetDevice(c->device));
-        if (c->slab_lists_valid && c->slab_lists_rows == (uint32_t)c->n) continue;
-        if (!c->grid_valid) {
-            local_rc = c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists of the step on the device and nothing to build them from: the first sph_slab_candidates_prepare of a step comes before its share");
-            break;
-        }
-        local_rc = slab_lists_on_device(c);
-    }
     *together = true;
-    if ((rc = agree(G, local_rc))) return rc;
+    rc = each_member(G, [&](size_t, sph_ctx* c) -> int {
+        c->slab_rows_open = c->slab_prob_open = false;   // (a slab context, not poisoned: both entry points and the loop above have seen to it)
+        if (!c->have_flags)
+            return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare follows a step (it filters that step's lists and reads the neighbours across a cut from its ghost layer)");
+        if (c->slab_lists_valid && c->slab_lists_rows == (uint32_t)c->n) return SPH_OK;
+        if (!c->grid_valid)
+            return c->fail(SPH_ERR_INVALID_ARGUMENT, "no neighbour lists of the step on the device and nothing to build them from: the first sph_slab_candidates_prepare of a step comes before its share");
+        return slab_lists_on_device(c);
+    });
+    if (rc) return rc;
     *together = false;
     // ---- the ghosts' records and levels as their owners hold them now
-    std::vector<Member> M(nm);
-    for (size_t i = 0; i < nm; i++) {
-        sph_ctx* c = G.m[i];
-        M[i].c = c;
-        M[i].n = c->dist.n_tot;
-        M[i].lv_pmnew = (float*)c->pm[c->pcur].as<float4>();
-        M[i].lv_level = c->lvl[c->cur].as<float>();
-    }
-    if ((rc = refresh_ghosts(G, M, sel_cand_pm, 4, "pm"))) return rc;
-    if ((rc = refresh_ghosts(G, M, sel_cand_lvl, 1, "level"))) return rc;
+    if ((rc = refresh_ghost_state(G, false))) return rc;
     // ---- classes, count, scan, fill
     const CandP q = cand_params(kind, ap);
     const dim3 blk(256);
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        HIPLOC(c, hipSetDevice(c->device));
+    *together = true;
+    rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
         hipStream_t s = c->stream;
         const uint32_t nt = c->dist.n_tot, n = (uint32_t)c->n;
         const int k = c->cur;
         TmpBuf d_ghost;
-        HIPLOC(c, d_ghost.ensure((size_t)nt + 4));
-        HIPLOC(c, c->cand_cls.ensure((size_t)nt + n + 4));
-        HIPLOC(c, c->cand_cnt.ensure((size_t)n * 4 + 4));
-        HIPLOC(c, c->cand_off.ensure(((size_t)n + 1) * 4));
-        HIPLOC(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+        HIPCHK(c, d_ghost.ensure((size_t)nt + 4));
+        HIPCHK(c, c->cand_cls.ensure((size_t)nt + n + 4));
+        HIPCHK(c, c->cand_cnt.ensure((size_t)n * 4 + 4));
+        HIPCHK(c, c->cand_off.ensure(((size_t)n + 1) * 4));
+        HIPCHK(c, c->cand_scan.ensure(((size_t)n / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
         uint8_t* cls = c->cand_cls.as<uint8_t>();
         uint8_t* row_cls = cls + nt;
         uint32_t* out_off = c->cand_off.as<uint32_t>();
@@ -184,15 +149,14 @@ int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_p
         }
         uint32_t tot = 0;
         DeviceStatus st{};
-        HIPLOC(c, hipMemcpyAsync(&tot, out_off + n, 4, hipMemcpyDeviceToHost, s));
-        HIPLOC(c, hipMemcpyAsync(&st, c->status.p, sizeof st, hipMemcpyDeviceToHost, s));
-        HIPLOC(c, hipStreamSynchronize(s));   // (d_ghost goes with this scope)
+        HIPCHK(c, hipMemcpyAsync(&tot, out_off + n, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&st, c->status.p, sizeof st, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));   // (d_ghost goes with this scope)
         if (st.error) {   // a ghost without a level value: LevelEstimationState::level of FluidInterior, as sph_classify reports it for an owned one
             (void)hipMemsetAsync(c->status.p, 0, sizeof(DeviceStatus), s);
-            local_rc = c->fail((int)st.error, "sph_slab_candidates_prepare: a ghost particle has no level value (particle i=%u)", st.info);
-            break;
+            return c->fail((int)st.error, "sph_slab_candidates_prepare: a ghost particle has no level value (particle i=%u)", st.info);
         }
-        HIPLOC(c, c->cand_idx.ensure((size_t)tot * 4 + 4));
+        HIPCHK(c, c->cand_idx.ensure((size_t)tot * 4 + 4));
         if (n && tot) {
             ProfScope ps(&c->prof, "slab_candidates_fill", s);
             hipLaunchKernelGGL(k_slab_cand_rows<ROWS_FILL>, grid_r, blk, 0, s, n, nt, q, row_cls, c->slab_row_slot.as<uint32_t>(), c->slab_off.as<uint32_t>(),
@@ -204,9 +168,8 @@ int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_p
         c->slab_rows_tot = tot;
         n_rows[i] = n;
         n_indices[i] = tot;
-    }
-    *together = true;
-    rc = agree(G, local_rc);
+        return SPH_OK;
+    });
     if (rc)
         for (auto c : G.m) c->slab_rows_open = false;
     return rc;
@@ -231,18 +194,10 @@ extern "C" int sph_slab_candidates_prepare(sph_ctx* c, int kind, const sph_param
     if (n_rows) *n_rows = 0;
     if (n_indices) *n_indices = 0;
     // (argument refusals are every rank's alike -- the ranks make the same call -- and come before any collective)
-    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare: params and ap must be given");
-    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_candidates_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    if (int rc = cand_check_args(c, "sph_slab_candidates_prepare", kind, p, ap)) return rc;
     if (int rc = slab_cand_refuse(c, "sph_slab_candidates_prepare")) return rc;   // (a plain context; a poisoned one, whatever its transport)
-    HIPCHK(c, hipSetDevice(c->device));
-    Group G;
-    G.m.push_back(c);
-    int rc = comm_for_rank(c, &G.comm);
-    if (rc) return rc;
-    if (!G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes sph_group_slab_candidates_prepare");
-    bool together = false;
-    rc = slab_cand_prepare(G, kind, p, ap, &rows, &tot, &together);
-    if (rc && !together) comm_abandon(c);   // (thread / shared-memory transports: the other ranks' next collective reports it instead of waiting)
+    const int rc = rank_entry(c, "sph_group_slab_candidates_prepare",
+                              [&](Group& G, bool* together) -> int { return slab_cand_prepare(G, kind, p, ap, &rows, &tot, together); });
     if (rc) return rc;
     if (n_rows) *n_rows = rows;
     if (n_indices) *n_indices = tot;
@@ -255,16 +210,11 @@ extern "C" int sph_group_slab_candidates_prepare(sph_ctx** ctxs, int n, int kind
     if (!ctxs || n <= 0) return SPH_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < n; i++)
         if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
-    if (!p || !ap) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_candidates_prepare: params and ap must be given");
-    if (kind != 0 && kind != 1) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_candidates_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
-    Group G;
-    for (int i = 0; i < n; i++) {
+    if (int rc = cand_check_args(ctxs[0], "sph_group_slab_candidates_prepare", kind, p, ap)) return rc;
+    for (int i = 0; i < n; i++)
         if (!ctxs[i]->dist.on) return slab_cand_refuse(ctxs[i], "sph_group_slab_candidates_prepare");
-        if (ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
-            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
-        G.m.push_back(ctxs[i]);
-    }
-    G.comm = comm_loopback();
+    Group G;
+    if (int rc = group_entry(G, ctxs, n)) return rc;
     std::vector<uint64_t> rows((size_t)n, 0), tot((size_t)n, 0);
     bool together = false;
     const int rc = slab_cand_prepare(G, kind, p, ap, rows.data(), tot.data(), &together);

@@ -14,7 +14,8 @@
 //           between two owned participants is empty, so the prepared offsets restricted to them are the local CSR's (as k_prob_pack)
 //
 // The entries stay in cand_idx (global ids).  A few words per slot, coalesced except for the scatter through rank: thread per element,
-// 256-thread blocks, like sph_partner_problem.hip.  Collective pattern: that of slab_cand_prepare (local_rc -> agree).
+// 256-thread blocks, like sph_partner_problem.hip, whose packed arrays and download these are (ProbBufs, prob_out, prob_download).
+// Collective rule: each_member / rank_entry / group_entry (sph_dist.hpp).
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -23,20 +24,10 @@
 #include "sph_candidates.hpp"
 #include "sph_dist.hpp"
 
-struct SlabProbOut {
-    uint32_t* ids;
-    uint8_t* cls;
-    float* mass;
-    float* level;
-    float2* pos;
-    float* h2;
-    uint32_t* off;
-};
-
 __global__ __launch_bounds__(256) void k_slab_prob_pack(uint32_t nt, uint32_t K, uint32_t Ko, uint32_t n_rows, uint32_t tot, const uint32_t* __restrict__ flag,
                                                          const uint32_t* __restrict__ rank, const uint32_t* __restrict__ orig, const uint8_t* __restrict__ cls,
                                                          const float4* __restrict__ pm, const float* __restrict__ lvl, const uint32_t* __restrict__ slot_row,
-                                                         const uint32_t* __restrict__ cand_off, SlabProbOut o)
+                                                         const uint32_t* __restrict__ cand_off, ProbOut o)
 {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= 2u * nt) return;
@@ -59,65 +50,42 @@ __global__ __launch_bounds__(256) void k_slab_prob_pack(uint32_t nt, uint32_t K,
     }
 }
 
-#define HIPLOC(ctx, call)                                                                                            \
-    {                                                                                                                \
-        hipError_t e_ = (call);                                                                                      \
-        if (e_ != hipSuccess) {                                                                                      \
-            local_rc = (ctx)->fail(SPH_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));                   \
-            break;                                                                                                   \
-        }                                                                                                            \
-    }
-
 static int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_part, uint64_t* n_owned, uint64_t* n_indices, bool* together)
 {
     const size_t nm = G.m.size();
     std::vector<uint64_t> rows(nm, 0), tots(nm, 0);
     int rc = slab_cand_prepare(G, kind, p, ap, rows.data(), tots.data(), together);   // (it closes the members' problems first)
     if (rc) return rc;
-    *together = false;
-    int local_rc = SPH_OK;
     const CandP q = cand_params(kind, ap);
-    for (size_t i = 0; i < nm && !local_rc; i++) {
-        sph_ctx* c = G.m[i];
-        HIPLOC(c, hipSetDevice(c->device));
+    rc = each_member(G, [&](size_t i, sph_ctx* c) -> int {
         hipStream_t s = c->stream;
         const uint32_t nt = c->dist.n_tot, n = c->slab_rows_n, tot = (uint32_t)c->slab_rows_tot;
         uint32_t K = 0, Ko = 0;
         if (n && nt && tot) {
             const size_t words = 2 * (size_t)nt;
-            HIPLOC(c, c->slab_prob_flag.ensure(words * 4));
-            HIPLOC(c, c->slab_prob_rank.ensure((words + 1) * 4));
-            HIPLOC(c, c->cand_scan.ensure((words / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+            HIPCHK(c, c->slab_prob_flag.ensure(words * 4));
+            HIPCHK(c, c->slab_prob_rank.ensure((words + 1) * 4));
+            HIPCHK(c, c->cand_scan.ensure((words / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
             uint32_t* rank = c->slab_prob_rank.as<uint32_t>();
             {
                 ProfScope ps(&c->prof, "slab_problem_mark", s);
-                HIPLOC(c, hipMemsetAsync(c->slab_prob_flag.p, 0, words * 4, s));
+                HIPCHK(c, hipMemsetAsync(c->slab_prob_flag.p, 0, words * 4, s));
                 slab_cand_mark_launch(c, q, c->slab_prob_flag.as<uint32_t>());
                 device_exclusive_scan_u32(s, c->slab_prob_flag.as<uint32_t>(), rank, (uint32_t)words, c->cand_scan.as<uint32_t>(), rank + words);
             }
-            HIPLOC(c, hipMemcpyAsync(&Ko, rank + nt, 4, hipMemcpyDeviceToHost, s));
-            HIPLOC(c, hipMemcpyAsync(&K, rank + words, 4, hipMemcpyDeviceToHost, s));
-            HIPLOC(c, hipStreamSynchronize(s));
-            if (K == 0 || Ko == 0 || Ko > K || Ko > n || K > words) {
-                local_rc = c->fail(SPH_ERR_DEVICE, "sph_slab_partner_problem_prepare: %u candidates but %u participants (%u owned) of %u slots", tot, K, Ko, nt);
-                break;
-            }
-            const size_t k = K;
-            HIPLOC(c, c->slab_prob_ids.ensure(k * 4));
-            HIPLOC(c, c->slab_prob_cls.ensure(k));
-            HIPLOC(c, c->slab_prob_mass.ensure(k * 4));
-            HIPLOC(c, c->slab_prob_level.ensure(k * 4));
-            HIPLOC(c, c->slab_prob_pos.ensure(k * 8));
-            HIPLOC(c, c->slab_prob_h2.ensure(k * 4));
-            HIPLOC(c, c->slab_prob_off.ensure(((size_t)Ko + 1) * 4));
+            HIPCHK(c, hipMemcpyAsync(&Ko, rank + nt, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(&K, rank + words, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (K == 0 || Ko == 0 || Ko > K || Ko > n || K > words)
+                return c->fail(SPH_ERR_DEVICE, "sph_slab_partner_problem_prepare: %u candidates but %u participants (%u owned) of %u slots", tot, K, Ko, nt);
+            ProbOut out;
+            if (int rc2 = prob_out(c, c->slab_prob, K, Ko, &out)) return rc2;
             ProfScope ps(&c->prof, "slab_problem_pack", s);
             hipLaunchKernelGGL(k_slab_prob_pack, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, s, nt, K, Ko, n, tot, (const uint32_t*)c->slab_prob_flag.as<uint32_t>(),
                                (const uint32_t*)rank, (const uint32_t*)c->orig[c->cur].as<uint32_t>(), (const uint8_t*)c->cand_cls.as<uint8_t>(),
                                (const float4*)c->pm[c->pcur].as<float4>(), (const float*)c->lvl[c->cur].as<float>(), (const uint32_t*)c->slab_slot_row.as<uint32_t>(),
-                               (const uint32_t*)c->cand_off.as<uint32_t>(),
-                               SlabProbOut{c->slab_prob_ids.as<uint32_t>(), c->slab_prob_cls.as<uint8_t>(), c->slab_prob_mass.as<float>(), c->slab_prob_level.as<float>(),
-                                           c->slab_prob_pos.as<float2>(), c->slab_prob_h2.as<float>(), c->slab_prob_off.as<uint32_t>()});
-            HIPLOC(c, hipStreamSynchronize(s));   // (the snapshot is complete before anybody changes the records it was packed from)
+                               (const uint32_t*)c->cand_off.as<uint32_t>(), out);
+            HIPCHK(c, hipStreamSynchronize(s));   // (the snapshot is complete before anybody changes the records it was packed from)
         }
         c->slab_prob_open = true;
         c->slab_prob_k = K;
@@ -125,9 +93,8 @@ static int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_
         n_part[i] = K;
         n_owned[i] = Ko;
         n_indices[i] = tot;
-    }
-    *together = true;
-    rc = agree(G, local_rc);
+        return SPH_OK;
+    });
     if (rc)
         for (auto c : G.m) c->slab_prob_open = false;   // (the rows of sph_slab_candidates_prepare stay: they are complete)
     return rc;
@@ -142,18 +109,10 @@ extern "C" int sph_slab_partner_problem_prepare(sph_ctx* c, int kind, const sph_
     if (n_owned_participants) *n_owned_participants = 0;
     if (n_indices) *n_indices = 0;
     // (argument refusals are every rank's alike -- the ranks make the same call -- and come before any collective)
-    if (!p || !ap) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_partner_problem_prepare: params and ap must be given");
-    if (kind != 0 && kind != 1) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_partner_problem_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
+    if (int rc = cand_check_args(c, "sph_slab_partner_problem_prepare", kind, p, ap)) return rc;
     if (int rc = slab_cand_refuse(c, "sph_slab_partner_problem_prepare")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    Group G;
-    G.m.push_back(c);
-    int rc = comm_for_rank(c, &G.comm);
-    if (rc) return rc;
-    if (!G.comm) return c->fail(SPH_ERR_INVALID_ARGUMENT, "a slab context of a loopback group takes sph_group_slab_partner_problem_prepare");
-    bool together = false;
-    rc = slab_prob_prepare(G, kind, p, ap, &K, &Ko, &tot, &together);
-    if (rc && !together) comm_abandon(c);   // (as sph_slab_candidates_prepare)
+    const int rc = rank_entry(c, "sph_group_slab_partner_problem_prepare",
+                              [&](Group& G, bool* together) -> int { return slab_prob_prepare(G, kind, p, ap, &K, &Ko, &tot, together); });
     if (rc) return rc;
     if (n_participants) *n_participants = K;
     if (n_owned_participants) *n_owned_participants = Ko;
@@ -172,16 +131,11 @@ extern "C" int sph_group_slab_partner_problem_prepare(sph_ctx** ctxs, int n, int
         if (n_owned_participants) n_owned_participants[i] = 0;
         if (n_indices) n_indices[i] = 0;
     }
-    if (!p || !ap) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_partner_problem_prepare: params and ap must be given");
-    if (kind != 0 && kind != 1) return ctxs[0]->fail(SPH_ERR_INVALID_ARGUMENT, "sph_group_slab_partner_problem_prepare: kind %d is neither 0 (share) nor 1 (merge)", kind);
-    Group G;
-    for (int i = 0; i < n; i++) {
+    if (int rc = cand_check_args(ctxs[0], "sph_group_slab_partner_problem_prepare", kind, p, ap)) return rc;
+    for (int i = 0; i < n; i++)
         if (!ctxs[i]->dist.on) return slab_cand_refuse(ctxs[i], "sph_group_slab_partner_problem_prepare");
-        if (ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n)
-            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
-        G.m.push_back(ctxs[i]);
-    }
-    G.comm = comm_loopback();
+    Group G;
+    if (int rc = group_entry(G, ctxs, n)) return rc;
     std::vector<uint64_t> K((size_t)n, 0), Ko((size_t)n, 0), tot((size_t)n, 0);
     bool together = false;
     const int rc = slab_prob_prepare(G, kind, p, ap, K.data(), Ko.data(), tot.data(), &together);
@@ -214,17 +168,5 @@ extern "C" int sph_slab_partner_problem_download(sph_ctx* c, uint32_t* ids, uint
     if ((ids || size_class || mass || level || position || h2 || offsets) && pcap < K)
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "participant buffers too small (%llu participants prepared)", (unsigned long long)K);
     if (indices && icap < tot) return c->fail(SPH_ERR_INVALID_ARGUMENT, "indices buffer too small (%llu entries prepared)", (unsigned long long)tot);
-    hipStream_t s = c->stream;
-    if (K) {
-        if (ids) HIPCHK(c, hipMemcpyAsync(ids, c->slab_prob_ids.p, K * 4, hipMemcpyDeviceToHost, s));
-        if (size_class) HIPCHK(c, hipMemcpyAsync(size_class, c->slab_prob_cls.p, K, hipMemcpyDeviceToHost, s));
-        if (mass) HIPCHK(c, hipMemcpyAsync(mass, c->slab_prob_mass.p, K * 4, hipMemcpyDeviceToHost, s));
-        if (level) HIPCHK(c, hipMemcpyAsync(level, c->slab_prob_level.p, K * 4, hipMemcpyDeviceToHost, s));
-        if (position) HIPCHK(c, hipMemcpyAsync(position, c->slab_prob_pos.p, K * 8, hipMemcpyDeviceToHost, s));
-        if (h2) HIPCHK(c, hipMemcpyAsync(h2, c->slab_prob_h2.p, K * 4, hipMemcpyDeviceToHost, s));
-        if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, c->slab_prob_off.p, (Ko + 1) * 4, hipMemcpyDeviceToHost, s));
-        if (indices && tot) HIPCHK(c, hipMemcpyAsync(indices, c->cand_idx.p, (size_t)tot * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    } else if (offsets) offsets[0] = 0;
-    return SPH_OK;
+    return prob_download(c, c->slab_prob, K, Ko, tot, c->cand_idx.p, ids, size_class, mass, level, position, h2, offsets, indices);
 }

@@ -1866,15 +1866,11 @@ static int agree_step_inputs(Group& G, const sph_params* p, bool* together)
     return SPH_ERR_INVALID_ARGUMENT;
 }
 
-static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool* refused_together = nullptr)
+// *together: every rank refused the step in the same collective (agree_step_inputs): the transport stays usable
+static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool* together)
 {
-    if (G.multi()) {
-        bool together = false;
-        if (int rc = agree_step_inputs(G, p, &together)) {
-            if (refused_together) *refused_together = together;
-            return rc;
-        }
-    }
+    if (G.multi())
+        if (int rc = agree_step_inputs(G, p, together)) return rc;
     bool started = false;
     for (auto c : G.m) c->drop(DROPS_STEP_START);   // (sph_candidates.hip, sph_slab_candidates.hip: the exported CSR holds the lists of the step before this one)
     const int rc = group_step_inner(G, p, outs, &started);
@@ -1895,15 +1891,8 @@ static int group_step(Group& G, const sph_params* p, sph_step_stats* outs, bool*
 extern "C" int sph_step(sph_ctx* c, const sph_params* p, sph_step_stats* out)
 {
     if (!c || !p) return SPH_ERR_INVALID_ARGUMENT;
-    HIPCHK(c, hipSetDevice(c->device));
-    Group G;
-    G.m.push_back(c);
-    int rc = comm_for_rank(c, &G.comm);
-    if (rc) return rc;
-    bool refused_together = false;   // every rank refused the step in the same collective: the transport stays usable
-    rc = group_step(G, p, out, &refused_together);
-    if (rc && !refused_together) comm_abandon(c);   // (thread / shared-memory transports: the other ranks' next collective reports it instead of waiting)
-    return rc;
+    // (rank_entry, sph_dist.hpp.  No group entry to name: a context without a transport is a plain context here, and is stepped)
+    return rank_entry(c, nullptr, [&](Group& G, bool* together) -> int { return group_step(G, p, out, together); });
 }
 
 // classify_particles (adaptivity/mod.rs:50-59) on the device-resident state: the level field and masses as they stand
@@ -1930,14 +1919,12 @@ extern "C" int sph_group_step(sph_ctx** ctxs, int n, const sph_params* p, sph_st
 {
     if (!ctxs || n <= 0 || !p) return SPH_ERR_INVALID_ARGUMENT;
     Group G;
-    for (int i = 0; i < n; i++) {
-        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
-        if (n > 1 && (!ctxs[i]->dist.on || ctxs[i]->dist.rank != i || ctxs[i]->dist.nranks != n))
-            return ctxs[i]->fail(SPH_ERR_INVALID_ARGUMENT, "context %d is not configured as rank %d of %d (sph_dist_configure)", i, i, n);
-        G.m.push_back(ctxs[i]);
-    }
-    if (n > 1) G.comm = comm_loopback();
-    return group_step(G, p, outs);
+    if (n == 1) {   // a group of one is the plain step: any context, no transport
+        if (!ctxs[0]) return SPH_ERR_INVALID_ARGUMENT;
+        G.m.push_back(ctxs[0]);
+    } else if (int rc = group_entry(G, ctxs, n)) return rc;
+    bool together = false;
+    return group_step(G, p, outs, &together);
 }
 
 extern "C" int sph_dist_configure(sph_ctx* c, int rank, int n_ranks, float cut_lo, float cut_hi)

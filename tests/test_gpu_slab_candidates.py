@@ -1,8 +1,12 @@
 """The candidate export of a slab context (include/sph_slab_candidates.h): the ranks' filtered rows, assembled by global id, against
 the host filter adaptivity.partner_candidates_reference applied to the ranks' own full lists and fields, entry by entry; the on-slab
 adaptive step in export="candidates" mode against the default (same partner arrays after every pass, bit-identical states), on the
-loopback group and with every rank on a thread of its own; sph_slab_sum_mass; the refusals."""
+loopback group and with every rank on a thread of its own; sph_slab_sum_mass; the refusals; a split that one rank has no room for
+ends the apply on every rank within the call."""
+import ctypes as C
+import time
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import nullcontext
 from pathlib import Path
 
 import numpy as np
@@ -359,6 +363,122 @@ def test_same_decisions_same_state(product_lib, monkeypatch, transport):
             for f in reversed(closers):
                 f()
     assert all(v > 0 for v in seen.values()), seen
+
+
+AMPLE = 70000
+
+
+def slab_ranks(lib, scene, cuts, capacities, group=None):
+    """The ranks of `cuts` with split patterns loaded, rank r with room for capacities[r] particles; on the thread transport of `group`
+    or, without one, for the loopback entry points."""
+    pos, mass, vel, planes = scene
+    parts = D.partition(pos[:, 0], cuts)
+    k = len(parts)
+    ctxs = []
+    for r, sel in enumerate(parts):
+        c = ffi.Context(lib, capacities[r], planes)
+        ctxs.append(c)
+        c.dist_configure(r, k, cuts[r], cuts[r + 1])
+        if group is not None:
+            c.comm_init_threads(group, r, k)
+        c.upload(mass[sel], pos[sel], vel[sel])
+        c.upload_field("particle_id", sel.astype(np.uint32))
+        c.set_split_patterns(split_patterns().patterns)
+    return ctxs
+
+
+def split_probe(lib, P, scene, cuts):
+    """A loopback group with ample capacity, stepped and adapted until an adaptive step splits.  -> (that step t, the ranks' owned
+    particles in front of the split, their children, the children's x)."""
+    p = P.to_ffi()
+    grp = slab_ranks(lib, scene, cuts, [AMPLE] * (len(cuts) - 1))
+    try:
+        for t in range(1, 8):
+            sts = ffi.group_step(grp, p)
+            owned = [c.n for c in grp]
+            ghosts = [sum(c.dist_get_stats()["n_ghost"]) for c in grp]
+            info = D.group_single_step_adaptivity_on_slabs(lib, grp, P, float(sts[0].dt), int(sts[0].step_number))
+            if info["splits"]:
+                children = [c.n - o for c, o in zip(grp, owned)]
+                x = np.concatenate([c.download("position")[c.download("particle_id") >= sum(owned), 0] for c in grp])
+                print(f"split probe: cuts {cuts[1:-1]} step {t}: owned {owned} ghosts {ghosts} children {children}")
+                assert len(x) == info["splits"] == sum(children)
+                return t, owned, children, x
+        raise AssertionError("no adaptive step of the first seven splits")
+    finally:
+        close_all(grp)
+
+
+class _RankStatuses(_Threads):
+    """... and what every rank's call returned, and how long the ranks took together, when one of them fails."""
+
+    def all(self, fn):
+        t0 = time.perf_counter()
+        futs = [self.pool.submit(fn, c) for c in self.grp]
+        self.statuses, out, err = [], [], None
+        for f in futs:
+            try:
+                out.append(f.result())
+                self.statuses.append(0)
+            except ffi.SphError as e:
+                self.statuses.append(e.status)
+                err = err or e
+        self.wall = time.perf_counter() - t0
+        if err:
+            raise err
+        return out
+
+
+@pytest.mark.parametrize("transport", ["loopback", "threads"])
+def test_a_split_without_room_on_one_rank_fails_on_every_rank(product_lib, transport):
+    """The collective rule on the adapt path.  Two ranks of the default scene; a probe group with ample capacity tells the adaptive
+    step that splits and rank 1's owned particles and children there (at least one child: the cut moves to the children's median x
+    if the equal-count cut leaves rank 1 none).  The same run with rank 1's capacity one short of owned + children: the split is
+    refused on the host before rank 1's apply kernel is launched -- SPH_ERR_CAPACITY there, and a non-zero status on every rank within
+    the same call, whether the group enters through sph_group_adapt or every rank through sph_split_particles on its own thread
+    (nobody waits in a collective for the rank that left: the wall time is bounded as in
+    test_ranks_on_threads_capacity_failure_is_collective)."""
+    P = default_params()
+    scene = default_scene(P)
+    p = P.to_ffi()
+    k = 2
+    cuts = D.slab_cuts(scene[0][:, 0], k)
+    t, owned, children, x = split_probe(product_lib, P, scene, cuts)
+    if children[1] == 0:
+        cuts = [-D.INF, float(np.median(x)), D.INF]
+        t, owned, children, x = split_probe(product_lib, P, scene, cuts)
+    assert children[1] > 0, (cuts, owned, children)
+    caps = [AMPLE, owned[1] + children[1] - 1]
+    group = C.c_void_p()
+    if transport == "threads":
+        assert product_lib.thread_group_create(k, C.byref(group)) == 0
+    grp = slab_ranks(product_lib, scene, cuts, caps, group if transport == "threads" else None)
+    th = _RankStatuses(grp) if transport == "threads" else None
+    try:
+        for s in range(1, t + 1):
+            sts = th.all(lambda c: c.step(p)) if th else ffi.group_step(grp, p)
+            dt, num = float(sts[0].dt), int(sts[0].step_number)
+            if s == t:
+                assert [c.n for c in grp] == owned
+            with pytest.raises(ffi.SphError) if s == t else nullcontext() as e:
+                if th:
+                    adapt_on_threads(product_lib, th, P, dt, num, "lists", [])
+                else:
+                    D.group_single_step_adaptivity_on_slabs(product_lib, grp, P, dt, num)
+        print(f"split without room [{transport}]: capacities {caps}, status {e.value.status}" + (f", per rank {th.statuses} in {th.wall:.3f} s" if th else "") +
+              f": {e.value}")
+        if th:
+            assert th.wall < 30.0
+            assert th.statuses[1] == 3 and all(st != 0 for st in th.statuses), th.statuses   # SPH_ERR_CAPACITY on rank 1, its status on the other
+        else:
+            assert e.value.status == 3 and "on rank 1" in str(e.value), e.value
+        assert grp[1].n == owned[1]                                                             # refused before anything of rank 1 was regathered
+    finally:
+        if th:
+            th.close()
+        close_all(grp)
+        if group:
+            product_lib.thread_group_destroy(group)
 
 
 def test_the_export_writes_nothing(product_lib):
