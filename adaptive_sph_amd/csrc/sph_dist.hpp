@@ -195,9 +195,7 @@ int slab_refresh_fused(Group& G, std::vector<Member>& M, std::vector<std::vector
 // `stride` / `off` (floats): where the field's words sit inside a wider per-particle record (default: a plain array of `words` floats)
 // `totals` (with tot_slot >= 0): this rank's solver totals of that iteration are added up by block 0 of the packing launch itself
 struct TotalsJob {
-    int iter, residual_density;
-    float max_avg_error;
-    uint32_t max_iters;
+    int iter;
 };
 int refresh_ghosts(Group& G, std::vector<Member>& M, float* (*sel)(Member&), int words, const char* what, int tot_slot = -1, float* (*sel2)(Member&) = nullptr,
                    int stride = 0, int off = 0, const TotalsJob* totals = nullptr);

@@ -78,6 +78,7 @@ struct ProfScope {
 };
 
 #include "sph_boundary_fused.hpp"   // HeaderOut (the step header), the header reduction's visiting order, the two-level cell-range table
+#include "sph_solve_rule.hpp"       // the pressure solve: stop rule, progress word, deciders / sweep parts / tails / source kinds
 
 // ---- Jacobi control block (device resident; copied to the host at sync points) ----------------
 struct SolverCtrl {
@@ -285,7 +286,7 @@ struct SweepArgs {
     const uint32_t* elist_a = nullptr;
     const uint32_t* elist_b = nullptr;
     uint32_t n_ea = 0, n_eb = 0;
-    int part = 0;
+    SweepPart part = PART_WHOLE;
     double* solver_tot; // multi-rank: all-reduced solver totals (RCCL: this rank's own row; the others' rows in tot_table)
     const double* tot_table = nullptr;   // RCCL transport: every rank's totals side by side, summed by the readers (SolveP, sph_sweeps.hip)
     int tot_nr = 0, tot_self = 0;
@@ -305,8 +306,8 @@ struct SweepArgs {
     SolverCtrl* ctrl;
     const uint32_t* gate = nullptr;   // chained solves: the launches of the second solve leave at once while this word is 0 (k_solver_handoff)
     DeviceStatus* status;
-    // paced solves (one context): the stop decision of every iteration is also stored in mapped host memory as
-    // (epoch << 16) | (stop << 15) | iteration, so that the host queues iterations against the device's progress (sph_step.hip)
+    // paced solves: the stop decision of every iteration is also stored in mapped host memory (sph_solve_rule.hpp: prog_word), so that
+    // the host queues iterations against the device's progress (sph_step.hip: solve_paced)
     uint32_t* prog_host = nullptr;
     uint32_t prog_epoch = 0;
     int opt_tile = 0, opt_jacobi_generic = 0;   // Options::tile / ::jacobi_generic of the context (sph_context.hpp)
@@ -331,25 +332,22 @@ void launch_constrain_apply(hipStream_t s, Profiler* prof, const SweepArgs& a, f
 void launch_aii_const(hipStream_t s, Profiler* prof, const SweepArgs& a);
 void launch_aii_const_non_pressure(hipStream_t s, Profiler* prof, const SweepArgs& a);   // + the non-pressure acceleration, one sweep
 void launch_non_pressure(hipStream_t s, Profiler* prof, const SweepArgs& a);                // vel -> vel_tmp
-void launch_source_term(hipStream_t s, Profiler* prof, const SweepArgs& a, int kind, int residual_density);  // kind: 0 div, 1 full, 2 only-density; includes Jacobi iteration 0
-// sweep A of iteration iter >= 1 (+ the stop decision of iteration iter - 1, taken by its block 0); iter < 0: a^p from the solve's final pressures
-// part (slab decomposition): 0 one launch; 1 the lanes without a ghost in reach; 2 the halo members and the ghosts (SweepCommon) --
-// with part != 0 the rank's totals come from launch_solver_totals instead of this sweep's block 0
-void launch_pressure_accel(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters, int multi,
-                           int part = 0);
-void launch_solver_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters);
-// ... as block 0 of the launch that packs the halo members' values for the iteration's ghost exchange (sph_slabs.hip: refresh_ghosts)
-void launch_pack_and_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters,
-                            const uint32_t* src_idx, uint32_t cnt0, uint32_t cnt1, int words, int stride, int off, const float* field, float* out0, float* out1);
+void launch_source_term(hipStream_t s, Profiler* prof, const SweepArgs& a, SourceKind kind, int residual_density);  // includes Jacobi iteration 0
+// sweep A of iteration iter >= 1 and, by its block 0, the stop decision of iteration iter - 1 (`decider`; the two launches of a split
+// sweep, `part` != PART_WHOLE, take DECIDE_NOT_HERE); iter < 0: a^p from the solve's final pressures, nothing is decided or read of `rule`
+void launch_pressure_accel(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule, SolveDecider decider, SweepPart part = PART_WHOLE);
+// slab decomposition: this rank's totals of iteration `iter`, as block 0 of the launch that packs the halo members' values for the
+// iteration's ghost exchange (sph_slabs.hip: refresh_ghosts)
+void launch_pack_and_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const uint32_t* src_idx, uint32_t cnt0, uint32_t cnt1, int words, int stride,
+                            int off, const float* field, float* out0, float* out1);
 void launch_ctrl_reset(hipStream_t s, SolverCtrl* ctrl, const uint32_t* gate);
-void launch_solver_progress(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters);   // paced slabs (no-op unless a.prog_host)
+// slab decomposition: the decision on iteration `iter` from the all-reduced totals (DECIDE_FROM_TOTALS) by a launch of its own
+void launch_solver_progress(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule);
 void launch_solver_handoff(hipStream_t s, Profiler* prof, SolverCtrl* ctrl, SolverCtrl* saved_host, uint32_t* gate);
-void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, int tail, float4* pm_out, int decide_iter = -1, int residual_density = 0,
-                        float max_avg_error = 0.f, uint32_t max_iters = 0, SolverCtrl* handoff_host = nullptr, uint32_t* gate_out = nullptr);
-// decide_iter >= 0 (slabs): the stop decision of that iteration is taken here; gate_out: the tail also does k_solver_handoff's job   // integrate map of the solver mode, once the solve is done
-void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters, int multi);
-void launch_solver_decide(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error,
-                          uint32_t max_iters);
+// the integrate map of the solver mode, once the solve is done; gate_out: the tail also does k_solver_handoff's job
+void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, SolveTail tail, float4* pm_out, SolverCtrl* handoff_host = nullptr,
+                        uint32_t* gate_out = nullptr);
+void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule);   // sweep B
 // level estimation (sorted order)
 struct LevelArgs {
     float k;                       // level_estimation_range / ETA
@@ -390,8 +388,6 @@ HeaderAheadP header_ahead_args(sph_ctx* c, uint32_t nblocks, HeaderOut* out_dev,
 // IISPH2: p /= sqrt(omega) on the current pressure buffer (+ p / rho^2), simulation.rs:2358-2360
 void launch_iisph2_scale(hipStream_t s, Profiler* prof, const SweepArgs& a);
 void launch_check_aii(hipStream_t s, Profiler* prof, const SweepArgs& a);   // after launch_aii_const when check_aii is set
-void launch_vel_add_pacc(hipStream_t s, Profiler* prof, const SweepArgs& a);               // v += dt a^p
-void launch_integrate(hipStream_t s, Profiler* prof, const SweepArgs& a, float4* pm_out, int mode);  // 0: v+=dt a; x+=dt v   1: hybrid
 
 // ---- regather of the persistent state into a new HOST-index order (sparse edits, merging, splitting; sph_api.hip) ----
 struct EditSrc {

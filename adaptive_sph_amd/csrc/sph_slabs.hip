@@ -513,9 +513,8 @@ int refresh_ghosts(Group& G, std::vector<Member>& M, float* (*sel)(Member&), int
         ProfScope ps(&c->prof, "ghost_pack", c->stream);
         const uint32_t nh = c->dist.n_halo[0] + c->dist.n_halo[1];
         if (totals && M[i].n && nf == 1) {   // the pack launch also adds up the rank's solver totals (its block 0): one launch, neighbours or not
-            launch_pack_and_totals(c->stream, nullptr, M[i].a, totals->iter, totals->residual_density, totals->max_avg_error, totals->max_iters,
-                                   c->dist.halo_src.as<uint32_t>(), c->dist.n_halo[0], c->dist.n_halo[1], words, stride, off, sel(M[i]), c->dist.send[0].as<float>(),
-                                   c->dist.send[1].as<float>());
+            launch_pack_and_totals(c->stream, nullptr, M[i].a, totals->iter, c->dist.halo_src.as<uint32_t>(), c->dist.n_halo[0], c->dist.n_halo[1], words, stride, off,
+                                   sel(M[i]), c->dist.send[0].as<float>(), c->dist.send[1].as<float>());
         } else
         for (int f = 0; f < nf && nh; f++)
             hipLaunchKernelGGL(k_pack_field, dim3((nh + 255) / 256), dim3(256), 0, c->stream, c->dist.halo_src.as<uint32_t>(), c->dist.n_halo[0],

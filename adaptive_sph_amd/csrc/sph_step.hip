@@ -351,15 +351,33 @@ static float* sel_lv_pmnew(Member& m) { return m.lv_pmnew; }
 // (simulation.rs:1499-1509) and everything queued behind it returns at once.  Iterations are queued speculatively up to the
 // predicted count, followed by the solve's tail (the integrate map of the solver mode, k_solver_tail), which runs only once the
 // decision is taken.  One host wait per chunk.
-// Slab decomposition: block 0 of A(k + 1) adds up the rank's totals; the all-reduce and the decision (k_solver_decide) follow
-// behind that sweep, i.e. the decision on iteration k is taken one sweep late and the reduction kernel between B and A is gone.
+// Slab decomposition: the rank's totals of iteration k are added up by block 0 of the launch that packs the ghost exchange in front of
+// A(k + 1) (k_pack_totals, or the push transport's fused launch: rank_totals_block) and all-reduced WITH that exchange; the decision is
+// taken from them at the same place as on one context -- block 0 of A(k + 1), DECIDE_FROM_TOTALS -- or, where no sweep's block 0 can
+// take it (a split sweep A, an empty slab), by k_solver_progress right behind the all-reduce (sph_solve_rule.hpp: SolveDecider).
+
+// One pressure solve of a step: its stop rule, its source term, what follows its last sweep, and which statistics it fills.
+struct SolveSpec {
+    SolveRule rule;
+    SourceKind source;
+    SolveTail tail;
+    bool density_solver;   // sph_step_stats::density_solver (else ::div_solver); the iteration counts it is predicted from are that solver's
+};
+static SolveSpec solve_iisph_density(const sph_params* p) { return {{1, p->iisph_max_avg_density_error, p->max_iters}, SRC_FULL, TAIL_VX, true}; }
+// (omega rides in the source-term sweep; the step rescales the pressures and integrates behind the solve itself)
+static SolveSpec solve_iisph2(const sph_params* p) { return {{1, p->iisph_max_avg_density_error, p->max_iters}, SRC_FULL_OMEGA, TAIL_NONE, true}; }
+static SolveSpec solve_divergence_only(const sph_params* p) { return {{0, p->hybrid_dfsph_max_avg_divergence_error, p->max_iters}, SRC_DIVERGENCE, TAIL_VX, false}; }
+static SolveSpec solve_hybrid_divergence(const sph_params* p) { return {{0, p->hybrid_dfsph_max_avg_divergence_error, p->max_iters}, SRC_DIVERGENCE, TAIL_VEL, false}; }
+static SolveSpec solve_hybrid_density(const sph_params* p)
+{
+    return {{1, p->hybrid_dfsph_max_avg_density_error, p->max_iters}, p->hybrid_dfsph_density_source_term == SPH_ONLY_DENSITY ? SRC_ONLY_DENSITY : SRC_FULL, TAIL_HYBRID, true};
+}
+// the iteration count the solve is queued for when nothing paces it: the previous step's
+static uint32_t predicted_iters(const sph_ctx* c, const SolveSpec& s) { return s.density_solver ? c->last_dens_iters : c->last_div_iters; }
+
 // The queueing state of one solve.
 struct SolveQ {
-    float max_avg_error;
-    int residual_density;
-    uint32_t max_iters;
-    int tail;
-    bool density_solver;
+    SolveSpec s;
     int tot_slot = 0;   // slab decomposition: which totals buffer the solve all-reduces (1: the gated solve of a chained pair)
     uint32_t k = 1, upto = 2;
     bool header_in_build = false;   // the build the caller queues right behind this solve's integrating tail reduces the tail's header partials (the fused merge: no k_header_ahead)
@@ -367,30 +385,25 @@ struct SolveQ {
                                                          // iteration costs two empty launches (~9 us), a wait the round trip to the host
                                                          // (measured on the driver window, 5 runs each: k/4 1.279-1.295 ms per step, k/2 1.284-1.292, k 1.300-1.311)
 };
-// sweep A of iteration k: a^p from pressure buffer k & 1, and the stop decision of iteration k - 1
-static int solve_sweep_a(Group& G, std::vector<Member>& M, const SolveQ& q, uint32_t k)
+// one context: sweep A of iteration k -- a^p from pressure buffer k & 1, and the stop decision of iteration k - 1 by its block 0
+static void solve_sweep_a(std::vector<Member>& M, const SolveQ& q, uint32_t k)
 {
-    const int multi = G.multi() ? 1 : 0;
     for (auto& m : M) {
         (void)hipSetDevice(m.c->device);
-        if (m.n) launch_pressure_accel(m.c->stream, &m.c->prof, m.a, (int)k, q.residual_density, q.max_avg_error, q.max_iters, multi);
-        else if (!multi) {   // a context without particles: nothing to iterate on (n_normal == 0)
+        if (m.n) launch_pressure_accel(m.c->stream, &m.c->prof, m.a, (int)k, q.s.rule, DECIDE_FROM_PARTIALS);
+        else {   // a context without particles: nothing to iterate on (n_normal == 0)
             SolverCtrl z{};
             z.done = 1u;
             z.slot_done[0] = z.slot_done[1] = 1u;
             z.cur = k & 1u;
             (void)hipMemcpyAsync(m.c->ctrl.p, &z, sizeof z, hipMemcpyHostToDevice, m.c->stream);
-        } else (void)hipMemsetAsync(m.c->dist.solver_tot.as<double>() + 8 * q.tot_slot, 0, 48, m.c->stream);   // an empty slab contributes zeros
+        }
     }
-    // slab decomposition: the totals of iteration k - 1 are all-reduced behind this sweep; the decision is evaluated by the
-    // blocks of B(k) themselves (OpJacobi::prologue), or by k_solver_decide before a solve's tail
-    if (multi) return G.comm->allreduce_solver(G, q.tot_slot);
-    return SPH_OK;
 }
 // Slab decomposition with neighbours: sweep A in two launches, so that the iteration's communication runs under compute.  The
 // interior -- every lane without a ghost in reach, most of the slab -- is swept on the context's SIDE stream as soon as sweep B is
-// done; the main stream meanwhile packs the halo members' p / rho^2, exchanges, unpacks, adds up this rank's totals of the previous
-// iteration (k_solver_totals: what block 0 of the one-launch sweep does) and all-reduces them; then it waits for the interior and
+// done; the main stream meanwhile adds up this rank's totals of the previous iteration and packs the halo members' p / rho^2 (one
+// launch, k_pack_totals), exchanges and all-reduces, unpacks and takes the decision (k_solver_progress); then it waits for the interior and
 // sweeps the halo members and the first ghost ring (a list launch, a few per cent of the slab).  The collectives stay on the main
 // stream on purpose: a dependency between two streams costs ~9.5 us on this platform (scripts/ubench/xstream_hop.hip), and this
 // way the two such hops (B -> interior, interior -> edge) sit beside the communication, not in its chain.  Same collectives in the
@@ -417,11 +430,14 @@ static int exchange_and_sweep_a(Group& G, std::vector<Member>& M, const SolveQ& 
     const bool recs = sweep_a_on_records(M[0].a);
     float* (*sel)(Member&) = recs ? ((ka & 1u) ? sel_rec1 : sel_rec0) : ((ka & 1u) ? sel_pt1 : sel_pt0);
     const int stride = recs ? 4 : 1, off = recs ? 2 : 0;
-    const TotalsJob job{(int)ka - 1, q.residual_density, q.max_avg_error, q.max_iters};   // this rank's totals of iteration ka - 1 (what block 0 of the single-rank sweep adds up)
+    const TotalsJob job{(int)ka - 1};   // this rank's totals of iteration ka - 1 (what block 0 of the single-rank sweep adds up)
     if (!split_sweep_a(G, M)) {
-        if (!G.multi()) return solve_sweep_a(G, M, q, ka);
-        // slab decomposition, one launch per sweep: this rank's totals of iteration ka - 1 first (k_solver_totals: what block 0 of
-        // the single-rank sweep does), so that their all-reduce can travel WITH the ghosts' p / rho^2 -- one collective call per
+        if (!G.multi()) {
+            solve_sweep_a(M, q, ka);
+            return SPH_OK;
+        }
+        // slab decomposition, one launch per sweep: this rank's totals of iteration ka - 1 first (block 0 of k_pack_totals:
+        // rank_totals_block), so that their all-reduce can travel WITH the ghosts' p / rho^2 -- one collective call per
         // iteration (one grouped RCCL launch) -- then the sweep with the reduced totals already in place
         for (auto& m : M) {
             sph_ctx* c = m.c;
@@ -431,8 +447,8 @@ static int exchange_and_sweep_a(Group& G, std::vector<Member>& M, const SolveQ& 
         if ((rc = refresh_ghosts(G, M, sel, 1, "pt", q.tot_slot, nullptr, stride, off, &job))) return rc;   // (block 0 of the pack launch adds up the totals)
         for (auto& m : M) {
             (void)hipSetDevice(m.c->device);
-            if (m.n) launch_pressure_accel(m.c->stream, &m.c->prof, m.a, (int)ka, q.residual_density, q.max_avg_error, q.max_iters, 2);   // (block 0 takes the decision on iteration ka - 1 from the all-reduced totals)
-            else launch_solver_progress(m.c->stream, &m.c->prof, m.a, (int)ka - 1, q.residual_density, q.max_avg_error, q.max_iters);   // an empty slab has no sweep to take it
+            if (m.n) launch_pressure_accel(m.c->stream, &m.c->prof, m.a, (int)ka, q.s.rule, DECIDE_FROM_TOTALS);   // (block 0 takes the decision on iteration ka - 1)
+            else launch_solver_progress(m.c->stream, &m.c->prof, m.a, (int)ka - 1, q.s.rule);   // an empty slab has no sweep to take it
         }
         return SPH_OK;
     }
@@ -445,7 +461,7 @@ static int exchange_and_sweep_a(Group& G, std::vector<Member>& M, const SolveQ& 
         (void)hipSetDevice(c->device);
         HIPCHK(c, hipEventRecord(d.ev_x[0], c->stream));
         HIPCHK(c, hipStreamWaitEvent(d.xstream, d.ev_x[0], 0));
-        if (m.n) launch_pressure_accel(d.xstream, &c->prof, m.a, (int)ka, q.residual_density, q.max_avg_error, q.max_iters, 1, 1);
+        if (m.n) launch_pressure_accel(d.xstream, &c->prof, m.a, (int)ka, q.s.rule, DECIDE_NOT_HERE, PART_INTERIOR);
         HIPCHK(c, hipEventRecord(d.ev_x[1], d.xstream));
         if (!m.n) HIPCHK(c, hipMemsetAsync(c->dist.solver_tot.as<double>() + 8 * q.tot_slot, 0, 48, c->stream));   // an empty slab contributes zeros
     }
@@ -453,9 +469,9 @@ static int exchange_and_sweep_a(Group& G, std::vector<Member>& M, const SolveQ& 
     for (auto& m : M) {
         sph_ctx* c = m.c;
         (void)hipSetDevice(c->device);
-        launch_solver_progress(c->stream, &c->prof, m.a, (int)ka - 1, q.residual_density, q.max_avg_error, q.max_iters);   // the decision on iteration ka - 1 (paced: the host learns of it while the interior still sweeps)
+        launch_solver_progress(c->stream, &c->prof, m.a, (int)ka - 1, q.s.rule);   // the decision on iteration ka - 1 (paced: the host learns of it while the interior still sweeps)
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->dist.ev_x[1], 0));
-        if (m.n) launch_pressure_accel(c->stream, &c->prof, m.a, (int)ka, q.residual_density, q.max_avg_error, q.max_iters, 1, 2);
+        if (m.n) launch_pressure_accel(c->stream, &c->prof, m.a, (int)ka, q.s.rule, DECIDE_NOT_HERE, PART_EDGE);
     }
     return SPH_OK;
 }
@@ -475,12 +491,12 @@ static int solve_begin(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
 static int solve_queue(Group& G, std::vector<Member>& M, SolveQ& q, bool handoff = false, bool publish_next = false)
 {
     int rc;
-    const int multi = G.multi() ? 1 : 0;
-    for (; q.k <= q.upto && q.k <= q.max_iters; q.k++) {
+    const SolveTail tail = q.s.tail;
+    for (; q.k <= q.upto && q.k <= q.s.rule.max_iters; q.k++) {
         const uint32_t k = q.k;
         for (auto& m : M) {
             (void)hipSetDevice(m.c->device);
-            if (m.n) launch_jacobi_update(m.c->stream, &m.c->prof, m.a, (int)k, q.residual_density, q.max_avg_error, q.max_iters, multi);
+            if (m.n) launch_jacobi_update(m.c->stream, &m.c->prof, m.a, (int)k, q.s.rule);
         }
         // (no exchange of a^p: the first ghost ring computes its own in sweep A)
         if ((rc = exchange_and_sweep_a(G, M, q, k + 1))) return rc;
@@ -491,22 +507,21 @@ static int solve_queue(Group& G, std::vector<Member>& M, SolveQ& q, bool handoff
         (void)hipSetDevice(m.c->device);
         SolverCtrl* hand_host = handoff ? m.c->ctrl_host_dev + 1 : nullptr;
         uint32_t* gate_out = handoff ? (uint32_t*)(m.c->ctrl.as<SolverCtrl>() + 2) : nullptr;
-        if (!m.n || q.tail == 0 /* TAIL_NONE */) {
+        if (!m.n || tail == TAIL_NONE) {
             if (handoff) launch_solver_handoff(m.c->stream, &m.c->prof, m.c->ctrl.as<SolverCtrl>(), hand_host, gate_out);
             continue;
         }
-        launch_solver_tail(m.c->stream, &m.c->prof, m.a, q.tail, m.c->pm[m.c->pcur ^ 1].as<float4>(), -1, q.residual_density,
-                           q.max_avg_error, q.max_iters, hand_host, gate_out);
-        if (q.tail == 1 /* TAIL_VEL */ && source_term_on_records(m.a)) m.a.xv_ok = true;   // (the tail rewrote the {x, y, v} record with the velocities it left)
-        if (q.tail >= 2 /* TAIL_VX, TAIL_HYBRID */ && m.a.hdr_partials && !q.header_in_build)
-            launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev, publish_next && !multi);
+        launch_solver_tail(m.c->stream, &m.c->prof, m.a, tail, m.c->pm[m.c->pcur ^ 1].as<float4>(), hand_host, gate_out);
+        if (tail == TAIL_VEL && source_term_on_records(m.a)) m.a.xv_ok = true;   // (the tail rewrote the {x, y, v} record with the velocities it left)
+        if (tail >= TAIL_VX /* the integrating tails */ && m.a.hdr_partials && !q.header_in_build)
+            launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev, publish_next && !G.multi());
     }
     return SPH_OK;
 }
 static void solve_stats(Member& m, const SolveQ& q, const SolverCtrl& h)
 {
     m.c->pressure_cur = h.cur;
-    sph_solver_stats* st = q.density_solver ? &m.st.density_solver : &m.st.div_solver;
+    sph_solver_stats* st = q.s.density_solver ? &m.st.density_solver : &m.st.div_solver;
     st->iters = h.iters;
     st->converged = 1;
     st->normal_count = h.normal;
@@ -545,11 +560,12 @@ static uint32_t pace_prediction(const sph_ctx* c, uint32_t n, uint32_t last, uin
     return std::min(last, prev);
 }
 // Slab decompositions pace the same way with lead 1 and no unpaced head beyond the two iterations every solve runs: block 0 of the
-// sweep A behind the iteration's exchange-and-all-reduce publishes what the stop rule makes of the ALL-REDUCED totals
-// (solver_publish_progress_multi) -- the same word on every rank -- and iteration k + 1 is queued only once iteration k is known to
+// sweep A behind the iteration's exchange-and-all-reduce (or k_solver_progress) publishes what the stop rule makes of the ALL-REDUCED
+// totals (solver_decide_multi) -- the same word on every rank -- and iteration k + 1 is queued only once iteration k is known to
 // continue: every rank queues exactly the same launches and collectives, none in vain (the predicted queue this replaces re-sent the
 // ghosts and all-reduced the totals of every over-predicted iteration, and waited for the host on every shortfall).
-static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t predicted_iters)
+// The unpaced head of the solve comes from its own solver's last two counts (pace_prediction).  The progress word: sph_solve_rule.hpp.
+static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q)
 {
     const bool multi = G.multi();
     size_t lead_member = 0;   // whose progress word the host watches: the first member with particles (all members publish the same decisions)
@@ -558,33 +574,36 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
     sph_ctx* c = m.c;
     const uint32_t lead = multi ? 1u : pace_lead(c, m.n);
     int rc;
-    // one epoch for the whole group (a member's word is only compared with the epoch its own launches carry)
     sph_ctx* c0 = M[0].c;
-    c0->solve_epoch = c0->solve_epoch >= 0xffffu ? 1u : c0->solve_epoch + 1u;
+    const uint32_t head = q.s.density_solver ? pace_prediction(c0, M[0].n, c0->last_dens_iters, c0->prev_dens_iters)
+                                             : pace_prediction(c0, M[0].n, c0->last_div_iters, c0->prev_div_iters);
+    // one epoch for the whole group (a member's word is only compared with the epoch its own launches carry)
+    c0->solve_epoch = prog_next_epoch(c0->solve_epoch);
     const uint32_t epoch = c0->solve_epoch;
     for (auto& mm : M) {
         mm.c->solve_epoch = epoch;
         mm.a.prog_host = mm.c->prog_host_dev;
         mm.a.prog_epoch = epoch;
     }
-    if ((rc = solve_begin(G, M, q, multi ? 2u : predicted_iters))) return rc;
+    if ((rc = solve_begin(G, M, q, multi ? 2u : head))) return rc;
+    const uint32_t max_iters = q.s.rule.max_iters;
     auto iteration = [&](uint32_t k) -> int {
         for (auto& mm : M) {
             (void)hipSetDevice(mm.c->device);
-            if (mm.n) launch_jacobi_update(mm.c->stream, &mm.c->prof, mm.a, (int)k, q.residual_density, q.max_avg_error, q.max_iters, multi ? 1 : 0);
+            if (mm.n) launch_jacobi_update(mm.c->stream, &mm.c->prof, mm.a, (int)k, q.s.rule);
         }
         return exchange_and_sweep_a(G, M, q, k + 1);
     };
-    for (; q.k <= q.upto && q.k <= q.max_iters; q.k++)
+    for (; q.k <= q.upto && q.k <= max_iters; q.k++)
         if ((rc = iteration(q.k))) return rc;
     auto t0 = std::chrono::steady_clock::now();
     int last_seen = -2;
     for (uint64_t spins = 0;; spins++) {
         const uint32_t w = *c->prog_host;
-        const bool seen = (w >> 16) == epoch;
-        if (seen && (w & 0x8000u)) break;
-        const int decided = seen ? (int)(w & 0x7fffu) : -1;   // iterations 0 .. decided are decided; A(q.k) is queued and decides q.k - 1
-        if (q.k <= q.max_iters && (int)q.k - 1 - decided < (int)lead) {
+        const bool seen = prog_seen(w, epoch);
+        if (seen && prog_stopped(w)) break;
+        const int decided = seen ? (int)prog_decided(w) : -1;   // iterations 0 .. decided are decided; A(q.k) is queued and decides q.k - 1
+        if (q.k <= max_iters && (int)q.k - 1 - decided < (int)lead) {
             if ((rc = iteration(q.k))) return rc;
             q.k++;
             continue;
@@ -596,8 +615,8 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
             // no decision for 2 s: a faulted kernel (the event path reports it) -- or a decision that never comes
             if ((rc = wait_stream(c))) return rc;
             const uint32_t w2 = *c->prog_host;
-            if ((w2 >> 16) == epoch && (w2 & 0x8000u)) break;
-            if ((w2 >> 16) == epoch && (int)(w2 & 0x7fffu) != decided) continue;
+            if (prog_seen(w2, epoch) && prog_stopped(w2)) break;
+            if (prog_seen(w2, epoch) && (int)prog_decided(w2) != decided) continue;
             return c->fail(SPH_ERR_DEVICE, "pressure solve: the device finished its queue without a stop decision (iteration %u queued)", q.k - 1);
         }
     }
@@ -606,36 +625,40 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
     return SPH_OK;
 }
 
+// The host wait that ends a solve.  On a slab decomposition the guards are agreed on the device first if this is the step's last
+// solve (SYNC_FINAL), and left for that one otherwise (SYNC_DEFER).
+static int solve_wait(Group& G, bool final_solve)
+{
+    const bool multi = G.multi();
+    int rc;
+    if (multi && final_solve && (rc = G.comm->agree_guards_queued(G))) return rc;
+    return sync_ctrl(G, multi ? (final_solve ? SYNC_FINAL : SYNC_DEFER) : SYNC_AGREE);
+}
+
 // iisph_pressure_iterations (simulation.rs:1377-1516) with a host wait of its own
-static int pressure_iterations(Group& G, std::vector<Member>& M, float max_avg_error, int residual_density, uint32_t max_iters,
-                               uint32_t predicted_iters, int tail, bool density_solver, bool final_solve,
+static int pressure_iterations(Group& G, std::vector<Member>& M, const SolveSpec& spec, bool final_solve,
                                const std::function<int()>* behind_tail = nullptr /* paced: queued behind the solve's tail, in front of the wait */,
                                bool header_in_build = false /* SolveQ::header_in_build: `behind_tail` queues the fused merge */)
 {
     int rc;
-    const int multi = G.multi() ? 1 : 0;
-    SolveQ q{max_avg_error, residual_density, max_iters, tail, density_solver};
+    SolveQ q{spec};
     q.header_in_build = header_in_build && behind_tail != nullptr;
     // (a slab decomposition paces whether or not THIS rank has particles: every rank must queue the same collectives -- an empty
     //  slab's progress word is published by a launch of its own, launch_solver_progress)
-    if ((multi || M[0].n > 0) && M[0].c->paced_step) {
-        sph_ctx* c0 = M[0].c;
-        const uint32_t head = density_solver ? pace_prediction(c0, M[0].n, c0->last_dens_iters, c0->prev_dens_iters) : pace_prediction(c0, M[0].n, c0->last_div_iters, c0->prev_div_iters);
-        if ((rc = solve_paced(G, M, q, head))) return rc;
+    if ((G.multi() || M[0].n > 0) && M[0].c->paced_step) {
+        if ((rc = solve_paced(G, M, q))) return rc;
         if ((rc = solve_queue(G, M, q, false, true))) return rc;   // (the tail)
         if (behind_tail && (rc = (*behind_tail)())) return rc;
-        if (multi && final_solve && (rc = G.comm->agree_guards_queued(G))) return rc;
-        if ((rc = sync_ctrl(G, multi ? (final_solve ? SYNC_FINAL : SYNC_DEFER) : SYNC_AGREE))) return rc;
+        if ((rc = solve_wait(G, final_solve))) return rc;
         for (auto& m : M) solve_stats(m, q, *m.c->ctrl_host);
         return SPH_OK;
     }
-    if ((rc = solve_begin(G, M, q, predicted_iters))) return rc;
+    if ((rc = solve_begin(G, M, q, predicted_iters(M[0].c, spec)))) return rc;
     for (;;) {
         if ((rc = solve_queue(G, M, q, false, true))) return rc;
-        if (multi && final_solve && (rc = G.comm->agree_guards_queued(G))) return rc;
-        if ((rc = sync_ctrl(G, multi ? (final_solve ? SYNC_FINAL : SYNC_DEFER) : SYNC_AGREE))) return rc;
+        if ((rc = solve_wait(G, final_solve))) return rc;
         if (M[0].c->ctrl_host->done) break;
-        if (q.k > max_iters) break;  // cannot happen: the decision on iteration max_iters is always "stop"
+        if (q.k > spec.rule.max_iters) break;  // cannot happen: the decision on iteration max_iters is always "stop"
         q.extend();   // the prediction (the previous step's count) fell short
     }
     for (auto& m : M) solve_stats(m, q, *m.c->ctrl_host);
@@ -816,7 +839,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     // (the progress word carries the iteration in 15 bits: a solve that may run longer keeps the predicted queue)
     // Slab decompositions pace too (Options::slab_paced; lead 1: nothing is ever queued in vain, so every rank queues the same
     // collectives) -- parameters only: the same on every rank
-    const bool paced = c0->opt.paced != 0 && p->max_iters <= 0x7fffu && (!G.multi() || c0->opt.slab_paced != 0);   // 0: predicted queue + waits
+    const bool paced = c0->opt.paced != 0 && p->max_iters <= PROG_MAX_ITERS && (!G.multi() || c0->opt.slab_paced != 0);   // 0: predicted queue + waits
     for (auto c : G.m) c->paced_step = paced;
     for (auto c : G.m) c->dist.overlap_env = c0->opt.overlap;
     for (auto c : G.m) c->publish_folded = false;
@@ -1463,11 +1486,11 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         }
         return refresh_ghosts(G, M, sel_vel, 2, "vel");
     };
-    auto begin_solve = [&](int kind, int residual_density) {
+    auto begin_solve = [&](const SolveSpec& s) {
         for (auto& m : M) {
             (void)hipSetDevice(m.c->device);
             if (!m.n) launch_ctrl_reset(m.c->stream, m.c->ctrl.as<SolverCtrl>(), m.a.gate);   // else: reset by the source-term sweep
-            if (m.n) launch_source_term(m.c->stream, &m.c->prof, m.a, kind, residual_density);  // + Jacobi iteration 0
+            if (m.n) launch_source_term(m.c->stream, &m.c->prof, m.a, s.source, s.rule.residual_density);  // + Jacobi iteration 0
         }
     };
     auto rec = [&](int e) {
@@ -1477,7 +1500,6 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                 (void)hipEventRecord(m.c->ev[e], m.c->stream);
             }
     };
-    enum { T_NONE = 0, T_VEL = 1, T_VX = 2, T_HYBRID = 3 };  // TAIL_* of sph_sweeps.hip
     g_trace.mark(3);
     // The NEXT step's neighbour build, queued behind this step's integrating tail (sph_context.hpp: Ahead): cell keys on a grid
     // predicted from this step's bounding box + 2 cells (a particle moves at most cfl_factor supports per step), cell sort,
@@ -1588,19 +1610,22 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     };
 
     switch (p->pressure_solver_method) {
-    case SPH_SOLVER_IISPH:  // simulation.rs:2389-2446
+    case SPH_SOLVER_IISPH: {  // simulation.rs:2389-2446
+        const SolveSpec solve = solve_iisph_density(p);
         if ((rc = non_pressure())) return rc;
         rec(4);
-        begin_solve(1, 1);
+        begin_solve(solve);
         if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, p->iisph_max_avg_density_error, 1, p->max_iters, c0->last_dens_iters, T_VX, true, !level_on, &queue_ahead_build, plan.fused))) return rc;
+        if ((rc = pressure_iterations(G, M, solve, !level_on, &queue_ahead_build, plan.fused))) return rc;
         rec(5);
         break;
-    case SPH_SOLVER_IISPH2:  // simulation.rs:2262-2387: omega rides in the source-term sweep; p /= sqrt(omega) before the last a^p
+    }
+    case SPH_SOLVER_IISPH2: {  // simulation.rs:2262-2387: omega rides in the source-term sweep; p /= sqrt(omega) before the last a^p
+        const SolveSpec solve = solve_iisph2(p);
         if ((rc = non_pressure())) return rc;
         rec(4);
-        begin_solve(3, 1);
-        if ((rc = pressure_iterations(G, M, p->iisph_max_avg_density_error, 1, p->max_iters, c0->last_dens_iters, T_NONE, true, false))) return rc;
+        begin_solve(solve);
+        if ((rc = pressure_iterations(G, M, solve, false))) return rc;
         for (auto& m : M) {
             (void)hipSetDevice(m.c->device);
             if (m.n) launch_iisph2_scale(m.c->stream, &m.c->prof, m.a);
@@ -1609,27 +1634,31 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         for (auto& m : M) {   // a^p again, from the rescaled pressures (simulation.rs:2362-2373), then v += dt a^p ; x += dt v
             (void)hipSetDevice(m.c->device);
             if (!m.n) continue;
-            launch_pressure_accel(m.c->stream, &m.c->prof, m.a, -1, 1, 0.f, 0u, G.multi() ? 1 : 0);
-            launch_solver_tail(m.c->stream, &m.c->prof, m.a, T_VX, m.c->pm[m.c->pcur ^ 1].as<float4>());
+            launch_pressure_accel(m.c->stream, &m.c->prof, m.a, -1, solve.rule, DECIDE_NOT_HERE);   // (the solve is over: nothing to decide)
+            launch_solver_tail(m.c->stream, &m.c->prof, m.a, TAIL_VX, m.c->pm[m.c->pcur ^ 1].as<float4>());
             if (m.a.hdr_partials) launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev);
         }
-        if (G.multi() && !level_on && (rc = G.comm->agree_guards_queued(G))) return rc;
-        if ((rc = sync_ctrl(G, G.multi() ? (level_on ? SYNC_DEFER : SYNC_FINAL) : SYNC_AGREE))) return rc;
+        if ((rc = solve_wait(G, !level_on))) return rc;
         rec(5);
         break;
-    case SPH_SOLVER_ONLY_DIVERGENCE:  // simulation.rs:2448-2500
+    }
+    case SPH_SOLVER_ONLY_DIVERGENCE: {  // simulation.rs:2448-2500
+        const SolveSpec solve = solve_divergence_only(p);
         if ((rc = non_pressure())) return rc;
         rec(2);
-        begin_solve(0, 0);
+        begin_solve(solve);
         if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, c0->last_div_iters, T_VX, false, !level_on, &queue_ahead_build, plan.fused))) return rc;
+        if ((rc = pressure_iterations(G, M, solve, !level_on, &queue_ahead_build, plan.fused))) return rc;
         rec(3);
         break;
+    }
     default: {  // HybridDFSPH, simulation.rs:2502-2670
+        const SolveSpec divergence = solve_hybrid_divergence(p), density = solve_hybrid_density(p);
+        const bool final_solve = !level_on;   // (of the density solve: the step's last unless the level estimation follows)
         if (p->hybrid_dfsph_non_pressure_accel_before_divergence_free)
             if ((rc = non_pressure())) return rc;
         rec(2);
-        begin_solve(0, 0);
+        begin_solve(divergence);
         // Forces in front of the divergence solve (the default): the two solves are CHAINED -- the density solve is queued right
         // behind the divergence solve's tail, its launches gated on the device by "the divergence solve ended" (k_solver_handoff),
         // and the step waits once, at its end.  If the divergence solve needed more iterations than were queued, the gated
@@ -1643,26 +1672,22 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         if (paced && (G.multi() || M[0].n > 0)) {
             // both solves paced against the device's progress, ONE host wait at the end of the step (a slab decomposition: the
             // ghosts' velocities follow the first solve's tail, the guards are agreed in front of the wait)
-            const bool multi = G.multi();
-            SolveQ qd{p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, T_VEL, false};
-            SolveQ qs{p->hybrid_dfsph_max_avg_density_error, 1, p->max_iters, T_HYBRID, true};
-            if ((rc = solve_paced(G, M, qd, pace_prediction(c0, M[0].n, c0->last_div_iters, c0->prev_div_iters)))) return rc;
+            SolveQ qd{divergence}, qs{density};
+            if ((rc = solve_paced(G, M, qd))) return rc;
             if ((rc = solve_queue(G, M, qd, true))) return rc;   // the tail (v += dt a^p): it also leaves the solve's control block in ctrl_host[1]
             g_trace.mark(4);
             rec(3);
-            if (multi && (rc = refresh_ghosts(G, M, sel_vel, 2, "vel"))) return rc;   // v += dt a^p happened in the tail: the forces / the source term read the neighbours' velocities
+            if (G.multi() && (rc = refresh_ghosts(G, M, sel_vel, 2, "vel"))) return rc;   // v += dt a^p happened in the tail: the forces / the source term read the neighbours' velocities
             if (!p->hybrid_dfsph_non_pressure_accel_before_divergence_free)
                 if ((rc = non_pressure())) return rc;
             rec(4);
-            begin_solve(p->hybrid_dfsph_density_source_term == SPH_ONLY_DENSITY ? 2 : 1, 1);
+            begin_solve(density);
             if ((rc = plan_ahead_build())) return rc;
             qs.header_in_build = plan.fused;   // (queue_ahead_build() right behind the tail)
-            if ((rc = solve_paced(G, M, qs, pace_prediction(c0, M[0].n, c0->last_dens_iters, c0->prev_dens_iters)))) return rc;
+            if ((rc = solve_paced(G, M, qs))) return rc;
             if ((rc = solve_queue(G, M, qs, false, true))) return rc;
             if ((rc = queue_ahead_build())) return rc;
-            const bool final_solve = !level_on;
-            if (multi && final_solve && (rc = G.comm->agree_guards_queued(G))) return rc;
-            if ((rc = sync_ctrl(G, multi ? (final_solve ? SYNC_FINAL : SYNC_DEFER) : SYNC_AGREE))) return rc;
+            if ((rc = solve_wait(G, final_solve))) return rc;
             for (auto& m : M) {
                 solve_stats(m, qd, m.c->ctrl_host[1]);
                 solve_stats(m, qs, *m.c->ctrl_host);
@@ -1674,12 +1699,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const bool chain_wanted = c0->opt.chain >= 0 ? c0->opt.chain == 1 : c0->last_div_iters == c0->prev_div_iters;
         const bool chain = (G.multi() || M[0].n > 0) && p->hybrid_dfsph_non_pressure_accel_before_divergence_free && chain_wanted;
         if (chain) {
-            const int multi = G.multi() ? 1 : 0;
-            const bool final_solve = !level_on;
-            SolveQ qd{p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, T_VEL, false};
-            SolveQ qs{p->hybrid_dfsph_max_avg_density_error, 1, p->max_iters, T_HYBRID, true};
+            SolveQ qd{divergence}, qs{density};
             qs.tot_slot = 1;
-            const int kind = p->hybrid_dfsph_density_source_term == SPH_ONLY_DENSITY ? 2 : 1;
             auto set_gate = [&](bool on) {
                 for (auto& m : M) {
                     m.a.gate = on ? (const uint32_t*)(m.c->ctrl.as<SolverCtrl>() + 2) : nullptr;
@@ -1687,7 +1708,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                     if (m.a.tot_table) m.a.tot_table = m.c->dist.tot_table.as<double>() + (on ? (size_t)m.c->dist.nranks * 8 : 0);
                 }
             };
-            if ((rc = solve_begin(G, M, qd, c0->last_div_iters))) return rc;
+            if ((rc = solve_begin(G, M, qd, predicted_iters(c0, divergence)))) return rc;
             for (bool div_done = false;;) {
                 if (!div_done) {
                     set_gate(false);
@@ -1697,12 +1718,11 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                     if ((rc = refresh_ghosts(G, M, sel_vel, 2, "vel"))) return rc;  // v += dt a^p happened in the tail (or nothing did: the same values again)
                     rec(4);
                     set_gate(true);
-                    begin_solve(kind, 1);   // the density solve from its start
-                    if ((rc = solve_begin(G, M, qs, c0->last_dens_iters))) return rc;
+                    begin_solve(density);   // the density solve from its start
+                    if ((rc = solve_begin(G, M, qs, predicted_iters(c0, density)))) return rc;
                 }
                 if ((rc = solve_queue(G, M, qs, false, true))) return rc;
-                if (multi && final_solve && (rc = G.comm->agree_guards_queued(G))) return rc;
-                if ((rc = sync_ctrl(G, multi ? (final_solve ? SYNC_FINAL : SYNC_DEFER) : SYNC_AGREE))) return rc;
+                if ((rc = solve_wait(G, final_solve))) return rc;
                 if (!div_done) {
                     if (!M[0].c->ctrl_host[1].done) {   // the divergence solve fell short: nothing of the density solve ran (on any rank)
                         if (qd.k > p->max_iters) return c0->fail(SPH_ERR_DEVICE, "divergence solve: no decision after max_iters iterations");
@@ -1722,15 +1742,15 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             rec(5);
             break;
         }
-        if ((rc = pressure_iterations(G, M, p->hybrid_dfsph_max_avg_divergence_error, 0, p->max_iters, c0->last_div_iters, T_VEL, false, false))) return rc;
+        if ((rc = pressure_iterations(G, M, divergence, false))) return rc;
         g_trace.mark(4);
         rec(3);
         if ((rc = refresh_ghosts(G, M, sel_vel, 2, "vel"))) return rc;  // v += dt a^p happened in the final sweep
         if (!p->hybrid_dfsph_non_pressure_accel_before_divergence_free)
             if ((rc = non_pressure())) return rc;
         rec(4);
-        begin_solve(p->hybrid_dfsph_density_source_term == SPH_ONLY_DENSITY ? 2 : 1, 1);
-        if ((rc = pressure_iterations(G, M, p->hybrid_dfsph_max_avg_density_error, 1, p->max_iters, c0->last_dens_iters, T_HYBRID, true, !level_on))) return rc;
+        begin_solve(density);
+        if ((rc = pressure_iterations(G, M, density, final_solve))) return rc;
         g_trace.mark(5);
         rec(5);
         break;

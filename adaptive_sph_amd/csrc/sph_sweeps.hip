@@ -93,9 +93,8 @@ struct SweepCommon {
     uint4* __restrict__ nlx;   // explicit index lists (nullptr in uniform scenes)
     const uint8_t* __restrict__ owned;  // slab decomposition: ghost lanes idle (their values come from their owner)
     const uint8_t* __restrict__ ring1;  // ... except, in RING1 ops, the ghosts within one support radius of the cut
-    // slab decomposition, a sweep in two launches (the ghost exchange runs under the first): part 1 = every lane whose `edge`
-    // byte is 0 (owned, no ghost within reach); part 2 = the listed slots (the halo members, then the ghosts); 0 = one launch
-    int part;
+    // slab decomposition, a sweep in two launches (sph_solve_rule.hpp: SweepPart): the edge bytes, the halo members' and the ghosts' slots
+    SweepPart part;
     const uint8_t* __restrict__ edge;
     const uint32_t* __restrict__ elist_a;
     const uint32_t* __restrict__ elist_b;
@@ -642,7 +641,7 @@ __device__ __forceinline__ void sweep_block(const Op& op, const SweepCommon& c)
     const uint32_t blk = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     if (blk >= c.nblocks) return;
     uint32_t i = blk * SWEEP_THREADS + threadIdx.x;
-    if (c.part == 2) i = i < c.n_ea ? c.elist_a[i] : (i < c.n_ea + c.n_eb ? c.elist_b[i - c.n_ea] : c.n);   // (launch-uniform test)
+    if (c.part == PART_EDGE) i = i < c.n_ea ? c.elist_a[i] : (i < c.n_ea + c.n_eb ? c.elist_b[i - c.n_ea] : c.n);   // (launch-uniform test)
     const uint32_t ic = i < c.n ? i : 0;
     // slab decomposition: the record and the list word are requested together with the flags (one memory round trip at the head
     // of every wave instead of two); otherwise only by the lanes that have work (level-set propagation skips most)
@@ -654,7 +653,7 @@ __device__ __forceinline__ void sweep_block(const Op& op, const SweepCommon& c)
         if (!BUILD) lw = c.nl[ic];
     }
     const bool mine = !slab || c.owned[ic] || (OpRing1<Op>::value && c.ring1 && c.ring1[ic]);
-    const bool active = i < c.n && mine && !op.lane_skip(i) && !(c.part == 1 && c.edge[ic]);
+    const bool active = i < c.n && mine && !op.lane_skip(i) && !(c.part == PART_INTERIOR && c.edge[ic]);
     typename Op::Acc acc;
     op.init(acc);  // lane-independent state
     if (active) {
@@ -732,7 +731,7 @@ __global__ __launch_bounds__(SWEEP_THREADS, OpOffWaves<Op>::value) void k_sweep_
         const uint32_t blk = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
         if (blk < c.nblocks) {
             uint32_t i = blk * SWEEP_THREADS + threadIdx.x;
-            if (c.part == 2) i = i < c.n_ea ? c.elist_a[i] : (i < c.n_ea + c.n_eb ? c.elist_b[i - c.n_ea] : c.n);   // (launch-uniform test)
+            if (c.part == PART_EDGE) i = i < c.n_ea ? c.elist_a[i] : (i < c.n_ea + c.n_eb ? c.elist_b[i - c.n_ea] : c.n);   // (launch-uniform test)
             const uint32_t ic = i < c.n ? i : 0;
             // the record, the header byte and the first three offset groups are requested together (one round trip at the head of the wave)
             const float4 Ai = op.loadA(ic);
@@ -740,7 +739,7 @@ __global__ __launch_bounds__(SWEEP_THREADS, OpOffWaves<Op>::value) void k_sweep_
             const uint2 g0 = c.nloff[ic], g1 = c.nloff[(size_t)c.n + ic], g2 = c.nloff[2 * (size_t)c.n + ic];
             const bool slab = c.owned != nullptr;   // launch-uniform
             const bool mine = !slab || c.owned[ic] || (OpRing1<Op>::value && c.ring1 && c.ring1[ic]);
-            const bool active = i < c.n && mine && !op.lane_skip(i) && !(c.part == 1 && c.edge[ic]);
+            const bool active = i < c.n && mine && !op.lane_skip(i) && !(c.part == PART_INTERIOR && c.edge[ic]);
             typename Op::Acc acc;
             op.init(acc);
             if (active && (head & NLH_OK)) {
@@ -1381,8 +1380,8 @@ struct NBVecMr {
     float qx, qy, mr;  // vector quantity Q_j, m_j / rho_j
 };
 
-// block partial of PressureSolverStatistics in fixed lane order (deterministic); k_solver_final adds the
-// block partials in block (= particle) order.  cls: 0 normal, 1 singular, 2 negative, 3 none.
+// block partial of PressureSolverStatistics in fixed lane order (deterministic); solver_reduce_decide (one context) or
+// rank_totals_block (a slab rank) adds the block partials in a fixed order.  cls: 0 normal, 1 singular, 2 negative, 3 none.
 __device__ __forceinline__ void solver_block_partial(SolverPartial* __restrict__ partials, uint32_t cls, float err, uint32_t blk)
 {
     __shared__ SolverPartial s_w[SWEEP_THREADS / 64];
@@ -1438,7 +1437,7 @@ struct OpSource {
     SolverCtrl* __restrict__ ctrl_reset;   // the solve's control block starts from zero (first kernel of a solve)
     DeviceStatus* status;
     StepP sp;
-    int kind;  // 0 divergence, 1 full, 2 only density, 3 full with omega (OMEGA)
+    SourceKind kind;   // (SRC_FULL_OMEGA: OMEGA)
     int residual_density;
     float* __restrict__ omega;              // OMEGA only
     const uint8_t* __restrict__ size_class;
@@ -1493,7 +1492,7 @@ struct OpSource {
     __device__ void pair(Acc& a, float4 Aj, NB Bj, float dx, float dy, float r2, float hij) const
     {
         if (OMEGA && !a.large) a.om += a.om_c * Aj.z * dwdh(sqrtf(r2), hij * 2.f);   // simulation.rs:2289-2305
-        if (kind == 2) return;
+        if (kind == SRC_ONLY_DENSITY) return;
         if constexpr (MathT::EXACT) {
             float gx, gy;
             m.grad(dx, dy, r2, hij, gx, gy);
@@ -1511,7 +1510,7 @@ struct OpSource {
         const float rho_i = a.rho_i, rho_b = sp.rest_density, dt = sp.dt;
         float s;
         const float nde = sp.opdisc == SPH_OP_WINCHENBACH2020 ? sp.rest_density : rho_i;
-        if (kind == 2) {
+        if (kind == SRC_ONLY_DENSITY) {
             s = -(sp.rest_density - rho_i) / (nde * dt * dt);
         } else {
             float2 gl = make_float2(0.f, 0.f);
@@ -1520,7 +1519,7 @@ struct OpSource {
             float bdiv = sp.opdisc == SPH_OP_WINCHENBACH2020 ? bdot : rho_b / rho_i * bdot;
             if constexpr (MathT::EXACT) bdiv = wall ? m.wall_divergence(i, a.qx, a.qy, rho_i, rho_b, sp.opdisc == SPH_OP_WINCHENBACH2020) : 0.f;
             const float vdiv = a.sum + (sp.n_planes ? bdiv : 0.f);
-            if (kind == 0) s = -vdiv / dt;
+            if (kind == SRC_DIVERGENCE) s = -vdiv / dt;
             else if (OMEGA) {
                 const float om = fminf(2.5f, fmaxf(a.om, 0.125f));
                 omega[i] = om;
@@ -1572,7 +1571,7 @@ struct OpSource {
 // reasoning of OpJacobiU / OpPressureAccelU: a replay sweep costs its gather instructions.  The record holds no mass: m_j becomes the
 // mass of particle 0 (see OpPressureAccelU) -- with equal masses the pair coefficient m_j / rho_i is the generic sweep's bit for bit,
 // and so is everything behind it (same finish, same closed-form iteration 0, same residual statistics).  Divergence and full source
-// terms (kind 0 / 1); the step driver says when the record is current (SweepArgs::xv_ok), else the sweep is OpSource.
+// terms (SRC_DIVERGENCE / SRC_FULL); the step driver says when the record is current (SweepArgs::xv_ok), else the sweep is OpSource.
 template <class MathT>
 struct OpSourceU : OpSource<MathT, false> {
     static_assert(MathT::UNIFORM, "OpSourceU: uniform-h scenes");
@@ -1612,24 +1611,11 @@ struct OpSourceU : OpSource<MathT, false> {
 //   iisph_boundary_pressure_accel                                  boundary_winchenbach2020.rs:164-194
 // The neighbour payload p_j / rho_j^2 is written once per particle by the sweep that produced p.
 // ------------------------------------------------------------------------------------------------
-// What follows the LAST pressure-acceleration sweep of a solve (k_solver_tail, a per-particle map):
-//   TAIL_NONE                 nothing
-//   TAIL_VEL      HybridDFSPH after the divergence solve: v += dt a^p                    (simulation.rs:2547-2560)
-//   TAIL_VX       IISPH / OnlyDivergence: v += dt a^p ; x += dt v                         (simulation.rs:2433-2445, 2486-2499)
-//   TAIL_HYBRID   HybridDFSPH: x += dt v + dt^2 a^p ; v += dt a^p * min(dt*factor, 1)   (simulation.rs:2644-2646)
-enum { TAIL_NONE = 0, TAIL_VEL = 1, TAIL_VX = 2, TAIL_HYBRID = 3 };
-
-// parameters of the stop rule (iisph_pressure_iterations, simulation.rs:1453-1479)
+// The stop rule, who takes the decision in this launch, and where it goes (sph_solve_rule.hpp).  (A slab rank's own totals are added up
+// by block 0 of the launch that packs the ghost exchange, k_pack_totals, or by the push transport's fused launch: rank_totals_block.)
 struct SolveP {
-    int residual_density;
-    float max_avg_error;
-    uint32_t max_iters;
-    int multi;   // slab decomposition (0: one context -- block 0 of sweep A reduces the partials and decides):
-                 // 1: block 0 only adds up this rank's totals (k_solver_totals, block 0 of k_pack_totals);
-                 // 2: the launch runs BEHIND the all-reduce of the totals that travelled with the ghost exchange: its block 0 takes the
-                 //    decision from them (solver_decide_multi) -- the place and the protocol of the one-context form, so sweep B and the
-                 //    tail read one flag whatever the transport;
-                 // 3: neither (the two launches of a split sweep A: k_solver_progress decides between them)
+    SolveRule rule;
+    SolveDecider decider;
     uint32_t* prog = nullptr;   // paced solve: mapped host word that receives every decision (SweepArgs::prog_host), else nullptr
     uint32_t epoch = 0;
     // slab decomposition over RCCL: the ranks' totals arrive as an all-gather (one row per rank, tot_table[8 j ..]) in the iteration's
@@ -1638,7 +1624,7 @@ struct SolveP {
     const double* tot_table = nullptr;
     int tot_nr = 0, tot_self = 0;
 };
-// element k of the ranks' summed totals (solver_reduce_decide's layout)
+// element k of the ranks' summed totals (rank_totals_block's layout, sph_device.h)
 __device__ __forceinline__ double solver_total(const double* __restrict__ tot, const SolveP& q, int k)
 {
     if (!q.tot_table) return tot[k];
@@ -1646,66 +1632,49 @@ __device__ __forceinline__ double solver_total(const double* __restrict__ tot, c
     for (int j = 0; j < q.tot_nr; j++) s += j == q.tot_self ? tot[k] : q.tot_table[8 * j + k];
     return s;
 }
-static SolveP solve_params(const SweepArgs& a, int residual_density, float max_avg_error, uint32_t max_iters, int multi, bool progress)
+static SolveP solve_params(const SweepArgs& a, const SolveRule& rule, SolveDecider decider)
 {
-    SolveP q{residual_density, max_avg_error, max_iters, multi, progress ? a.prog_host : nullptr, a.prog_epoch};
+    SolveP q{rule, decider, decider != DECIDE_NOT_HERE ? a.prog_host : nullptr, a.prog_epoch};   // (only a launch that decides publishes the progress)
     q.tot_table = a.tot_table;
     q.tot_nr = a.tot_nr;
     q.tot_self = a.tot_self;
     return q;
 }
 
-// stopping rule of iisph_pressure_iterations (simulation.rs:1453-1479) for iteration `iter`
-__device__ __forceinline__ bool solver_stop_rule(uint32_t normal, float sum_err, int iter, const SolveP& q, float rest_density, float dt)
-{
-    const float avg = normal > 0 ? sum_err / (float)normal : __uint_as_float(0x7fc00000u);
-    bool stop;
-    if (q.residual_density) stop = normal == 0 || (fabsf(avg / rest_density) < q.max_avg_error && iter > 1);
-    else stop = normal == 0 || (fabsf(avg) < q.max_avg_error / dt && iter > 1);
-    if (!stop && (uint32_t)iter == q.max_iters) stop = true;
-    return stop;
-}
-
-// Slab decomposition: the ranks' totals of iteration `iter` (tot[0..5], all-reduced behind sweep A(iter + 1)) -> the decision,
-// evaluated by whoever needs it (every block of sweep B(iter + 1), k_solver_decide before a solve's tail).  tot[5] counts the
-// ranks whose device-side guards fired: the solve then ends on every rank together (ctrl->peer_error) instead of leaving the
-// others in a collective.  `publish`: this thread also writes the control block.
-__device__ __forceinline__ bool solver_decide_multi(const double* __restrict__ tot, SolverCtrl* ctrl, int iter, const SolveP& q, float rest_density, float dt,
-                                                    bool publish)
+// Slab decomposition: the ranks' totals of iteration `iter` (tot[0..5]: rank_totals_block's layout, all-reduced with the ghost
+// exchange in front of sweep A(iter + 1)) -> the decision, by thread 0 of that sweep's block 0 or of k_solver_progress.  tot[5] counts
+// the ranks whose device-side guards fired: the solve then ends on every rank together (ctrl->peer_error) instead of leaving the
+// others in a collective.
+__device__ __forceinline__ void solver_decide_multi(const double* __restrict__ tot, SolverCtrl* ctrl, int iter, const SolveP& q, float rest_density, float dt)
 {
     const uint32_t slot = (uint32_t)(iter + 1) & 1u;
     if (ctrl->slot_done[iter & 1] != 0u) {   // decided earlier: hand the flag on (the totals are stale)
-        if (publish) {
-            ctrl->slot_done[slot] = 1u;
-            if (q.prog) *(volatile uint32_t*)q.prog = (q.epoch << 16) | 0x8000u | ((uint32_t)iter & 0x7fffu);
-        }
-        return true;
+        ctrl->slot_done[slot] = 1u;
+        if (q.prog) *(volatile uint32_t*)q.prog = prog_word(q.epoch, true, (uint32_t)iter);
+        return;
     }
     const uint32_t normal = (uint32_t)solver_total(tot, q, 0);
     const float sum_err = (float)solver_total(tot, q, 3);
     const bool failed = solver_total(tot, q, 5) > 0.0;
-    const bool stop = failed || solver_stop_rule(normal, sum_err, iter, q, rest_density, dt);
-    if (publish) {
-        ctrl->normal = normal;
-        ctrl->singular = (uint32_t)solver_total(tot, q, 1);
-        ctrl->negative = (uint32_t)solver_total(tot, q, 2);
-        ctrl->sum_err = sum_err;
-        ctrl->max_err = (float)solver_total(tot, q, 4);
-        ctrl->iters = (uint32_t)iter;
-        ctrl->cur = (uint32_t)((iter + 1) & 1);
-        ctrl->slot_done[slot] = stop ? 1u : 0u;
-        if (failed) ctrl->peer_error = 1u;
-        if (stop) ctrl->done = 1u;
-        // paced solve: the host learns of the decision while the launch that took it still sweeps
-        if (q.prog) *(volatile uint32_t*)q.prog = (q.epoch << 16) | (stop ? 0x8000u : 0u) | ((uint32_t)iter & 0x7fffu);
-    }
-    return stop;
+    const bool stop = failed || solver_stop_rule(normal, sum_err, iter, q.rule, rest_density, dt);
+    ctrl->normal = normal;
+    ctrl->singular = (uint32_t)solver_total(tot, q, 1);
+    ctrl->negative = (uint32_t)solver_total(tot, q, 2);
+    ctrl->sum_err = sum_err;
+    ctrl->max_err = (float)solver_total(tot, q, 4);
+    ctrl->iters = (uint32_t)iter;
+    ctrl->cur = (uint32_t)((iter + 1) & 1);
+    ctrl->slot_done[slot] = stop ? 1u : 0u;
+    if (failed) ctrl->peer_error = 1u;
+    if (stop) ctrl->done = 1u;
+    // paced solve: the host learns of the decision while the launch that took it still sweeps
+    if (q.prog) *(volatile uint32_t*)q.prog = prog_word(q.epoch, stop, (uint32_t)iter);
 }
 
 // PressureSolverStatistics of iteration `iter` from the per-block partials (fixed order: deterministic; the reference's rayon
 // tree order is not) and the stop rule of simulation.rs:1453-1479.  Called by ALL threads of one block.
-__device__ __forceinline__ void solver_reduce_decide(const SolverPartial* __restrict__ partials, uint32_t nparts, SolverCtrl* ctrl, double* __restrict__ tot,
-                                                     int iter, const SolveP& q, float rest_density, float dt, const DeviceStatus* status)
+__device__ __forceinline__ void solver_reduce_decide(const SolverPartial* __restrict__ partials, uint32_t nparts, SolverCtrl* ctrl, int iter, const SolveP& q,
+                                                     float rest_density, float dt)
 {
     __shared__ SolverPartial s_r[SWEEP_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1744,16 +1713,7 @@ __device__ __forceinline__ void solver_reduce_decide(const SolverPartial* __rest
         t.sum_err += s_r[k].sum_err;
         t.max_err = fmaxf(t.max_err, s_r[k].max_err);
     }
-    if (q.multi) {   // local totals (doubles, exact for the counts) -> all-reduce(sum) over the ranks -> k_solver_decide
-        tot[0] = (double)t.normal;
-        tot[1] = (double)t.singular;
-        tot[2] = (double)t.negative;
-        tot[3] = (double)t.sum_err;
-        tot[4] = (double)t.max_err;   // summed over the ranks: informational
-        tot[5] = status->error != 0u ? 1.0 : 0.0;   // a guard fired on this rank: every rank ends the solve (solver_decide_multi)
-        return;
-    }
-    const bool stop = solver_stop_rule(t.normal, t.sum_err, iter, q, rest_density, dt);
+    const bool stop = solver_stop_rule(t.normal, t.sum_err, iter, q.rule, rest_density, dt);
     ctrl->normal = t.normal;
     ctrl->singular = t.singular;
     ctrl->negative = t.negative;
@@ -1764,7 +1724,7 @@ __device__ __forceinline__ void solver_reduce_decide(const SolverPartial* __rest
     ctrl->slot_done[(iter + 1) & 1] = stop ? 1u : 0u;
     if (stop) ctrl->done = 1u;
     // paced solve: the host learns of the decision while this launch still sweeps (it queues the next iteration, or the tail)
-    if (q.prog) *(volatile uint32_t*)q.prog = (q.epoch << 16) | (stop ? 0x8000u : 0u) | ((uint32_t)iter & 0x7fffu);
+    if (q.prog) *(volatile uint32_t*)q.prog = prog_word(q.epoch, stop, (uint32_t)iter);
 }
 
 // Sweep A of iteration `iter` >= 1 reads pressure buffer iter & 1 -- and its block 0 first takes the stop decision of iteration
@@ -1814,15 +1774,15 @@ struct OpPressureAccel {
         if (gate && *gate == 0u) return true;
         if (iter < 0) return ctrl->done == 0u;
         if (ctrl->slot_done[(iter - 1) & 1] != 0u) {   // the solve ended before this launch: hand the flag on, leave
-            if (raw_block == 0u && threadIdx.x == 0 && (solve.multi == 0 || solve.multi == 2)) {
+            if (raw_block == 0u && threadIdx.x == 0 && solve.decider != DECIDE_NOT_HERE) {
                 ctrl->slot_done[iter & 1] = 1u;
-                if (solve.multi == 2 && solve.prog)   // (paced slabs: an unpaced head launch behind the end of the solve)
-                    *(volatile uint32_t*)solve.prog = (solve.epoch << 16) | 0x8000u | ((uint32_t)(iter - 1) & 0x7fffu);
+                if (solve.decider == DECIDE_FROM_TOTALS && solve.prog)   // (paced slabs: an unpaced head launch behind the end of the solve)
+                    *(volatile uint32_t*)solve.prog = prog_word(solve.epoch, true, (uint32_t)(iter - 1));
             }
             return true;
         }
-        if (raw_block == 0u && solve.multi <= 1) solver_reduce_decide(partials, nparts, ctrl, tot, iter - 1, solve, sp.rest_density, sp.dt, status);
-        if (raw_block == 0u && solve.multi == 2 && threadIdx.x == 0) solver_decide_multi(tot, ctrl, iter - 1, solve, sp.rest_density, sp.dt, true);
+        if (raw_block == 0u && solve.decider == DECIDE_FROM_PARTIALS) solver_reduce_decide(partials, nparts, ctrl, iter - 1, solve, sp.rest_density, sp.dt);
+        if (raw_block == 0u && solve.decider == DECIDE_FROM_TOTALS && threadIdx.x == 0) solver_decide_multi(tot, ctrl, iter - 1, solve, sp.rest_density, sp.dt);
         return false;
     }
     __device__ bool lane_skip(uint32_t) const { return false; }
@@ -1944,17 +1904,14 @@ struct OpPressureAccelU : OpPressureAccel<MathT> {
 // The integrating tails know the positions and velocities the NEXT step starts from: they also reduce that step's header
 // (bounding box, h range, CFL term -- what k_header computes) per block, so the next step starts without the header kernels
 // and without the host wait behind them (hdr_partials == nullptr: not wanted).
-__global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, int tail, float dt, float vfactor, const float4* __restrict__ pm, float4* __restrict__ pm_out,
+__global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, SolveTail tail, float dt, float vfactor, const float4* __restrict__ pm, float4* __restrict__ pm_out,
                                                       float2* __restrict__ vel, const float4* __restrict__ pacc, const uint32_t* __restrict__ orig,
                                                       const uint8_t* __restrict__ owned, const SolverCtrl* __restrict__ ctrl, HeaderOut* __restrict__ hdr_partials,
-                                                      DeviceStatus* status, const uint32_t* __restrict__ gate, const double* __restrict__ tot,
-                                                      int decide_iter, SolveP solve, float rest_density, SolverCtrl* __restrict__ handoff_host,
+                                                      DeviceStatus* status, const uint32_t* __restrict__ gate, SolverCtrl* __restrict__ handoff_host,
                                                       uint32_t* __restrict__ gate_out, IncClassifyP inc, float4* __restrict__ xv)
 {
     if (gate && *gate == 0u) return;
     const bool b0t0 = blockIdx.x == 0 && threadIdx.x == 0;
-    (void)decide_iter;
-    (void)tot;
     const bool done = ctrl->done != 0u;   // (the decision was taken by the last sweep A's block 0, or the launch that stood in for it)
     // chained solves: this is the FIRST solve's tail -- hand its control block to the host and open (or keep shut) the gate of
     // the second solve's launches (k_solver_handoff's job; the next kernel starts after every block of this one has finished)
@@ -2032,8 +1989,8 @@ __global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, int tail, float
 // Op: relaxed-Jacobi pressure update (sweep B)
 //   iisph_single_pressure_iteration    simulation.rs:1241-1319
 //   a_ii >= 0 pre-check                simulation.rs:1390-1403 (done here at iteration 0)
-// Per-particle residual class goes to stat[] (normal: the error; singular / negative: tagged NaNs),
-// reduced in fixed particle order by k_solver_reduce.
+// Per-particle residual class and error go into the block's partial (solver_block_partial), reduced in a fixed order by whoever
+// takes the iteration's stop decision.
 // ------------------------------------------------------------------------------------------------
 template <class MathT>
 struct OpJacobi {
@@ -3002,15 +2959,6 @@ __global__ __launch_bounds__(256) void k_classify(uint32_t n, const float4* __re
     size_class[i] = cls;
 }
 
-// ------------------------------------------------------------------------------------------------
-// stop decision of a slab decomposition: the ranks' totals of iteration `iter` (solver_reduce_decide, multi) were all-reduced
-// (RCCL, in stream); every rank takes the same decision here (stopping rule of iisph_pressure_iterations, simulation.rs:1453-1479)
-// ------------------------------------------------------------------------------------------------
-__global__ void k_solver_decide(const double* __restrict__ tot, SolverCtrl* ctrl, int iter, SolveP q, float rest_density, float dt, const uint32_t* __restrict__ gate)
-{
-    if (gate && *gate == 0u) return;   // chained solves: the solve before this one has not ended
-    if (threadIdx.x == 0) solver_decide_multi(tot, ctrl, iter, q, rest_density, dt, true);
-}
 // an empty slab's control block at the start of a (possibly gated) solve
 __global__ void k_ctrl_reset(SolverCtrl* ctrl, const uint32_t* __restrict__ gate)
 {
@@ -3019,17 +2967,17 @@ __global__ void k_ctrl_reset(SolverCtrl* ctrl, const uint32_t* __restrict__ gate
 }
 // slab decomposition: the decision on iteration `iter` (and a paced solve's progress word) by a launch of its own, right behind the
 // all-reduce of its totals -- where no sweep A's block 0 can take it: a split sweep A (its interior runs BESIDE the all-reduce, its
-// edge launch only after the interior), an empty slab (no sweep at all)
+// edge launch only after the interior), an empty slab (no sweep at all).  Every rank takes the same decision from the same totals.
 __global__ void k_solver_progress(const double* __restrict__ tot, SolverCtrl* ctrl, int iter, SolveP q, float rest_density, float dt, const uint32_t* __restrict__ gate)
 {
-    if (gate && *gate == 0u) return;
-    if (threadIdx.x == 0) solver_decide_multi(tot, ctrl, iter, q, rest_density, dt, true);
+    if (gate && *gate == 0u) return;   // chained solves: the solve before this one has not ended
+    if (threadIdx.x == 0) solver_decide_multi(tot, ctrl, iter, q, rest_density, dt);
 }
-void launch_solver_progress(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters)
+void launch_solver_progress(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule)
 {
     ProfScope ps(prof, "solver_progress", s);
-    hipLaunchKernelGGL(k_solver_progress, dim3(1), dim3(64), 0, s, a.solver_tot, a.ctrl, iter, solve_params(a, residual_density, max_avg_error, max_iters, 2, true),
-                       a.sp.rest_density, a.sp.dt, a.gate);
+    hipLaunchKernelGGL(k_solver_progress, dim3(1), dim3(64), 0, s, a.solver_tot, a.ctrl, iter, solve_params(a, rule, DECIDE_FROM_TOTALS), a.sp.rest_density,
+                       a.sp.dt, a.gate);
 }
 void launch_ctrl_reset(hipStream_t s, SolverCtrl* ctrl, const uint32_t* gate) { hipLaunchKernelGGL(k_ctrl_reset, dim3(1), dim3(64), 0, s, ctrl, gate); }
 
@@ -3213,57 +3161,13 @@ struct OpFuse {
     }
 };
 
-// HybridDFSPH after the divergence solve: v += dt * a^p   (simulation.rs:2547-2560)
-__global__ __launch_bounds__(256) void k_vel_add_pacc(uint32_t n, float dt, float2* __restrict__ vel, const float4* __restrict__ pacc,
-                                                       const uint32_t* __restrict__ orig, DeviceStatus* status)
-{
-    uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float2 v = vel[i];
-    const float4 rec = pacc[i];
-    const float2 a = make_float2(rec.z, rec.w);
-    v.x += dt * a.x;
-    v.y += dt * a.y;
-    vel[i] = v;
-    if (!isfinite(v.x) || !isfinite(v.y)) raise_error(status, SPH_ERR_VELOCITY_NOT_FINITE, orig[i]);
-}
-
-// mode 0: v += dt a^p ; x += dt v                     (IISPH / OnlyDivergence, simulation.rs:2433-2445, 2486-2499)
-// mode 1: x += dt v + dt^2 a^p ; v += dt a^p * min(dt*factor, 1)   (HybridDFSPH, simulation.rs:2644-2646)
-__global__ __launch_bounds__(256) void k_integrate(uint32_t n, float dt, float vfactor, int mode, const float4* __restrict__ pm,
-                                                    float4* __restrict__ pm_out, float2* __restrict__ vel, const float4* __restrict__ pacc,
-                                                    const uint32_t* __restrict__ orig, DeviceStatus* status)
-{
-    uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float4 p = pm[i];
-    float2 v = vel[i];
-    const float4 rec = pacc[i];
-    const float2 a = make_float2(rec.z, rec.w);
-    if (mode == 0) {
-        v.x += dt * a.x;
-        v.y += dt * a.y;
-        p.x += dt * v.x;
-        p.y += dt * v.y;
-        if (!isfinite(v.x) || !isfinite(v.y)) raise_error(status, SPH_ERR_VELOCITY_NOT_FINITE, orig[i]);
-    } else {
-        p.x += dt * v.x + dt * dt * a.x;
-        p.y += dt * v.y + dt * dt * a.y;
-        v.x += dt * a.x * vfactor;
-        v.y += dt * a.y * vfactor;
-        if (!isfinite(p.x) || !isfinite(p.y)) raise_error(status, SPH_ERR_POSITION_NOT_FINITE, orig[i]);
-    }
-    pm_out[i] = p;
-    vel[i] = v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static SweepCommon common_of(const SweepArgs& a, bool ext)
 {
     return SweepCommon{a.g, ext ? a.t_ext : a.t, a.n, (a.n + SWEEP_THREADS - 1) / SWEEP_THREADS, a.cell_start, ext ? a.nl_ext : a.nl, ext ? a.nlx_ext : a.nlx, a.owned, a.ring1,
-                       0, nullptr, nullptr, nullptr, 0u, 0u, ext ? nullptr : a.nloff, ext ? nullptr : a.nlh, ext ? nullptr : a.nloff_out, ext ? nullptr : a.nlh_out, nullptr};
+                       PART_WHOLE, nullptr, nullptr, nullptr, 0u, 0u, ext ? nullptr : a.nloff, ext ? nullptr : a.nlh, ext ? nullptr : a.nloff_out, ext ? nullptr : a.nlh_out, nullptr};
 }
 
 // SPH_TILE: bit 0 = the BUILD sweep (density), bit 1 = the replay sweeps through the LDS-staged form (k_sweep_tile) in
@@ -3316,7 +3220,7 @@ template <class Op, bool BUILD>
 static void launch_sweep(hipStream_t s, const SweepArgs& a, const Op& op)
 {
     if (a.n == 0) return;
-    if (a.part) {   // one of the two launches of a split sweep (slab decomposition, sph_step.hip)
+    if (a.part != PART_WHOLE) {   // one of the two launches of a split sweep (slab decomposition, sph_step.hip)
         SweepCommon c = common_of(a, Op::EXTENDED);
         c.part = a.part;
         c.edge = a.edge;
@@ -3324,7 +3228,7 @@ static void launch_sweep(hipStream_t s, const SweepArgs& a, const Op& op)
         c.elist_b = a.elist_b;
         c.n_ea = a.n_ea;
         c.n_eb = a.n_eb;
-        if (a.part == 2) c.nblocks = (a.n_ea + a.n_eb + SWEEP_THREADS - 1) / SWEEP_THREADS;
+        if (a.part == PART_EDGE) c.nblocks = (a.n_ea + a.n_eb + SWEEP_THREADS - 1) / SWEEP_THREADS;
         if (c.nblocks == 0) c.nblocks = 1;   // (the launch's prologue still runs)
         if constexpr (!BUILD && OpOff16<Op>::value) {
             if (a.nloff) {
@@ -3490,18 +3394,18 @@ using OpSourcePlain = OpSource<M, false>;
 template <class M>
 using OpSourceOmega = OpSource<M, true>;
 
-void launch_source_term(hipStream_t s, Profiler* prof, const SweepArgs& a, int kind, int residual_density)
+void launch_source_term(hipStream_t s, Profiler* prof, const SweepArgs& a, SourceKind kind, int residual_density)
 {
     ProfScope ps(prof, "source_term", s, true);
     float4* rec1 = solve_on_records(a) ? a.rec1 : nullptr;
-    if (source_term_on_records(a) && a.xv_ok && (kind == 0 || kind == 1)) {
+    if (source_term_on_records(a) && a.xv_ok && (kind == SRC_DIVERGENCE || kind == SRC_FULL)) {
         OpSourceU<MathUniform> op{{uniform_math(a.h_uniform), a.pm, a.orig, a.rho, a.mrho, a.vel, a.lam_grad, a.aii, a.src, a.p1, a.pt1, rec1, a.dens_err,
                                    (SolverPartial*)a.partials, a.ctrl, a.status, a.sp, kind, residual_density, nullptr, nullptr, a.gate},
                                   a.xv};
         launch_sweep<OpSourceU<MathUniform>, false>(s, a, op);
         return;
     }
-    if (kind == 3) {
+    if (kind == SRC_FULL_OMEGA) {
         SPH_DISPATCH(OpSourceOmega, false, a.pm, a.orig, a.rho, a.mrho, a.vel, a.lam_grad, a.aii, a.src, a.p1, a.pt1, rec1, a.dens_err,
                      (SolverPartial*)a.partials, a.ctrl, a.status, a.sp, kind, residual_density, a.omega, a.size_class, a.gate)
         return;
@@ -3510,15 +3414,14 @@ void launch_source_term(hipStream_t s, Profiler* prof, const SweepArgs& a, int k
                  (SolverPartial*)a.partials, a.ctrl, a.status, a.sp, kind, residual_density, nullptr, nullptr, a.gate)
 }
 
-void launch_pressure_accel(hipStream_t s, Profiler* prof, const SweepArgs& a0, int iter, int residual_density, float max_avg_error, uint32_t max_iters, int multi,
-                           int part)
+void launch_pressure_accel(hipStream_t s, Profiler* prof, const SweepArgs& a0, int iter, const SolveRule& rule, SolveDecider decider, SweepPart part)
 {
-    ProfScope ps(prof, part == 2 ? "pressure_accel_edge" : "pressure_accel", s, true);
+    ProfScope ps(prof, part == PART_EDGE ? "pressure_accel_edge" : "pressure_accel", s, true);
     SweepArgs a = a0;
     a.part = part;
-    // (split sweep: neither launch publishes the paced solve's progress -- the interior runs BESIDE the all-reduce of the totals, the
-    //  edge launch only after the interior: the step driver queues launch_solver_progress right behind the all-reduce instead)
-    const SolveP q = solve_params(a, residual_density, max_avg_error, max_iters, part ? 3 : multi, part == 0);   // (part != 0: launch_solver_progress decides)
+    // (split sweep, DECIDE_NOT_HERE: neither launch decides or publishes the paced solve's progress -- the interior runs BESIDE the all-reduce
+    //  of the totals, the edge launch only after the interior: the step driver queues launch_solver_progress right behind the all-reduce)
+    const SolveP q = solve_params(a, rule, decider);
     if (solve_on_records(a) && iter >= 1) {   // (iter < 0: IISPH2's extra sweep -- never on records)
         OpPressureAccelU<MathUniform> op{{uniform_math(a.h_uniform), a.pm, a.orig, a.rho, a.p0, a.p1, a.pt0, a.pt1, a.lam_grad, a.pacc, a.ctrl,
                                           (const SolverPartial*)a.partials, solver_reduce_blocks(a.n), a.solver_tot, a.status, a.sp, q, iter, a.owned, a.gate},
@@ -3530,27 +3433,10 @@ void launch_pressure_accel(hipStream_t s, Profiler* prof, const SweepArgs& a0, i
                  solver_reduce_blocks(a.n), a.solver_tot, a.status, a.sp, q, iter, a.owned, a.gate)
 }
 
-// Split sweep A (slab decomposition with neighbours): this rank's totals of iteration `iter` -- what block 0 of the unsplit sweep
-// A(iter + 1) adds up -- by a launch of its own on the stream of the collectives, so that the all-reduce runs under the sweep.
-__global__ __launch_bounds__(SWEEP_THREADS) void k_solver_totals(const SolverPartial* __restrict__ partials, uint32_t nparts, SolverCtrl* ctrl,
-                                                                 double* __restrict__ tot, int iter, SolveP q, float rest_density, float dt,
-                                                                 const DeviceStatus* status, const uint32_t* __restrict__ gate)
-{
-    if (gate && *gate == 0u) return;
-    if (ctrl->slot_done[iter & 1] != 0u) return;   // the solve ended before: the totals are stale, nobody reads them (solver_decide_multi)
-    solver_reduce_decide(partials, nparts, ctrl, tot, iter, q, rest_density, dt, status);
-}
-void launch_solver_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters)
-{
-    ProfScope ps(prof, "solver_totals", s);
-    hipLaunchKernelGGL(k_solver_totals, dim3(1), dim3(SWEEP_THREADS), 0, s, (const SolverPartial*)a.partials, solver_reduce_blocks(a.n), a.ctrl, a.solver_tot, iter,
-                       solve_params(a, residual_density, max_avg_error, max_iters, 1, false), a.sp.rest_density, a.sp.dt, a.status, a.gate);
-}
-
-// The same totals as block 0 of the launch that packs the halo members' values for the iteration's ghost exchange (slab
-// decomposition): both wait for sweep B, both precede the exchange -- one launch instead of two (a kernel boundary is ~4 us, and an
-// iteration of 1M particles per rank is ~45 us of sweeps).  Blocks 1.. pack: entries [0, cnt0) go to the left neighbour's staging
-// buffer, [cnt0, cnt0 + cnt1) to the right one's (k_pack_field of sph_slabs.hip).
+// Slab decomposition: this rank's totals of iteration `iter` -- what the ranks all-reduce for the stop decision -- by block 0 of the
+// launch that packs the halo members' values for the iteration's ghost exchange: both wait for sweep B, both precede the exchange --
+// one launch instead of two (a kernel boundary is ~4 us, and an iteration of 1M particles per rank is ~45 us of sweeps).  Blocks 1..
+// pack: entries [0, cnt0) go to the left neighbour's staging buffer, [cnt0, cnt0 + cnt1) to the right one's (k_pack_field of sph_slabs.hip).
 static_assert(RANK_TOTALS_THREADS == 1024, "k_pack_totals' block 0 is rank_totals_block's workgroup");
 #define PACK_THREADS 1024   // block 0 adds up one partial per 256 particles: 32768 of them at 8M particles per rank -- on the iteration's critical path
 __global__ __launch_bounds__(PACK_THREADS) void k_pack_totals(const SolverPartial* __restrict__ partials, uint32_t nparts, SolverCtrl* ctrl, double* __restrict__ tot,
@@ -3561,7 +3447,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_totals(const SolverPartia
 {
     if (blockIdx.x == 0) {
         if (gate && *gate == 0u) return;
-        if (ctrl->slot_done[iter & 1] != 0u) return;   // (see k_solver_totals)
+        if (ctrl->slot_done[iter & 1] != 0u) return;   // the solve ended before: the totals are stale, nobody reads them (solver_decide_multi)
         rank_totals_block(partials, nparts, tot, &status->error);   // (sph_device.h: the same reduction the push transport's fused launch runs)
         return;
     }
@@ -3571,26 +3457,21 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_totals(const SolverPartia
     float* out = k < cnt0 ? out0 + (size_t)k * words : out1 + (size_t)(k - cnt0) * words;
     for (int w = 0; w < words; w++) out[w] = field[(size_t)i * stride + off + w];
 }
-void launch_pack_and_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters,
-                            const uint32_t* src_idx, uint32_t cnt0, uint32_t cnt1, int words, int stride, int off, const float* field, float* out0, float* out1)
+void launch_pack_and_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const uint32_t* src_idx, uint32_t cnt0, uint32_t cnt1, int words, int stride,
+                            int off, const float* field, float* out0, float* out1)
 {
-    (void)residual_density;
-    (void)max_avg_error;
-    (void)max_iters;
     ProfScope ps(prof, "ghost_pack_totals", s);
     const uint32_t nb = 1u + (cnt0 + cnt1 + PACK_THREADS - 1u) / PACK_THREADS;
     hipLaunchKernelGGL(k_pack_totals, dim3(nb), dim3(PACK_THREADS), 0, s, (const SolverPartial*)a.partials, solver_reduce_blocks(a.n), a.ctrl, a.solver_tot, iter,
                        a.sp.rest_density, a.sp.dt, a.status, a.gate, src_idx, cnt0, cnt1, words, stride, off, field, out0, out1);
 }
 
-void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, int tail, float4* pm_out, int decide_iter, int residual_density,
-                        float max_avg_error, uint32_t max_iters, SolverCtrl* handoff_host, uint32_t* gate_out)
+void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, SolveTail tail, float4* pm_out, SolverCtrl* handoff_host, uint32_t* gate_out)
 {
     ProfScope ps(prof, "solver_tail", s);
     if (a.n && tail != TAIL_NONE)
         hipLaunchKernelGGL(k_solver_tail, dim3((a.n + 255) / 256), dim3(256), 0, s, a.n, tail, a.sp.dt, a.sp.hyb_vfactor, a.pm, pm_out, a.vel, a.pacc, a.orig,
-                           a.owned, a.ctrl, tail >= TAIL_VX ? a.hdr_partials : nullptr, a.status, a.gate, a.solver_tot, decide_iter,
-                           solve_params(a, residual_density, max_avg_error, max_iters, 1, false), a.sp.rest_density, handoff_host, gate_out,
+                           a.owned, a.ctrl, tail >= TAIL_VX ? a.hdr_partials : nullptr, a.status, a.gate, handoff_host, gate_out,
                            tail >= TAIL_VX ? a.inc : IncClassifyP{}, tail == TAIL_VEL && source_term_on_records(a) ? a.xv : nullptr);
 }
 
@@ -3611,13 +3492,14 @@ void launch_solver_handoff(hipStream_t s, Profiler* prof, SolverCtrl* ctrl, Solv
     hipLaunchKernelGGL(k_solver_handoff, dim3(1), dim3(64), 0, s, ctrl, saved_host, gate);
 }
 
-void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error, uint32_t max_iters, int multi)
+void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule)
 {
     ProfScope ps(prof, "jacobi_update", s, true);
     const float* pin = (iter & 1) ? a.p1 : a.p0;
     float* pout = (iter & 1) ? a.p0 : a.p1;
     float* ptout = (iter & 1) ? a.pt0 : a.pt1;
-    const SolveP q = solve_params(a, residual_density, max_avg_error, max_iters, multi, false);
+    const int residual_density = rule.residual_density;
+    const SolveP q = solve_params(a, rule, DECIDE_NOT_HERE);   // (sweep B decides nothing: it reads the flag sweep A(iter) left)
     if (jacobi_on_records(a)) {
         float4* recout = solve_on_records(a) ? ((iter & 1) ? a.rec0 : a.rec1) : nullptr;
         OpJacobiU<MathUniform> op{{uniform_math(a.h_uniform), a.pm, a.orig, a.rho, a.mrho, a.pacc, a.lam_grad, a.aii, a.src, pin, pout, ptout, recout, a.dens_err,
@@ -3627,27 +3509,6 @@ void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int
     }
     SPH_DISPATCH(OpJacobi, false, a.pm, a.orig, a.rho, a.mrho, a.pacc, a.lam_grad, a.aii, a.src, pin, pout, ptout, (float4*)nullptr, a.dens_err, (SolverPartial*)a.partials, a.ctrl,
                  a.status, a.sp, iter, residual_density, q, a.solver_tot, a.gate)
-}
-
-void launch_solver_decide(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, int residual_density, float max_avg_error,
-                          uint32_t max_iters)
-{
-    ProfScope ps(prof, "solver_decide", s);
-    hipLaunchKernelGGL(k_solver_decide, dim3(1), dim3(64), 0, s, a.solver_tot, a.ctrl, iter, solve_params(a, residual_density, max_avg_error, max_iters, 1, false),
-                       a.sp.rest_density, a.sp.dt, a.gate);
-}
-
-void launch_vel_add_pacc(hipStream_t s, Profiler* prof, const SweepArgs& a)
-{
-    ProfScope ps(prof, "vel_add_pacc", s);
-    hipLaunchKernelGGL(k_vel_add_pacc, dim3((a.n + 255) / 256), dim3(256), 0, s, a.n, a.sp.dt, a.vel, a.pacc, a.orig, a.status);
-}
-
-void launch_integrate(hipStream_t s, Profiler* prof, const SweepArgs& a, float4* pm_out, int mode)
-{
-    ProfScope ps(prof, "integrate", s);
-    hipLaunchKernelGGL(k_integrate, dim3((a.n + 255) / 256), dim3(256), 0, s, a.n, a.sp.dt, a.sp.hyb_vfactor, mode, a.pm, pm_out, a.vel, a.pacc,
-                       a.orig, a.status);
 }
 
 // ---- level estimation (simulation.rs:862-927, 803-857; adaptivity/mod.rs:32-59) ---------------------------------
