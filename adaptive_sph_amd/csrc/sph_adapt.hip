@@ -712,12 +712,14 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
 }
 
 // The decisions of a COMPACT problem (include/sph_slab_partner_problem.h): k participants by ascending global id, a partner named by its
-// compact id.
+// compact id.  The three arrays are the host's, the same on every rank; or (on_device, sph_slab_partner_search.hip) every member holds them
+// on its own device -- slab_sol_ids / slab_sol_partner / slab_sol_counter, checked where they were made -- and the pointers here are null.
 struct SlabCompact {
     uint64_t k;
     const uint32_t* ids;
     const uint32_t* partner_c;
     const uint16_t* counter_c;
+    bool on_device = false;
 };
 // merge_partner / merge_counter of the whole vector on a member's device: copied from the host's arrays, or (cd) expanded from the k
 // decisions (prob_expand, sph_partner_problem.hip) -- 10 B per participant go up instead of 6 B per particle.  Everything behind this
@@ -725,6 +727,9 @@ struct SlabCompact {
 static int slab_decisions_to_device(sph_ctx* c, hipStream_t s, uint32_t n_global, const uint32_t* partner, const uint16_t* counter, const SlabCompact* cd,
                                     uint32_t* d_partner, uint16_t* d_counter, TmpBuf& up_ids, TmpBuf& up_partner, TmpBuf& up_counter)
 {
+    if (cd && cd->on_device)   // (device arrays: nothing is staged)
+        return prob_expand(c, "slab_problem_expand", n_global, (uint32_t)cd->k, c->slab_sol_ids.as<uint32_t>(), c->slab_sol_partner.as<uint32_t>(),
+                           c->slab_sol_counter.as<uint16_t>(), d_partner, d_counter);
     if (cd) return prob_expand(c, "slab_problem_expand", n_global, (uint32_t)cd->k, cd->ids, cd->partner_c, cd->counter_c, d_partner, d_counter, ExpandStage{&up_ids, &up_partner, &up_counter});
     HIPCHK(c, hipMemcpyAsync(d_partner, partner, (size_t)n_global * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_counter, counter, (size_t)n_global * 2, hipMemcpyHostToDevice, s));
@@ -755,7 +760,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
         if ((rc = G.comm->allreduce_sum_u32(G, rows))) return rc;
         n_global = rows[0][0];
     }
-    if (cd && cd->k && cd->ids[cd->k - 1] >= n_global) {   // (ascending: the last id is the largest.  Every rank holds the same ids and the same sum)
+    if (cd && !cd->on_device && cd->k && cd->ids[cd->k - 1] >= n_global) {   // (ascending: the last id is the largest.  Every rank holds the same ids and the same sum)
         if (together) *together = true;
         return G.m[0]->fail(SPH_ERR_INVALID_ARGUMENT, "ids holds %u, the vector has %u particles", cd->ids[cd->k - 1], n_global);
     }
@@ -950,7 +955,7 @@ static int slab_apply_compact_rank(sph_ctx* c, int op, const char* what, const s
     if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (a plain context takes sph_download_partner_problem and sph_share_particles_compact / sph_merge_particles_compact)", what);
     if (c->poisoned) return c->refuse_poisoned();
     if (int rc = slab_compact_check(c, what, p, ap, k, ids, partner_c, counter_c)) return rc;
-    const SlabCompact cd{k, ids, partner_c, counter_c};
+    const SlabCompact cd{k, ids, partner_c, counter_c, false};
     return slab_adapt_rank(c, op, p, ap, nullptr, nullptr, &cd);
 }
 
@@ -980,7 +985,13 @@ extern "C" int sph_group_adapt_compact(sph_ctx** ctxs, int n, int op, const sph_
     for (auto c : G.m)
         if (c->poisoned) return c->refuse_poisoned();
     if (int rc = slab_compact_check(ctxs[0], "sph_group_adapt_compact", p, ap, k, ids, partner_c, counter_c)) return rc;
-    const SlabCompact cd{k, ids, partner_c, counter_c};
+    const SlabCompact cd{k, ids, partner_c, counter_c, false};
+    return slab_adapt(G, op, p, ap, nullptr, nullptr, &cd);
+}
+
+int slab_adapt_device(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, uint64_t k)
+{
+    const SlabCompact cd{k, nullptr, nullptr, nullptr, true};
     return slab_adapt(G, op, p, ap, nullptr, nullptr, &cd);
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "sph_context.hpp"
+#include "sph_partner_search.h"   // sph_partner_search_info
 
 struct CandP {
     int share;             // kind == 0
@@ -115,3 +116,19 @@ struct Group;
 int slab_cand_refuse(sph_ctx* c, const char* what);
 int slab_cand_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_rows, uint64_t* n_indices, bool* together);
 void slab_cand_mark_launch(sph_ctx* c, const CandP& q, uint32_t* flag);
+
+// sph_partner_search.hip, shared with sph_slab_partner_search.hip: the exact-schedule search on the compact problem that sits in c's
+// prob.off[K + 1] / prob_idx[tot] / prob.mass / prob.level / prob.cls (K > 0), on c's stream and work arrays -- the writers CSR, first,
+// the resident and wide rounds, validate.  The decisions land in c->sol_partner / c->sol_counter.  A HIP failure is the return value;
+// what the search itself found wrong (ps_error_text) is out->error, with SPH_OK returned.  *info is filled when neither happened.
+struct PsOutcome {
+    uint32_t error, undecided, rounds;
+};
+int ps_solve(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t wide_threshold, uint32_t K, uint32_t tot, sph_partner_search_info* info,
+             PsOutcome* out);
+const char* ps_error_text(uint32_t e);
+// sph_slab_partner_problem.hip: the collective prepare of sph_slab_partner_problem.h for the members of G (the three arrays: one entry per member)
+int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_part, uint64_t* n_owned, uint64_t* n_indices, bool* together);
+// sph_adapt.hip: slab_adapt (op 0 share, 1 merge) from the k decisions every member holds on its own device (slab_sol_ids /
+// slab_sol_partner / slab_sol_counter): the device form of SlabCompact
+int slab_adapt_device(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, uint64_t k);

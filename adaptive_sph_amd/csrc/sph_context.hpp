@@ -150,8 +150,20 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     uint32_t slab_prob_k = 0, slab_prob_ko = 0;
     ProbBufs slab_prob;
     DevBuf slab_prob_flag, slab_prob_rank;
-    std::array<DevBuf*, 13> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob.ids, &slab_prob.cls,
-                                                  &slab_prob.mass, &slab_prob.level, &slab_prob.pos, &slab_prob.h2, &slab_prob.off}; }
+    // sph_slab_partner_search.hip: the decisions of the GROUP's merged problem as every member holds them (slab_sol_k participants of kind
+    // slab_sol_kind: global ids ascending, partner in compact ids, counter), THE OPEN SOLUTION of the group on this member while its
+    // prepared problem is open and slab_sol_serial == slab_prob_serial (slab_prob_serial counts the problems prepared; 0 = no solution).
+    // The member that merged and solved (slab_sol_root) keeps the merged problem in prob / prob_idx -- a slab context has no other use
+    // for them -- with slab_sol_tot entries, and the merge's work arrays: the staged local problems, a flag and a rank word per global
+    // id, a seen byte and a row length per participant, the error word.
+    uint64_t slab_prob_serial = 0, slab_sol_serial = 0, slab_sol_tot = 0;
+    uint32_t slab_sol_k = 0;
+    int slab_sol_kind = 0, slab_sol_root = 0;
+    DevBuf slab_sol_ids, slab_sol_partner, slab_sol_counter;
+    DevBuf ss_stage, ss_flag, ss_rank, ss_seen, ss_rowlen, ss_err;
+    std::array<DevBuf*, 22> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob.ids, &slab_prob.cls,
+                                                  &slab_prob.mass, &slab_prob.level, &slab_prob.pos, &slab_prob.h2, &slab_prob.off, &slab_sol_ids, &slab_sol_partner,
+                                                  &slab_sol_counter, &ss_stage, &ss_flag, &ss_rank, &ss_seen, &ss_rowlen, &ss_err}; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];

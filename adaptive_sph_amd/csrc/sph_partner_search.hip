@@ -424,7 +424,7 @@ static bool solution_open(sph_ctx* c)
     return c->prob_open && c->sol_serial == c->prob_serial;
 }
 
-static const char* ps_error_text(uint32_t e)
+const char* ps_error_text(uint32_t e)
 {
     switch (e) {
     case PS_ERR_STUCK: return "no donor is ready while donors remain";
@@ -435,25 +435,13 @@ static const char* ps_error_text(uint32_t e)
     return "unknown error";
 }
 
-extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t wide_threshold, sph_partner_search_info* info)
+// The search on the compact problem in c's prob / prob_idx buffers (sph_candidates.hpp: ps_solve), for sph_find_partners_device on its own
+// context and for sph_group_find_partners_device on the root of a slab group.
+int ps_solve(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t wide_threshold, uint32_t K, uint32_t tot, sph_partner_search_info* info,
+             PsOutcome* out)
 {
-    const char* what = "sph_find_partners_device";
-    if (!c) return SPH_ERR_INVALID_ARGUMENT;
-    if (info) *info = sph_partner_search_info{};
-    c->prob_open = false;   // (this call replaces the open problem, or closes it)
-    if (!p || !ap || !info) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params, ap and info must be given", what);
-    if (int rc = cand_check_args(c, what, kind, p, ap)) return rc;
-    if (int rc = cand_refuse_common(c, what)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = cand_need_lists(c)) return rc;
+    *out = PsOutcome{0, 0, 0};
     hipStream_t s = c->stream;
-    uint32_t K = 0, tot = 0;
-    if (int rc = prob_build_on_device(c, kind, ap, what, nullptr, &K, &tot)) return rc;
-    if (K == 0) {
-        prob_open_problem(c, kind, 0);
-        c->sol_serial = c->prob_serial;
-        return SPH_OK;
-    }
     if (wide_threshold == 0) wide_threshold = PS_DEFAULT_WIDE_THRESHOLD;
     const size_t k = K, wtot = (size_t)tot + k;   // a writers entry per candidate entry and one per donor
     // words: woff[K + 1], cnt[K], hp[K], stamp_x[K], stamp_d[K], lists[5 K]
@@ -536,9 +524,8 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
         HIPCHK(c, hipStreamSynchronize(s));
         prog[3] = r.error;
     }
-    prob_open_problem(c, kind, K);   // (the problem itself is sound: the host may still solve it)
-    if (prog[3]) return c->fail(SPH_ERR_DEVICE, "%s: %s (K=%u, %u donors undecided after %u rounds)", what, ps_error_text(prog[3]), K, prog[0], prog[2]);
-    c->sol_serial = c->prob_serial;
+    *out = PsOutcome{prog[3], prog[0], prog[2]};
+    if (prog[3]) return SPH_OK;
     info->participants = K;
     info->candidates = tot;
     info->donors = r.donors;
@@ -546,6 +533,32 @@ extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* 
     info->rounds = r.rounds;
     info->max_frontier = r.max_frontier;
     info->wide_rounds = r.wide_rounds;
+    return SPH_OK;
+}
+
+extern "C" int sph_find_partners_device(sph_ctx* c, int kind, const sph_params* p, const sph_adapt_params* ap, uint32_t wide_threshold, sph_partner_search_info* info)
+{
+    const char* what = "sph_find_partners_device";
+    if (!c) return SPH_ERR_INVALID_ARGUMENT;
+    if (info) *info = sph_partner_search_info{};
+    c->prob_open = false;   // (this call replaces the open problem, or closes it)
+    if (!p || !ap || !info) return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: params, ap and info must be given", what);
+    if (int rc = cand_check_args(c, what, kind, p, ap)) return rc;
+    if (int rc = cand_refuse_common(c, what)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = cand_need_lists(c)) return rc;
+    uint32_t K = 0, tot = 0;
+    if (int rc = prob_build_on_device(c, kind, ap, what, nullptr, &K, &tot)) return rc;
+    if (K == 0) {
+        prob_open_problem(c, kind, 0);
+        c->sol_serial = c->prob_serial;
+        return SPH_OK;
+    }
+    PsOutcome o;
+    if (int rc = ps_solve(c, kind, p, ap, wide_threshold, K, tot, info, &o)) return rc;
+    prob_open_problem(c, kind, K);   // (the problem itself is sound: the host may still solve it)
+    if (o.error) return c->fail(SPH_ERR_DEVICE, "%s: %s (K=%u, %u donors undecided after %u rounds)", what, ps_error_text(o.error), K, o.undecided, o.rounds);
+    c->sol_serial = c->prob_serial;
     return SPH_OK;
 }
 

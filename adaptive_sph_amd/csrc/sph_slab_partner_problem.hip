@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_slab_prob_pack(uint32_t nt, uint32_t K,
     }
 }
 
-static int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_part, uint64_t* n_owned, uint64_t* n_indices, bool* together)
+int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_params* ap, uint64_t* n_part, uint64_t* n_owned, uint64_t* n_indices, bool* together)
 {
     const size_t nm = G.m.size();
     std::vector<uint64_t> rows(nm, 0), tots(nm, 0);
@@ -88,6 +88,7 @@ static int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_
             HIPCHK(c, hipStreamSynchronize(s));   // (the snapshot is complete before anybody changes the records it was packed from)
         }
         c->slab_prob_open = true;
+        c->slab_prob_serial++;   // (a solution of an earlier problem is not one of this problem: sph_slab_partner_search.hip)
         c->slab_prob_k = K;
         c->slab_prob_ko = Ko;
         n_part[i] = K;

@@ -348,7 +348,9 @@ def group_single_step_adaptivity(lib: ffi.SphLibrary, contexts: Sequence[ffi.Con
     return info
 
 
+C_INFO_BYTES = 48   # sizeof(sph_partner_search_info): what one device search brings down
 SLAB_EXPORTS = ("lists", "candidates", "compact")
+GROUP_SLAB_EXPORTS = SLAB_EXPORTS + ("device",)   # the in-process group form also solves on the device (include/sph_slab_partner_search.h)
 
 
 def _decide_compact(lib, kind: str, ids, fields, off_c, idx_c, P, dt: float):
@@ -396,13 +398,22 @@ def group_single_step_adaptivity_on_slabs(lib: ffi.SphLibrary, contexts: Sequenc
     decisions (sph_group_adapt_compact).  No particle ids, no field of the whole vector and no list comes down.  info["participants"]:
     the sum of K over the passes; ["bytes_down"]: 25 B per local participant (id, class, mass, level, position, h2), 4 B per offset of
     an owned participant's row (one more than there are), 4 B per candidate, 8 B per device sum; ["bytes_up"] (compact only): 10 B x K
-    per rank; ["passes"]: per search its kind, K and the ranks' (participants, owned participants, candidates)."""
+    per rank; ["passes"]: per search its kind, K and the ranks' (participants, owned participants, candidates).
+
+    "device" (include/sph_slab_partner_search.h; this in-process form only): the local problems are packed as for "compact", merged on
+    member 0's device, solved there in the search's exact parallel schedule and validated, the K decisions go to every member device
+    to device and every member applies its copy (sph_group_find_partners_device, sph_group_adapt_device): the same decisions, the
+    same state.  No problem comes down and no decision goes up: ["bytes_down"] counts the 48 B info struct per search and the 8 B
+    device sums, ["bytes_up"] is 0, ["bytes_between_devices"] what the members' buffers exchange with the root's -- 25 B per local
+    participant, 4 B per offset and per candidate towards the root, 10 B x K back to every member, the root's own copies not counted;
+    ["passes"]: per search its kind, K ("participants"), the ranks' local counts ("ranks"), rounds, max_frontier and wide_rounds."""
     from .adaptivity import adapt_params
     if P.support_length_estimation != "FromMass":
         raise ValueError("group_single_step_adaptivity_on_slabs: support_length_estimation must be FromMass")
-    if export not in SLAB_EXPORTS:
-        raise ValueError(f"group_single_step_adaptivity_on_slabs: export must be one of {SLAB_EXPORTS}, not {export!r}")
-    compact = export == "compact"
+    if export not in GROUP_SLAB_EXPORTS:
+        raise ValueError(f"group_single_step_adaptivity_on_slabs: export must be one of {GROUP_SLAB_EXPORTS}, not {export!r}")
+    device = export == "device"
+    compact = export == "compact" or device   # (what the two share: no ids, no whole field, the device mass sums)
     candidates = export == "candidates"
     p, ap = P.to_ffi(), adapt_params(P, dt)
     ids = None if compact else [c.download("particle_id") for c in contexts]
@@ -410,6 +421,8 @@ def group_single_step_adaptivity_on_slabs(lib: ffi.SphLibrary, contexts: Sequenc
     info = {"n_before": n, "shares": 0, "merges": 0, "splits": 0, "export": export, "exported_indices": 0, "bytes_down": 0 if compact else 4 * n}
     if compact:
         info.update(participants=0, bytes_up=0, passes=[])
+    if device:
+        info["bytes_between_devices"] = 0
     lists = None
 
     def mass_sum():
@@ -452,6 +465,17 @@ def group_single_step_adaptivity_on_slabs(lib: ffi.SphLibrary, contexts: Sequenc
             return int(mc.sum()), lambda: ffi.group_adapt(contexts, kind, p, ap, mp, mc)
         for c in contexts:
             c.classify(p)
+        if device:
+            root = 0
+            found = ffi.group_find_partners_device(contexts, kind, p, ap, root=root)
+            K, counts = found["participants"], found["ranks"]
+            info["participants"] += K
+            info["exported_indices"] += int(sum(t for _, _, t in counts))
+            info["bytes_down"] += C_INFO_BYTES
+            info["bytes_between_devices"] += int(sum(25 * k + 4 * (ko + 1) + 4 * t for r, (k, ko, t) in enumerate(counts) if r != root and k)) + 10 * K * (len(contexts) - 1)
+            info["passes"].append({"kind": kind, "participants": K, "ranks": counts, "rounds": found["rounds"], "max_frontier": found["max_frontier"],
+                                   "wide_rounds": found["wide_rounds"]})
+            return found["transfers"], lambda: ffi.group_adapt_device(contexts, kind, p, ap)
         counts = ffi.group_slab_partner_problem_prepare(contexts, kind, p, ap)
         parts = [c.slab_partner_problem_download() for c in contexts]
         pids, *fields, off_c, idx_c = merge_slab_partner_problems(parts)
@@ -498,6 +522,9 @@ def rank_single_step_adaptivity_on_slabs(ctx: ffi.Context, P, dt: float, step_nu
     from .adaptivity import adapt_params
     if P.support_length_estimation != "FromMass":
         raise ValueError("rank_single_step_adaptivity_on_slabs: support_length_estimation must be FromMass")
+    if export == "device":
+        raise ValueError("rank_single_step_adaptivity_on_slabs: export=\"device\" exists for the in-process group form only (group_single_step_adaptivity_on_slabs: "
+                         "the transports between processes have no gather to a root)")
     if export not in SLAB_EXPORTS:
         raise ValueError(f"rank_single_step_adaptivity_on_slabs: export must be one of {SLAB_EXPORTS}, not {export!r}")
     candidates = export == "candidates"

@@ -184,6 +184,9 @@ SLAB_CANDIDATE_SYMBOLS = ["slab_candidates_prepare", "group_slab_candidates_prep
 SLAB_PROBLEM_SYMBOLS = ["slab_partner_problem_prepare", "group_slab_partner_problem_prepare", "slab_partner_problem_download",
                         "slab_share_particles_compact", "slab_merge_particles_compact", "group_adapt_compact"]
 
+# include/sph_slab_partner_search.h: the searches of a slab group on the device -- merge on one member, solve, hand over, apply (product only)
+SLAB_SEARCH_SYMBOLS = ["group_find_partners_device", "group_download_merged_partner_problem", "group_download_partner_decisions", "group_adapt_device"]
+
 
 # include/sph_slab_render.h: frames drawn from slab contexts -- rank layers composed on the device (product only)
 SLAB_RENDER_SYMBOLS = ["slab_render_pressure_max", "slab_render_layer", "slab_render_layer_download", "render_compose", "group_render"]
@@ -370,6 +373,12 @@ class SphLibrary:
         self.slab_share_particles_compact = sig("slab_share_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
         self.slab_merge_particles_compact = sig("slab_merge_particles_compact", i32, [vp, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
         self.group_adapt_compact = sig("group_adapt_compact", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, u64, vp, vp, vp], required=False)
+        self.group_find_partners_device = sig("group_find_partners_device", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap, C.c_uint32, i32,
+                                                                                 C.POINTER(SphPartnerSearchInfo), pu64, pu64, pu64], required=False)
+        self.group_download_merged_partner_problem = sig("group_download_merged_partner_problem", i32, [C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp, vp, u64, vp, u64, pu64,
+                                                                                                       pu64], required=False)
+        self.group_download_partner_decisions = sig("group_download_partner_decisions", i32, [C.POINTER(vp), i32, i32, u64, vp, vp, vp], required=False)
+        self.group_adapt_device = sig("group_adapt_device", i32, [C.POINTER(vp), i32, i32, C.POINTER(SphParams), ap], required=False)
         bp = C.POINTER(SphRenderBand)
         self.slab_render_pressure_max = sig("slab_render_pressure_max", i32, [vp, C.POINTER(C.c_float)], required=False)
         self.slab_render_layer = sig("slab_render_layer", i32, [vp, C.POINTER(SphParams), rpp, C.c_float, bp], required=False)
@@ -1057,6 +1066,79 @@ def group_adapt_compact(contexts, op: str, params: SphParams, ap, ids, partner_c
     if rc != 0:
         msgs = [c.lib.last_error(c.handle) for c in contexts]
         raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+
+
+def _slab_search_lib(lib):
+    if any(getattr(lib, s, None) is None for s in SLAB_SEARCH_SYMBOLS):
+        raise SphError(30, f"{lib.path.name} has no device partner search for slab groups (sph_slab_partner_search.h)")
+    return lib
+
+
+def _group_check(contexts, rc):
+    if rc != 0:
+        msgs = [c.lib.last_error(c.handle) for c in contexts]
+        raise SphError(rc, " | ".join(m.decode(errors="replace") for m in msgs if m))
+
+
+def group_find_partners_device(contexts, kind, params: SphParams, ap, wide_threshold: int = 0, root: int = 0) -> dict:
+    """sph_group_find_partners_device: prepare the ranks' local problems of the `kind` ("share" / 0, "merge" / 1) search, merge them on
+    the device of member `root`, solve and validate there, hand the K decisions to every member's device: the group's open solution
+    for group_adapt_device.  -> the info struct of the merged problem as a dict (participants, candidates, donors, transfers, rounds,
+    max_frontier, wide_rounds) plus "ranks": the members' (n_participants, n_owned_participants, n_indices) as the prepare reports
+    them.  `wide_threshold`: as in Context.find_partners_device."""
+    lib = _slab_search_lib(contexts[0].lib)
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    K, Ko, tot = (C.c_uint64 * k)(), (C.c_uint64 * k)(), (C.c_uint64 * k)()
+    info = SphPartnerSearchInfo()
+    _group_check(contexts, lib.group_find_partners_device(handles, k, int({"share": 0, "merge": 1}.get(kind, kind)), C.byref(params) if params is not None else None,
+                                                          C.byref(ap) if ap is not None else None, int(wide_threshold), int(root), C.byref(info), K, Ko, tot))
+    out = info.as_dict()
+    out["ranks"] = [(int(K[i]), int(Ko[i]), int(tot[i])) for i in range(k)]
+    return out
+
+
+def group_download_merged_partner_problem(contexts):
+    """sph_group_download_merged_partner_problem (inspection; the solution stays open): the merged problem as it sits on the root, in the
+    layout of distributed.merge_slab_partner_problems: (ids, size_class, mass, level_estimation, position, h2, offsets, indices), K
+    entries per field, offsets[K + 1], the indices in compact ids.  A sizing call, then the filling one."""
+    lib = _slab_search_lib(contexts[0].lib)
+    n = len(contexts)
+    handles = (C.c_void_p * n)(*[c.handle for c in contexts])
+    k, tot = C.c_uint64(0), C.c_uint64(0)
+    _group_check(contexts, lib.group_download_merged_partner_problem(handles, n, None, None, None, None, None, None, None, 0, None, 0, C.byref(k), C.byref(tot)))
+    K, T = int(k.value), int(tot.value)
+    v = {"ids": np.empty(K, np.uint32), "offsets": np.empty(K + 1, np.uint32), "indices": np.empty(T, np.uint32)}
+    for name in PROBLEM_FIELDS:
+        fid, dt, w = FIELDS[name]
+        v[name] = np.empty(K * w, dt)
+    ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+    _group_check(contexts, lib.group_download_merged_partner_problem(handles, n, ptr(v["ids"]), *[ptr(v[f]) for f in PROBLEM_FIELDS], v["offsets"].ctypes.data, K,
+                                                                     ptr(v["indices"]), T, None, None))
+    return (v["ids"], v["particle_size_class"], v["mass"], v["level_estimation"], v["position"].reshape(K, 2), v["h2"], v["offsets"], v["indices"])
+
+
+def group_download_partner_decisions(contexts, from_member: int, k: int):
+    """sph_group_download_partner_decisions (inspection; the solution stays open): -> (ids, partner_c, counter_c) as member `from_member`
+    holds them; the open solution must have exactly `k` participants."""
+    lib = _slab_search_lib(contexts[0].lib)
+    n = len(contexts)
+    handles = (C.c_void_p * n)(*[c.handle for c in contexts])
+    k = int(k)
+    ids, mp, mc = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint16)
+    ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+    _group_check(contexts, lib.group_download_partner_decisions(handles, n, int(from_member), k, ptr(ids), ptr(mp), ptr(mc)))
+    return ids, mp, mc
+
+
+def group_adapt_device(contexts, op, params: SphParams, ap):
+    """sph_group_adapt_device: share / merge on the k slab contexts of this process from the group's open solution, which it consumes;
+    the same state as group_adapt_compact with the same decisions."""
+    lib = _slab_search_lib(contexts[0].lib)
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    _group_check(contexts, lib.group_adapt_device(handles, k, int({"share": 0, "merge": 1}.get(op, op)), C.byref(params) if params is not None else None,
+                                                  C.byref(ap) if ap is not None else None))
 
 
 def group_render(contexts, params: SphParams, rp: "SphRenderParams") -> np.ndarray:
