@@ -3,6 +3,8 @@
 // forms of the first two: one definition of the tests, of the row walk, of the packed arrays and of the way decisions come back.
 #pragma once
 
+#include <vector>
+
 #include "sph_context.hpp"
 #include "sph_partner_search.h"   // sph_partner_search_info
 
@@ -132,3 +134,25 @@ int slab_prob_prepare(Group& G, int kind, const sph_params* p, const sph_adapt_p
 // sph_adapt.hip: slab_adapt (op 0 share, 1 merge) from the k decisions every member holds on its own device (slab_sol_ids /
 // slab_sol_partner / slab_sol_counter): the device form of SlabCompact
 int slab_adapt_device(Group& G, int op, const sph_params* p, const sph_adapt_params* ap, uint64_t k);
+
+// sph_slab_partner_search.hip, shared with sph_rank_partner_search.hip: one member's local problem as it is STAGED in the root's memory,
+// and the merge of the staged problems -- the one merge of both forms; what differs is how the arrays got there (peer copies in the
+// group form, a relay over the ranks' transport in the per-process form).  slab_merge_staged: see its definition.
+struct SmPart {
+    const uint32_t* ids;   // [K] owned participants first
+    const uint8_t* cls;
+    const float* mass;
+    const float* level;
+    const float2* pos;
+    const float* h2;
+    const uint32_t* off;   // [Ko + 1]
+    const uint32_t* idx;   // [T] global ids
+    uint32_t K, Ko, T;
+};
+int slab_merge_staged(sph_ctx* r, int root, const char* what, const std::vector<SmPart>& part, const uint32_t* ids_side_by_side, uint32_t n_global, uint32_t* K_out,
+                      uint32_t* tot_out);
+// THE OPEN SOLUTION is open on c (the lifetime rule of sph_slab_partner_search.h)
+inline bool slab_solution_open(const sph_ctx* c)
+{
+    return c->slab_prob_open && c->slab_rows_open && c->slab_lists_valid && c->slab_sol_serial != 0 && c->slab_sol_serial == c->slab_prob_serial;
+}

@@ -161,9 +161,15 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     int slab_sol_kind = 0, slab_sol_root = 0;
     DevBuf slab_sol_ids, slab_sol_partner, slab_sol_counter;
     DevBuf ss_stage, ss_flag, ss_rank, ss_seen, ss_rowlen, ss_err;
-    std::array<DevBuf*, 22> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob.ids, &slab_prob.cls,
+    // sph_rank_partner_search.hip (one process per rank): the ranks' blobs in rank order sit in ss_stage on every rank that relays them;
+    // rs_bcast: the header and the decisions blob the root sends out
+    DevBuf rs_bcast;
+    // ... and what the relays of the open solution's search moved (sph_slab_relay_sizes)
+    std::vector<uint64_t> rs_blob_bytes;
+    uint64_t rs_chunk = 0, rs_header_bytes = 0, rs_dec_bytes = 0, rs_sent = 0, rs_received = 0;
+    std::array<DevBuf*, 23> slab_bufs() { return {&slab_row_slot, &slab_slot_row, &slab_off, &slab_idx, &slab_prob_flag, &slab_prob_rank, &slab_prob.ids, &slab_prob.cls,
                                                   &slab_prob.mass, &slab_prob.level, &slab_prob.pos, &slab_prob.h2, &slab_prob.off, &slab_sol_ids, &slab_sol_partner,
-                                                  &slab_sol_counter, &ss_stage, &ss_flag, &ss_rank, &ss_seen, &ss_rowlen, &ss_err}; }
+                                                  &slab_sol_counter, &ss_stage, &ss_flag, &ss_rank, &ss_seen, &ss_rowlen, &ss_err, &rs_bcast}; }
 
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];

@@ -59,6 +59,9 @@ struct Comm {
                                  std::vector<uint32_t>& from_left, std::vector<uint32_t>& from_right, int* status = nullptr) = 0;
     // device buffers; ordered after everything queued on the members' streams
     virtual int exchange(Group& G, std::vector<Xfer>& x) = 0;
+    // the most bytes one message of exchange() may hold: bytes_per_side of sph_comm_init_shm / sph_comm_ipc_export, above which those
+    // transports answer SPH_ERR_CAPACITY and are abandoned; SIZE_MAX where there is no limit (RCCL, threads, loopback)
+    virtual size_t max_message_bytes(Group&) { return SIZE_MAX; }
     // element-wise sum of the members' 6 device doubles (solver totals + error flag), result in every member's buffer
     virtual int allreduce_solver(Group& G, int slot) = 0;   // slot 1: the second solve of a chained pair keeps totals of its own
     // a Jacobi iteration's two collectives -- the ghosts' p / rho^2 and the totals of the iteration before -- as ONE call: a
@@ -175,6 +178,15 @@ inline int group_entry(Group& G, sph_ctx** ctxs, int n)
     G.comm = comm_loopback();
     return SPH_OK;
 }
+// (sph_relay.hip) A GATHER TO ONE RANK AND A BROADCAST FROM IT over Comm::exchange alone, for a group of ONE member on its own transport:
+// the ranks are a row, a blob moves one hop per round (the schedule: include/sph_rank_partner_search.h, sph_relay_plan -- the function
+// that drives these).  bytes[o]: rank o's blob, a multiple of 16; buf: the blobs in rank order, blob o at the sum of the sizes in front
+// of it -- this rank's own blob is in place on entry, on the root all of them are on return, a rank in between holds those it passed on.
+// chunk: the most bytes of one message, a multiple of 16.  relay_bcast: `bytes` bytes at buf, in place on the root on entry, on every
+// rank on return.  Queued on the member's stream; the ordering is exchange's.  *sent / *received: what this rank's messages added up to.
+int relay_gather(Group& G, int root, const std::vector<uint64_t>& bytes, uint64_t chunk, uint8_t* buf, uint64_t* sent, uint64_t* received);
+int relay_bcast(Group& G, int root, uint64_t bytes, uint64_t chunk, uint8_t* buf, uint64_t* sent, uint64_t* received);
+
 // (sph_adapt.hip) the ghosts hold what their owners hold NOW (stale behind a share): the records, the velocities if asked for, the level
 int refresh_ghost_state(Group& G, bool with_velocity);
 // the arrays a reorder of the context's state moves: records pm_in -> pm_out, cells to `cxy`, everything else from the buffers of c->cur

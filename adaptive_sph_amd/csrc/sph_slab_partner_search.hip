@@ -3,7 +3,8 @@
 //
 //   staging  every member's packed arrays to the ROOT's device (ss_stage: the members' ids side by side, then per member its five
 //            fields, offsets and entries): hipMemcpyPeerAsync between two devices, a device-to-device copy on one, queued on the root's
-//            stream behind an event of the member's stream.  No kernel reads another device's memory
+//            stream behind an event of the member's stream.  No kernel reads another device's memory.  (slab_merge_on_root.  Everything below
+//            is slab_merge_staged, which the per-process form -- sph_rank_partner_search.hip: staging by a relay -- calls as well)
 //   mark     flag[n_global], zeroed; one thread per reported id stores 1 (plain stores of equal values, nobody reads a flag in that
 //            launch); an id >= n_global sets the error word and is skipped
 //   scan     device_exclusive_scan_u32 over the flags: rank[g] = compact id, K in the last word; ids_c[rank[g]] = g (one thread per
@@ -31,19 +32,6 @@
 #include "sph_dist.hpp"
 
 enum : uint32_t { SM_ERR_ID = 1, SM_ERR_BITS = 2, SM_ERR_OWNERS = 3, SM_ERR_ENTRY = 4, SM_ERR_ROWS = 5 };
-
-// one member's local problem as staged on the root
-struct SmPart {
-    const uint32_t* ids;   // [K] owned participants first
-    const uint8_t* cls;
-    const float* mass;
-    const float* level;
-    const float2* pos;
-    const float* h2;
-    const uint32_t* off;   // [Ko + 1]
-    const uint32_t* idx;   // [T] global ids
-    uint32_t K, Ko, T;
-};
 
 __global__ __launch_bounds__(256) void k_slab_merge_mark(uint32_t n_ids, const uint32_t* __restrict__ ids, uint32_t n_global, uint32_t* __restrict__ flag,
                                                           uint32_t* __restrict__ err)
@@ -168,11 +156,6 @@ static hipError_t sm_copy(void* dst, int dst_dev, const void* src, int src_dev, 
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s);
 }
 
-static bool slab_solution_open(const sph_ctx* c)
-{
-    return c->slab_prob_open && c->slab_rows_open && c->slab_lists_valid && c->slab_sol_serial != 0 && c->slab_sol_serial == c->slab_prob_serial;
-}
-
 // what every entry point of this header refuses first; fills G
 static int slab_search_entry(Group& G, sph_ctx** ctxs, int n, const char* what)
 {
@@ -186,18 +169,17 @@ static int slab_search_entry(Group& G, sph_ctx** ctxs, int n, const char* what)
     return group_entry(G, ctxs, n);
 }
 
-// the members' local problems -> the merged problem in root's prob / prob_idx; *K_out / *tot_out: its participants and entries
+// STAGING, the group form: the members' packed arrays copied to the root's device (peer copies between two devices), the members' ids
+// side by side in front; then THE MERGE (slab_merge_staged, below) on what was staged.  The per-process form stages by a relay over the
+// ranks' transport instead (sph_rank_partner_search.hip) and calls the same merge.
 static int slab_merge_on_root(Group& G, size_t root, const char* what, const uint64_t* Ki, const uint64_t* Koi, const uint64_t* Ti, uint32_t n_global, uint32_t* K_out,
                               uint32_t* tot_out)
 {
     const size_t nm = G.m.size();
     sph_ctx* r = G.m[root];
     *K_out = *tot_out = 0;
-    uint64_t sum_k = 0, sum_t = 0;
-    for (size_t i = 0; i < nm; i++) {
-        sum_k += Ki[i];
-        sum_t += Ti[i];
-    }
+    uint64_t sum_k = 0;
+    for (size_t i = 0; i < nm; i++) sum_k += Ki[i];
     if (sum_k == 0) return SPH_OK;
     // ---- where each member's arrays sit in the staging buffer (16-byte aligned)
     struct Place {
@@ -237,14 +219,7 @@ static int slab_merge_on_root(Group& G, size_t root, const char* what, const uin
     HIPCHK(r, hipSetDevice(r->device));
     hipStream_t s = r->stream;
     HIPCHK(r, r->ss_stage.ensure(bytes + 16));
-    HIPCHK(r, r->ss_flag.ensure((size_t)n_global * 4 + 4));
-    HIPCHK(r, r->ss_rank.ensure(((size_t)n_global + 1) * 4));
-    HIPCHK(r, r->ss_err.ensure(16));
-    HIPCHK(r, r->cand_scan.ensure(((size_t)std::max<uint64_t>(n_global, sum_k) / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
     uint8_t* stage = r->ss_stage.as<uint8_t>();
-    uint32_t* flag = r->ss_flag.as<uint32_t>();
-    uint32_t* rank = r->ss_rank.as<uint32_t>();
-    uint32_t* err = r->ss_err.as<uint32_t>();
     std::vector<SmPart> part(nm);
     {
         ProfScope ps(&r->prof, "slab_search_stage", s);
@@ -267,20 +242,50 @@ static int slab_merge_on_root(Group& G, size_t root, const char* what, const uin
             HIPCHK(r, sm_copy(stage + at[i].idx, r->device, c->cand_idx.p, c->device, t * 4, s));
         }
     }
+    return slab_merge_staged(r, (int)root, what, part, (const uint32_t*)stage, n_global, K_out, tot_out);
+}
+
+// THE MERGE, once for both forms: the local problems `part` (every pointer in the root's memory, queued behind whatever staged them on
+// r's stream) -> the merged problem in r's prob / prob_idx; *K_out / *tot_out: its participants and entries.  ids_side_by_side: the
+// members' ids in one array in member order (the group form's staging: ONE mark launch reads them all), or nullptr: the ids sit inside
+// each member's blob and the mark kernel is launched once per blob (the relay's staging) -- equal stores to the same flags either way.
+int slab_merge_staged(sph_ctx* r, int root, const char* what, const std::vector<SmPart>& part, const uint32_t* ids_side_by_side, uint32_t n_global, uint32_t* K_out,
+                      uint32_t* tot_out)
+{
+    const size_t nm = part.size();
+    hipStream_t s = r->stream;
+    *K_out = *tot_out = 0;
+    uint64_t sum_k = 0, sum_t = 0;
+    for (size_t i = 0; i < nm; i++) {
+        sum_k += part[i].K;
+        sum_t += part[i].T;
+    }
+    if (sum_k == 0) return SPH_OK;
+    HIPCHK(r, r->ss_flag.ensure((size_t)n_global * 4 + 4));
+    HIPCHK(r, r->ss_rank.ensure(((size_t)n_global + 1) * 4));
+    HIPCHK(r, r->ss_err.ensure(16));
+    HIPCHK(r, r->cand_scan.ensure(((size_t)std::max<uint64_t>(n_global, sum_k) / 2048 + 4) * 4));   // device_exclusive_scan_u32: one word per tile of 2048
+    uint32_t* flag = r->ss_flag.as<uint32_t>();
+    uint32_t* rank = r->ss_rank.as<uint32_t>();
+    uint32_t* err = r->ss_err.as<uint32_t>();
     const dim3 blk(256);
     uint32_t K = 0, e = 0;
     {
         ProfScope ps(&r->prof, "slab_search_mark", s);
         HIPCHK(r, hipMemsetAsync(flag, 0, (size_t)n_global * 4, s));
         HIPCHK(r, hipMemsetAsync(err, 0, 16, s));
-        hipLaunchKernelGGL(k_slab_merge_mark, dim3((uint32_t)((sum_k + 255) / 256)), blk, 0, s, (uint32_t)sum_k, (const uint32_t*)stage, n_global, flag, err);
+        if (ids_side_by_side)
+            hipLaunchKernelGGL(k_slab_merge_mark, dim3((uint32_t)((sum_k + 255) / 256)), blk, 0, s, (uint32_t)sum_k, ids_side_by_side, n_global, flag, err);
+        else
+            for (size_t i = 0; i < nm; i++)
+                if (part[i].K) hipLaunchKernelGGL(k_slab_merge_mark, dim3((part[i].K + 255) / 256), blk, 0, s, part[i].K, part[i].ids, n_global, flag, err);
         device_exclusive_scan_u32(s, flag, rank, n_global, r->cand_scan.as<uint32_t>(), rank + n_global);
     }
     HIPCHK(r, hipMemcpyAsync(&K, rank + n_global, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(r, hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(r, hipStreamSynchronize(s));
     if (!e && (K == 0 || K > n_global || K > sum_k)) e = SM_ERR_ID;
-    if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, %llu local participants)", what, sm_error_text(e), (int)root, (unsigned long long)sum_k);
+    if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, %llu local participants)", what, sm_error_text(e), root, (unsigned long long)sum_k);
     ProbOut out;
     if (int rc = prob_out(r, r->prob, K, K, &out)) return rc;
     HIPCHK(r, r->ss_seen.ensure((size_t)K + 4));
@@ -303,7 +308,7 @@ static int slab_merge_on_root(Group& G, size_t root, const char* what, const uin
     HIPCHK(r, hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(r, hipStreamSynchronize(s));
     if (!e && tot_c != sum_t) e = SM_ERR_ROWS;
-    if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, K=%u)", what, sm_error_text(e), (int)root, K);
+    if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, K=%u)", what, sm_error_text(e), root, K);
     HIPCHK(r, r->prob_idx.ensure((size_t)tot_c * 4 + 4));
     if (tot_c) {
         ProfScope ps(&r->prof, "slab_search_rows", s);
@@ -313,7 +318,7 @@ static int slab_merge_on_root(Group& G, size_t root, const char* what, const uin
                                    (const uint32_t*)out.off, r->prob_idx.as<uint32_t>(), err);
         HIPCHK(r, hipMemcpyAsync(&e, err, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(r, hipStreamSynchronize(s));
-        if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, K=%u)", what, sm_error_text(e), (int)root, K);
+        if (e) return r->fail(SPH_ERR_DEVICE, "%s: %s (merge on rank %d, K=%u)", what, sm_error_text(e), root, K);
     }
     *K_out = K;
     *tot_out = tot_c;

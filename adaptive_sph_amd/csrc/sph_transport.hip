@@ -582,8 +582,10 @@ struct RendezvousComm : Comm {
     // one side of an exchange: the sender stages its payload before the pair meets, the receiver takes it while the two are together
     static int stage(sph_ctx* c, Rdv& R, const Xfer& x, int side);
     static int take(sph_ctx* c, Rdv& R, const Xfer& x, int side);
+    static size_t message_limit(sph_ctx* c);
 
     bool host_collectives_wait() const override { return true; }
+    size_t max_message_bytes(Group& G) override { return message_limit(G.m[0]); }
     static int settle(sph_ctx* c)   // everything queued on the rank's stream is through
     {
         const int rc = wait_stream(c);
@@ -677,6 +679,7 @@ struct RendezvousComm : Comm {
 // threads: the sender's staging pointers travel through the pair channel, the receiver copies device to device on its own stream
 template <> ThreadGroup* RendezvousComm<ThreadGroup>::board(sph_ctx* c) { return (ThreadGroup*)c->dist.tgroup; }
 template <> void RendezvousComm<ThreadGroup>::abandon(sph_ctx* c) { board(c)->abandon(); }
+template <> size_t RendezvousComm<ThreadGroup>::message_limit(sph_ctx*) { return SIZE_MAX; }
 template <> int RendezvousComm<ThreadGroup>::stage(sph_ctx*, Rdv& R, const Xfer& x, int side)
 {
     for (int sd = 0; sd < 2; sd++) R.b.pair[(size_t)R.lower(side)].send[R.who(side)][sd] = x.send[sd];
@@ -691,6 +694,7 @@ template <> int RendezvousComm<ThreadGroup>::take(sph_ctx* c, Rdv& R, const Xfer
 // processes: device -> my outbox in the segment by the sender, the neighbour's outbox -> device by the receiver
 template <> ShmSegment* RendezvousComm<ShmSegment>::board(sph_ctx* c) { return (ShmSegment*)c->dist.shm; }
 template <> void RendezvousComm<ShmSegment>::abandon(sph_ctx* c) { comm_abandon(c); }
+template <> size_t RendezvousComm<ShmSegment>::message_limit(sph_ctx* c) { return (size_t)board(c)->bytes_per_side; }
 template <> int RendezvousComm<ShmSegment>::stage(sph_ctx* c, Rdv& R, const Xfer& x, int side)
 {
     if (x.send_bytes[side] > R.b.bytes_per_side) {
@@ -1041,6 +1045,7 @@ struct IpcComm : ShmComm {
         return SPH_OK;
     }
     int exchange(Group& G, std::vector<Xfer>& x) override { return round(G, &x, -1); }
+    size_t max_message_bytes(Group& G) override { return (size_t)st(G.m[0])->bytes_per_side; }
     int allreduce_solver(Group& G, int slot) override { return round(G, nullptr, slot); }
     int exchange_and_allreduce_solver(Group& G, std::vector<Xfer>& x, int slot) override { return round(G, &x, slot); }
 };

@@ -7,6 +7,8 @@ unique id and the launcher's barrier; the halo exchange itself is RCCL inside li
   make_loopback_group  k contexts in this process (ranks 0..k-1) for single-GPU verification
   group_single_step_adaptivity  single_step_adaptivity for a slab group, through a gather to one context and back
   rank_single_step_adaptivity   the same with one process per rank: gather / scatter through the launcher's process group
+  rank_single_step_adaptivity_on_slabs         the particles stay on their ranks; the decisions on the root's host, through the launcher
+  rank_single_step_adaptivity_on_slabs_device  ... the decisions on the root's device, relayed over the ranks' own transport
   ThreadedGroup      k ranks of this process, one host thread each, every rank calling sph_step by itself (verification of the per-rank code)
 """
 from __future__ import annotations
@@ -63,10 +65,11 @@ _SHM_SERIAL = [0]
 
 
 def make_slab_context(lib: ffi.SphLibrary, pos, mass, vel, planes, rank: int, world: int, local_rank: int, transport: str = None,
-                      cuts: Sequence[float] = None) -> ffi.Context:
+                      cuts: Sequence[float] = None, bytes_per_side: int = None) -> ffi.Context:
     """This rank's slab context of a `torch.distributed` launch (one process per rank): configured, communicator attached, particles
     uploaded.  torch.distributed only carries the RCCL unique id (or the shared-memory segment's name) and a barrier.  `cuts`: the
-    world + 1 static cuts (default: slab_cuts, equal counts)."""
+    world + 1 static cuts (default: slab_cuts, equal counts).  `bytes_per_side` (shared-memory and peer-mapped transports): the size of an
+    outbox / inbox, the most one message may hold (default: room for every particle of the slab as a migrant record)."""
     import os
     import torch.distributed as dist
     import torch
@@ -85,7 +88,7 @@ def make_slab_context(lib: ffi.SphLibrary, pos, mass, vel, planes, rank: int, wo
         _SHM_SERIAL[0] += 1
         name = [f"/sph_shm_{os.getpid()}_{_SHM_SERIAL[0]}" if rank == 0 else None]
         dist.broadcast_object_list(name, src=0)
-        per_side = max(1 << 22, cap * 48)
+        per_side = int(bytes_per_side) if bytes_per_side else max(1 << 22, cap * 48)
         if rank == 0:
             ctx.comm_init_shm(name[0], rank, world, per_side, True)
         dist.barrier()
@@ -524,7 +527,7 @@ def rank_single_step_adaptivity_on_slabs(ctx: ffi.Context, P, dt: float, step_nu
         raise ValueError("rank_single_step_adaptivity_on_slabs: support_length_estimation must be FromMass")
     if export == "device":
         raise ValueError("rank_single_step_adaptivity_on_slabs: export=\"device\" exists for the in-process group form only (group_single_step_adaptivity_on_slabs: "
-                         "the transports between processes have no gather to a root)")
+                         "the transports between processes have no gather to a root; rank_single_step_adaptivity_on_slabs_device relays over the rank's own transport)")
     if export not in SLAB_EXPORTS:
         raise ValueError(f"rank_single_step_adaptivity_on_slabs: export must be one of {SLAB_EXPORTS}, not {export!r}")
     candidates = export == "candidates"
@@ -682,6 +685,81 @@ def rank_single_step_adaptivity_on_slabs(ctx: ffi.Context, P, dt: float, step_nu
     return info
 
 
+def _launcher_total(v):
+    """the sum of `v` over the ranks of the launcher's process group"""
+    import torch.distributed as dist
+    t = [None] * dist.get_world_size()
+    dist.all_gather_object(t, v)
+    return sum(t)
+
+
+def rank_single_step_adaptivity_on_slabs_device(ctx: ffi.Context, P, dt: float, step_number: int, root: int = 0, relay_bytes: int = 0, total=None) -> dict:
+    """single_step_adaptivity with ONE PROCESS PER RANK and the partner searches ON THE DEVICE (include/sph_rank_partner_search.h): per
+    search every rank classifies, packs its local problem and relays it to `root` over the context's own transport, `root` merges,
+    solves and validates on its device and relays the K decisions back, every rank applies its copy (Context.slab_find_partners_device,
+    Context.slab_adapt_device: collective calls).  The same decisions and the same state as
+    rank_single_step_adaptivity_on_slabs(export="compact"); no problem comes down, nothing is pickled, no decision goes up.  Every rank
+    calls this after the same sph_step; a failure on the root inside merge or solve is raised on every rank.
+
+    `relay_bytes`: the most bytes of one relay message (0: the transport's limit).  `total`: the sum of a number over all ranks, for
+    the particle counts and the mass check (default: through the launcher's process group, torch.distributed; ranks that are threads
+    of one process pass their own).
+
+    info: the counts are this rank's, shaped like the group form's: ["passes"]: per search its kind, K ("participants"), this rank's
+    local counts ("ranks": one triple), rounds, max_frontier, wide_rounds; ["bytes_down"]: the 48 B info struct per search and the 8 B
+    device mass sums; ["bytes_up"]: 0; ["bytes_between_devices"]: what this rank sent and received in the relays; ["seconds"]: this
+    rank's clock in the searches and the applies."""
+    import time
+    from .adaptivity import adapt_params
+    if P.support_length_estimation != "FromMass":
+        raise ValueError("rank_single_step_adaptivity_on_slabs_device: support_length_estimation must be FromMass")
+    total = total or _launcher_total
+    p, ap = P.to_ffi(), adapt_params(P, dt)
+    info = {"n_before": total(ctx.n), "shares": 0, "merges": 0, "splits": 0, "export": "device", "exported_indices": 0, "bytes_down": 0, "bytes_up": 0,
+            "bytes_between_devices": 0, "participants": 0, "passes": []}
+    tm = {"find_s": 0.0, "apply_s": 0.0}
+
+    def mass_sum():
+        info["bytes_down"] += 8
+        return total(ctx.slab_sum_mass())
+
+    def search(kind):
+        t0 = time.perf_counter()
+        ctx.classify(p)
+        found = ctx.slab_find_partners_device(kind, p, ap, root=root, relay_bytes=relay_bytes)
+        moved = ctx.slab_relay_sizes()
+        tm["find_s"] += time.perf_counter() - t0
+        info["participants"] += found["participants"]
+        info["exported_indices"] += found["local"][2]
+        info["bytes_down"] += C_INFO_BYTES
+        info["bytes_between_devices"] += moved["bytes_sent"] + moved["bytes_received"]
+        info["passes"].append({"kind": kind, "participants": found["participants"], "ranks": [found["local"]], "rounds": found["rounds"],
+                               "max_frontier": found["max_frontier"], "wide_rounds": found["wide_rounds"]})
+        t0 = time.perf_counter()
+        ctx.slab_adapt_device(kind, p, ap)
+        tm["apply_s"] += time.perf_counter() - t0
+        return found["transfers"]
+
+    m1 = mass_sum()
+    if P.sharing:
+        info["shares"] = search("share")
+    if step_number % 2 == 0:
+        if P.merging:
+            info["merges"] = search("merge")
+    elif P.splitting:
+        t0 = time.perf_counter()
+        ctx.classify(p)
+        ctx.split_particles(p, ap)
+        tm["apply_s"] += time.perf_counter() - t0
+    info["n_after"] = total(ctx.n)
+    info["splits"] = max(0, info["n_after"] - info["n_before"]) if step_number % 2 == 1 else 0
+    m2 = mass_sum()
+    if not abs(m1 - m2) <= 0.005:
+        raise AssertionError(f"mass sum: {m1} vs {m2}")
+    info["seconds"] = tm
+    return info
+
+
 def rank_single_step_adaptivity(ctx: ffi.Context, gather: GatherContext, P, dt: float, step_number: int, capacity: int = 0, root: int = 0) -> dict:
     """The same adaptive step with ONE PROCESS PER RANK (the launch bench.py --gpus N and the RCCL / shared-memory transports use):
     every rank hands the fields adaptivity reads and its exported neighbour lists to `root` through the launcher's process group
@@ -740,7 +818,7 @@ class ThreadedGroup:
     (sph_thread_group_create / sph_comm_init_threads).  A collective that not every rank enters, ranks in different collectives or
     a send without a matching receive -- what would hang the RCCL transport -- comes back as an error."""
 
-    def __init__(self, lib: ffi.SphLibrary, pos, mass, vel, planes, n_ranks: int, device_id: int = 0, capacities=None):
+    def __init__(self, lib: ffi.SphLibrary, pos, mass, vel, planes, n_ranks: int, device_id: int = 0, capacities=None, cuts: Sequence[float] = None):
         import ctypes as C
         from concurrent.futures import ThreadPoolExecutor
         self.lib = lib
@@ -748,7 +826,7 @@ class ThreadedGroup:
         rc = lib.thread_group_create(n_ranks, C.byref(self.group))
         if rc != 0:
             raise ffi.SphError(rc, "sph_thread_group_create failed")
-        cuts = slab_cuts(pos[:, 0], n_ranks)
+        cuts = list(cuts) if cuts is not None else slab_cuts(pos[:, 0], n_ranks)   # (as make_loopback_group takes them)
         parts = partition(pos[:, 0], cuts)
         self.contexts = []
         for r in range(n_ranks):
