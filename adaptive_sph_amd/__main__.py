@@ -21,6 +21,13 @@ from .simulation import init_fluid_sim, init_simulation_params
 from .simulation_parameters import SimulationParams, load_yaml_mapping
 
 
+def _positive_float(text: str) -> float:
+    v = float(text)
+    if not (0.0 < v < float("inf")):
+        raise argparse.ArgumentTypeError(f"{text!r} is not a positive finite number")
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="adaptive_sph_amd", description="2-D adaptive SPH step on MI355X (kaegi/adaptive-sph hot path)")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -47,6 +54,14 @@ def build_parser() -> argparse.ArgumentParser:
     # the reference's VtkExporter is compiled in but switched off (main_loop.rs:253 `export_vtk_data = false`); same writer here
     run.add_argument("--vtk", default=None, metavar="FOLDER", help="write FOLDER/my-sph-NNNNN.vtk + my-sph.vtk.series (one snapshot per step)")
     run.add_argument("--vtk-every", type=int, default=1, help="snapshot every N-th step")
+    # not in the reference either: the continuous fields, sampled on the device over the scene's boundary box (sampling.py)
+    run.add_argument("--grid-vtk", default=None, metavar="FOLDER",
+                     help="write FOLDER/my-sph-grid-NNNNN.vtk + my-sph-grid.vtk.series: the SPH interpolant on a regular grid, at the cadence of --vtk-every; "
+                          "the state sampled is the one the step leaves, BEFORE that step's sharing / merging / splitting (whose edits leave "
+                          "density and pressure behind)")
+    run.add_argument("--grid-spacing", type=_positive_float, default=None, help="sample spacing of --grid-vtk (default: the smallest block spacing of the scene)")
+    run.add_argument("--grid-fields", default="density,pressure,velocity",
+                     help="comma-separated fields of --grid-vtk: density, pressure, velocity, level, constant_field")
     img = sub.add_parser("image", help="Render images (and video frames) as described by export recipes")
     img.add_argument("RECIPE", nargs="+", help="ImageExportConfig list (YAML); paths inside are relative to its directory")
     img.add_argument("--split-patterns", default=None,
@@ -86,17 +101,32 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         from .vtk_exporter import VtkExporter
         vtk = VtkExporter(args.vtk, "my-sph")          # main_loop.rs:256
         vtk_planes = boundary_planes(scene.boundary, params.init_boundary_handler)
+    grid_vtk = None
+    if args.grid_vtk:
+        from . import sampling
+        from .vtk_exporter import VtkGridExporter
+        spacing = args.grid_spacing if args.grid_spacing is not None else min(float(b.spacing) for b in scene.blocks)
+        grid = sampling.GridSpec.covering(scene.boundary, spacing)
+        grid_fields = [f.strip() for f in args.grid_fields.split(",") if f.strip()]
+        sampling.expand_channels(grid_fields)   # (an unknown name stops the run here, not at the first snapshot)
+        grid_vtk = VtkGridExporter(args.grid_vtk, "my-sph-grid")
     steps, t0 = 0, time.perf_counter()
     while (args.max_seconds is None or sim.time < args.max_seconds) and (args.max_steps is None or steps < args.max_steps):
-        if adaptive:
-            sim.single_step(params)
-        else:
-            sim.single_step_without_adaptivity(p)
+        dt = sim.single_step_without_adaptivity(p)
         steps += 1
-        if vtk is not None and steps % max(args.vtk_every, 1) == 0:
+        snapshot = steps % max(args.vtk_every, 1) == 0
+        if grid_vtk is not None and snapshot:
+            # between the step and its adaptivity (single_step, simulation.rs:1973-1978, taken apart): density and pressure are the
+            # step's outputs and line up with the particles only until sharing / merging / splitting edit the vector
+            grid_vtk.add_snapshot(sim.time, grid, sampling.sample_grid(sim.ctx, p, grid, grid_fields).planes)
+        if adaptive:
+            sim.single_step_adaptivity(params, dt)
+        if vtk is not None and snapshot:
             vtk.add_snapshot(sim.time, sim, vtk_planes)       # main_loop.rs:302-309
     if vtk is not None:
         vtk.close()
+    if grid_vtk is not None:
+        grid_vtk.close()
     wall = time.perf_counter() - t0
     print(f"{steps} steps, simulated time {sim.time:.6f} s, {sim.num_fluid_particles()} particles, "
           f"{sim.num_fluid_particles() * steps / max(wall, 1e-9) / 1e6:.2f} M particle-steps/s", file=out)

@@ -310,6 +310,9 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     DevBuf rnd_layer, rnd_band, rnd_words, rnd_stage;
     bool rnd_have_layer = false;
     int rnd_layer_sx0 = 0, rnd_layer_sx1 = 0, rnd_layer_hs = 0;
+    // fields on a regular grid (sph_sample.hip): the int64 planes, the resolved f32 planes, the words of the range pass and the counts
+    // -- allocated on first use, kept across calls, freed by sph_destroy
+    DevBuf smp_planes, smp_out, smp_red;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)

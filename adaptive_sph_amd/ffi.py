@@ -225,6 +225,33 @@ class SphRenderParams(C.Structure):
                 ("line_width", C.c_float)]
 
 
+# include/sph_sample.h: SPH fields on a regular grid, accumulated as 64-bit fixed-point integers on the device (product only)
+SAMPLE_SYMBOLS = ["sample_grid", "sample_field_range"]
+SAMPLE_MAX_CHANNELS = 6
+SAMPLE_MAX_SIDE = 16384
+SAMPLE_MIN_EXPONENT, SAMPLE_MAX_EXPONENT, SAMPLE_AUTO_EXPONENT = -64, 64, 0x7FFFFFFF
+SAMPLE_VOLUMES = {"density": 0, "rest": 1}   # SPH_SAMPLE_VOLUME_*
+SAMPLE_NORMALIZE = 1
+# channel name -> (field, component): the (field, component) pairs sph_sample.h can sample
+SAMPLE_CHANNELS = {"density": ("density", 0), "pressure": ("pressure", 0), "velocity_x": ("velocity", 0), "velocity_y": ("velocity", 1),
+                   "constant_field": ("constant_field", 0), "level_estimation": ("level_estimation", 0)}
+
+
+class SphSampleChannel(C.Structure):
+    _fields_ = [("field", C.c_int32), ("component", C.c_int32), ("exponent", C.c_int32)]
+
+
+class SphSampleParams(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("origin_x", C.c_float), ("origin_y", C.c_float), ("spacing", C.c_float),
+                ("volume", C.c_int32), ("flags", C.c_uint32), ("min_weight", C.c_float), ("fill", C.c_float), ("n_channels", C.c_int32),
+                ("channels", SphSampleChannel * SAMPLE_MAX_CHANNELS)]
+
+
+class SphSampleInfo(C.Structure):
+    _fields_ = [("exponents", C.c_int32 * SAMPLE_MAX_CHANNELS), ("n_touching", C.c_uint64), ("max_footprint", C.c_uint64),
+                ("n_pairs", C.c_uint64)]
+
+
 ABI_SYMBOLS = [
     "create", "destroy", "upload", "upload_field", "download", "download_neighbors", "num_particles", "time",
     "set_time", "step", "classify", "share_particles", "merge_particles", "set_split_patterns", "split_particles", "host_find_partners", "last_error", "grid", "set_boundary_polygon", "set_math_policy", "get_math_policy", "apply_edits", "profile_enable", "profile_reset", "profile_get", "profile_event_overhead", "profile_dispatch_bracket", "profile_copy_bandwidth", "profile_list_forms", "set_sweep_variant",
@@ -411,6 +438,10 @@ class SphLibrary:
         self.slab_render_layer_download = sig("slab_render_layer_download", i32, [vp, vp, u64], required=False)
         self.render_compose = sig("render_compose", i32, [vp, rpp, i32, bp, C.POINTER(vp), vp, u64], required=False)
         self.group_render = sig("group_render", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), rpp, vp, u64], required=False)
+        self.sample_grid = sig("sample_grid", i32, [vp, C.POINTER(SphParams), C.POINTER(SphSampleParams), vp, u64, vp, u64, C.POINTER(SphSampleInfo)],
+                               required=False)
+        self.sample_field_range = sig("sample_field_range", i32, [vp, C.POINTER(SphParams), i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
+                                      required=False)
 
 
 _PRODUCT = None
@@ -969,6 +1000,39 @@ class Context:
         out = np.empty((int(rp.height), int(rp.width), 3), np.uint8)
         self._check(lib.render_compose(self.handle, C.byref(rp), k, barr, ptrs, out.ctypes.data, out.nbytes))
         return out
+
+    # ---- fields on a regular grid (include/sph_sample.h; adaptive_sph_amd/sampling.py builds the parameters) ----
+    def _sample_lib(self):
+        if any(getattr(self.lib, s, None) is None for s in SAMPLE_SYMBOLS):
+            raise SphError(30, f"{self.lib.path.name} samples no fields (sph_sample.h is implemented by the product library only)")
+        return self.lib
+
+    def sample_grid(self, params: SphParams, sp: "SphSampleParams", raw: bool = False, host: "HostBuffers" = None):
+        """sph_sample_grid: (values float32[C+1, ny, nx] with plane 0 = the weight and row 0 = the LOWEST y, raw int64[C+1, ny, nx] or None,
+        SphSampleInfo).  `host`: persistent host buffers as in download() -- the arrays are then VIEWS, overwritten by the next call
+        into the same buffers.  Density, pressure and the density volume are the last STEP's outputs: sample right behind the step,
+        before anything edits the particle vector (include/sph_sample.h, "which state")."""
+        lib = self._sample_lib()
+        shape = (1, 1, 1) if sp is None else (max(0, int(sp.n_channels)) + 1, max(0, int(sp.ny)), max(0, int(sp.nx)))
+        if shape[0] > SAMPLE_MAX_CHANNELS + 1 or shape[1] > SAMPLE_MAX_SIDE or shape[2] > SAMPLE_MAX_SIDE:
+            shape = (1, 1, 1)   # (the library refuses the call before it looks at the buffers)
+        count = shape[0] * shape[1] * shape[2]
+        values = np.empty(shape, np.float32) if host is None else host.view("sample:values", np.float32, count).reshape(shape)
+        planes = None
+        if raw:
+            planes = np.empty(shape, np.int64) if host is None else host.view("sample:raw", np.int64, count).reshape(shape)
+        info = SphSampleInfo()
+        self._check(lib.sample_grid(self.handle, C.byref(params) if params is not None else None, C.byref(sp) if sp is not None else None,
+                                    values.ctypes.data if values.size else None, values.nbytes,
+                                    planes.ctypes.data if raw and planes.size else None, planes.nbytes if raw else 0, C.byref(info)))
+        return values, planes, info
+
+    def sample_field_range(self, params: SphParams, field: str, component: int = 0):
+        """sph_sample_field_range: (max |a|, the smallest e with max |a| < 2^e -- 0 for a field of zeros) of one channel."""
+        m, e = C.c_float(0.0), C.c_int32(0)
+        fid = FIELDS[field][0] if isinstance(field, str) else int(field)
+        self._check(self._sample_lib().sample_field_range(self.handle, C.byref(params), fid, int(component), C.byref(m), C.byref(e)))
+        return float(m.value), int(e.value)
 
     def grid(self) -> SphGridInfo:
         g = SphGridInfo()

@@ -108,8 +108,42 @@ def write_vtk_file2(path, positions: np.ndarray, data_ft: List[Tuple[str, np.nda
             f.write(b"\n")
 
 
-class VtkExporter:
-    """`VtkExporter::new(folder, basename)` + `add_snapshot(time, ...)` (:31-80); call `close()` (the reference's Drop, :249-253)."""
+def write_vtk_grid(path, grid, planes):
+    """Sampled fields (sampling.sample_grid) as an image volume: legacy 4.2, BINARY, big-endian, DATASET STRUCTURED_POINTS of
+    nx x ny x 1 points at the sample centres (x fastest, row 0 = the lowest y: the planes' own order).  One SCALARS array per plane in
+    the order given; "velocity_x" and "velocity_y" together become one 3-component VECTORS "velocity" with z = 0, written where
+    "velocity_x" stood.  `grid`: sampling.GridSpec; `planes`: name -> float32[ny, nx] (the reference has no counterpart: it exports
+    particles only)."""
+    nx, ny = int(grid.nx), int(grid.ny)
+    s = float(grid.spacing)
+    planes = dict(planes)
+    for name, a in planes.items():
+        if np.shape(a) != (ny, nx):
+            raise ValueError(f"plane {name!r} has shape {np.shape(a)}, the grid is {ny} x {nx}")
+    vector = "velocity_x" in planes and "velocity_y" in planes
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 4.2\nSPH grid 1.0\nBINARY\nDATASET STRUCTURED_POINTS\n")
+        f.write(f"DIMENSIONS {nx} {ny} 1\n".encode())
+        f.write(f"ORIGIN {float(grid.origin[0]) + 0.5 * s!r} {float(grid.origin[1]) + 0.5 * s!r} 0.0\n".encode())
+        f.write(f"SPACING {s!r} {s!r} 1.0\n".encode())
+        f.write(f"POINT_DATA {nx * ny}\n".encode())
+        for name, a in planes.items():
+            if vector and name == "velocity_y":
+                continue
+            if vector and name == "velocity_x":
+                v = np.zeros((ny, nx, 3), ">f4")
+                v[:, :, 0] = planes["velocity_x"]
+                v[:, :, 1] = planes["velocity_y"]
+                f.write(b"VECTORS velocity float\n")
+                f.write(v.tobytes())
+            else:
+                f.write(f"SCALARS {name} float 1\nLOOKUP_TABLE default\n".encode())
+                f.write(np.asarray(a).astype(">f4").tobytes())
+            f.write(b"\n")
+
+
+class _Series:
+    """The ParaView `<basename>.vtk.series` index both exporters write (vtk_exporter.rs:31-80, 249-253)."""
 
     def __init__(self, folder, basename: str):
         self.folder = str(folder)
@@ -119,11 +153,46 @@ class VtkExporter:
         self.series_file = open(os.path.join(self.folder, f"{basename}.vtk.series"), "w")
         self.series_file.write('{\n"file-series-version": "1.0",\n"files": [')
 
-    def add_snapshot(self, time: float, sim, planes):
-        """`sim`: FluidSimulation mirror (simulation.py); `planes`: what scene.boundary_planes returned for it."""
+    def next_name(self) -> str:
+        return f"{self.basename}-{self.snapshot_number:05d}.vtk"
+
+    def written(self, name: str, time: float):
+        """The snapshot's file exists: enter it into the index."""
         if self.snapshot_number > 1:
             self.series_file.write(",")
-        name = f"{self.basename}-{self.snapshot_number:05d}.vtk"
+        self.series_file.write(f'\n{{ "name": "{name}", "time": {float(time)} }}')
+        self.snapshot_number += 1
+
+    def close(self):
+        if self.series_file:
+            self.series_file.write("\n]\n}")
+            self.series_file.close()
+            self.series_file = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class VtkGridExporter(_Series):
+    """One `write_vtk_grid` file per snapshot, `<basename>-NNNNN.vtk`, plus the same `.vtk.series` index as VtkExporter."""
+
+    def add_snapshot(self, time: float, grid, planes) -> str:
+        name = self.next_name()
+        path = os.path.join(self.folder, name)
+        write_vtk_grid(path, grid, planes)
+        self.written(name, time)
+        return path
+
+
+class VtkExporter(_Series):
+    """`VtkExporter::new(folder, basename)` + `add_snapshot(time, ...)` (:31-80); call `close()` (the reference's Drop, :249-253)."""
+
+    def add_snapshot(self, time: float, sim, planes):
+        """`sim`: FluidSimulation mirror (simulation.py); `planes`: what scene.boundary_planes returned for it."""
+        name = self.next_name()
         p = sim.particles
         pos = p.position
         zeros = np.zeros(len(pos), np.float32)
@@ -141,17 +210,4 @@ class VtkExporter:
         data_vec = [("velocity", p.velocity), ("pressure_accel", p.pressure_accel)]
         data_u8 = [("flag_is_fluid_surface", p.flag_is_fluid_surface), ("flag_neighborhood_reduced", p.flag_neighborhood_reduced)]
         write_vtk_file2(os.path.join(self.folder, name), pos, data_ft, data_vec, data_u8, lines)
-        self.series_file.write(f'\n{{ "name": "{name}", "time": {float(time)} }}')
-        self.snapshot_number += 1
-
-    def close(self):
-        if self.series_file:
-            self.series_file.write("\n]\n}")
-            self.series_file.close()
-            self.series_file = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self.written(name, time)
