@@ -313,6 +313,12 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // fields on a regular grid (sph_sample.hip): the int64 planes, the resolved f32 planes, the words of the range pass and the counts
     // -- allocated on first use, kept across calls, freed by sph_destroy
     DevBuf smp_planes, smp_out, smp_red;
+    // fields from slab contexts (sph_slab_sample.hip): this rank's layer -- smp_layer_planes planes of smp_layer_ny rows of the sample
+    // columns [smp_layer_sx0, smp_layer_sx1), one int64 word per sample -- kept until the next layer call; the words of the band
+    // reduction; the staging of layers that arrive from the host
+    DevBuf smp_layer, smp_band, smp_stage;
+    bool smp_have_layer = false;
+    int smp_layer_sx0 = 0, smp_layer_sx1 = 0, smp_layer_ny = 0, smp_layer_planes = 0;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)

@@ -252,6 +252,33 @@ class SphSampleInfo(C.Structure):
                 ("n_pairs", C.c_uint64)]
 
 
+# include/sph_slab_sample.h: the same planes from slab contexts -- rank layers of int64 sums added on the device (product only)
+SLAB_SAMPLE_SYMBOLS = ["slab_sample_range", "sample_fold_words", "slab_sample_layer", "slab_sample_layer_download", "sample_compose",
+                       "group_sample_grid"]
+SAMPLE_NO_OFFENDER = 0xFFFFFFFFFFFFFFFF
+
+
+class SphSlabSampleWords(C.Structure):
+    """sph_slab_sample_words: a rank's verdict -- (global id << 8 | reason) of its smallest offending owned particle (all ones: none) and
+    max |a| per channel as float bits."""
+    _fields_ = [("first_bad", C.c_uint64), ("max_bits", C.c_uint32 * SAMPLE_MAX_CHANNELS)]
+
+    def as_tuple(self):
+        return int(self.first_bad), tuple(int(b) for b in self.max_bits)
+
+    @classmethod
+    def from_tuple(cls, t):
+        return cls(int(t[0]), (C.c_uint32 * SAMPLE_MAX_CHANNELS)(*[int(b) for b in t[1]]))
+
+
+class SphSampleBand(C.Structure):
+    """sph_sample_band: the sample columns [sx0, sx1) that hold a rank's layer, and the owned particles whose box meets the grid."""
+    _fields_ = [("sx0", C.c_int32), ("sx1", C.c_int32), ("n_boxes", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return int(self.sx0), int(self.sx1), int(self.n_boxes)
+
+
 ABI_SYMBOLS = [
     "create", "destroy", "upload", "upload_field", "download", "download_neighbors", "num_particles", "time",
     "set_time", "step", "classify", "share_particles", "merge_particles", "set_split_patterns", "split_particles", "host_find_partners", "last_error", "grid", "set_boundary_polygon", "set_math_policy", "get_math_policy", "apply_edits", "profile_enable", "profile_reset", "profile_get", "profile_event_overhead", "profile_dispatch_bracket", "profile_copy_bandwidth", "profile_list_forms", "set_sweep_variant",
@@ -442,6 +469,14 @@ class SphLibrary:
                                required=False)
         self.sample_field_range = sig("sample_field_range", i32, [vp, C.POINTER(SphParams), i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
                                       required=False)
+        spp, sbp, swp = C.POINTER(SphSampleParams), C.POINTER(SphSampleBand), C.POINTER(SphSlabSampleWords)
+        self.slab_sample_range = sig("slab_sample_range", i32, [vp, C.POINTER(SphParams), spp, swp], required=False)
+        self.sample_fold_words = sig("sample_fold_words", i32, [i32, swp, spp, C.c_char_p, u64], required=False)
+        self.slab_sample_layer = sig("slab_sample_layer", i32, [vp, C.POINTER(SphParams), spp, sbp, C.POINTER(SphSampleInfo)], required=False)
+        self.slab_sample_layer_download = sig("slab_sample_layer_download", i32, [vp, vp, u64], required=False)
+        self.sample_compose = sig("sample_compose", i32, [vp, spp, i32, sbp, C.POINTER(vp), vp, u64, vp, u64], required=False)
+        self.group_sample_grid = sig("group_sample_grid", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), spp, vp, u64, vp, u64, C.POINTER(SphSampleInfo)],
+                                     required=False)
 
 
 _PRODUCT = None
@@ -1034,6 +1069,61 @@ class Context:
         self._check(self._sample_lib().sample_field_range(self.handle, C.byref(params), fid, int(component), C.byref(m), C.byref(e)))
         return float(m.value), int(e.value)
 
+    # ---- the same planes from slab contexts (include/sph_slab_sample.h; adaptive_sph_amd/sampling.py: sample_group, sample_rank) ----
+    def _slab_sample_lib(self):
+        return _slab_sample_lib(self.lib)
+
+    def slab_sample_range(self, params: SphParams, sp: "SphSampleParams") -> "SphSlabSampleWords":
+        """sph_slab_sample_range: this rank's verdict over its owned particles -- the smallest offending global id and max |a| per
+        channel.  The ranks' words go to sample_fold_words."""
+        w = SphSlabSampleWords()
+        self._check(self._slab_sample_lib().slab_sample_range(self.handle, C.byref(params) if params is not None else None,
+                                                              C.byref(sp) if sp is not None else None, C.byref(w)))
+        return w
+
+    def slab_sample_layer(self, params: SphParams, sp: "SphSampleParams"):
+        """sph_slab_sample_layer: scatter this rank's owned particles into its layer (kept on the device) with sp's EXPLICIT exponents
+        -> (the band of sample columns, SphSampleInfo with the rank's own counts)."""
+        band, info = SphSampleBand(), SphSampleInfo()
+        self._sample_layer_shape = None
+        self._check(self._slab_sample_lib().slab_sample_layer(self.handle, C.byref(params) if params is not None else None,
+                                                              C.byref(sp) if sp is not None else None, C.byref(band), C.byref(info)))
+        self._sample_layer_shape = (int(sp.n_channels) + 1, int(sp.ny), int(band.sx1) - int(band.sx0))
+        return band, info
+
+    def slab_sample_layer_download(self) -> np.ndarray:
+        """sph_slab_sample_layer_download: the layer scattered last as int64[C+1, ny, sx1 - sx0], plane 0 = the weight's sums, row 0 = the
+        lowest y: the sums of the rank's owned particles' terms at the band's samples."""
+        lib = self._slab_sample_lib()
+        shape = getattr(self, "_sample_layer_shape", None)
+        if shape is None:   # (no layer call through this object: the library says what is missing)
+            self._check(lib.slab_sample_layer_download(self.handle, None, 0))
+            return np.zeros((0, 0, 0), np.int64)
+        out = np.empty(shape, np.int64)
+        self._check(lib.slab_sample_layer_download(self.handle, out.ctypes.data if out.size else None, out.size))
+        return out
+
+    def sample_compose(self, sp: "SphSampleParams", bands, layers, raw: bool = False, host: "HostBuffers" = None):
+        """sph_sample_compose on this context (plain or slab): the ranks' layers -> (values float32[C+1, ny, nx], raw int64[C+1, ny, nx] or
+        None).  layers[k]: int64[C+1, ny, sx1 - sx0] of bands[k], or None for an empty band; sp holds explicit exponents; `host` as in sample_grid."""
+        lib = self._slab_sample_lib()
+        k = len(bands)
+        barr = (SphSampleBand * max(1, k))()
+        ptrs = (C.c_void_p * max(1, k))()
+        keep = []
+        for i, (b, l) in enumerate(zip(bands, layers)):
+            barr[i] = SphSampleBand(int(b.sx0), int(b.sx1), int(b.n_boxes), 0)
+            if l is not None and np.asarray(l).size:
+                a = np.ascontiguousarray(l, np.int64)
+                keep.append(a)
+                ptrs[i] = a.ctypes.data
+            else:
+                ptrs[i] = None
+        values, planes = _sample_buffers(sp, raw, host)
+        self._check(lib.sample_compose(self.handle, C.byref(sp) if sp is not None else None, k, barr, ptrs, values.ctypes.data if values.size else None,
+                                       values.nbytes, planes.ctypes.data if raw and planes.size else None, planes.nbytes if raw else 0))
+        return values, planes
+
     def grid(self) -> SphGridInfo:
         g = SphGridInfo()
         self._check(self.lib.grid(self.handle, C.byref(g)))
@@ -1339,3 +1429,61 @@ def group_render(contexts, params: SphParams, rp: "SphRenderParams") -> np.ndarr
     for c in contexts:
         c._layer_shape = None   # (the members' layers were redrawn; their bands stayed in the library)
     return out
+
+
+# ---- fields on a regular grid from slab contexts (include/sph_slab_sample.h) ---------------------------------------------------
+def _slab_sample_lib(lib):
+    if any(getattr(lib, s, None) is None for s in SLAB_SAMPLE_SYMBOLS):
+        raise SphError(30, f"{lib.path.name} samples no slab contexts (sph_slab_sample.h is implemented by the product library only)")
+    return lib
+
+
+def _sample_buffers(sp, raw: bool, host: "HostBuffers" = None):
+    """(values float32[C+1, ny, nx], raw int64 of the same shape or None) for sp; one sample where the library refuses sp's shape before
+    it looks at the buffers.  `host`: persistent host buffers as in Context.sample_grid -- the arrays are then views."""
+    shape = (1, 1, 1) if sp is None else (max(0, int(sp.n_channels)) + 1, max(0, int(sp.ny)), max(0, int(sp.nx)))
+    if shape[0] > SAMPLE_MAX_CHANNELS + 1 or shape[1] > SAMPLE_MAX_SIDE or shape[2] > SAMPLE_MAX_SIDE:
+        shape = (1, 1, 1)
+    count = shape[0] * shape[1] * shape[2]
+    if host is None:
+        return np.empty(shape, np.float32), (np.empty(shape, np.int64) if raw else None)
+    return host.view("sample:values", np.float32, count).reshape(shape), (host.view("sample:raw", np.int64, count).reshape(shape) if raw else None)
+
+
+def sample_fold_words(lib: "SphLibrary", words, sp: "SphSampleParams", msg_bytes: int = 512) -> "SphSampleParams":
+    """sph_sample_fold_words (no device, no context): the ranks' verdicts -> a copy of `sp` whose automatic exponents are those of the
+    whole vector.  Raises SphError(1) with the sentence sph_sample_grid writes when a particle offends (the smallest global id over
+    the ranks) or an exponent is out of range: the same on every rank that folds the same words."""
+    lib = _slab_sample_lib(lib)
+    words = list(words)
+    arr = (SphSlabSampleWords * max(1, len(words)))()
+    for i, w in enumerate(words):
+        arr[i] = w if isinstance(w, SphSlabSampleWords) else SphSlabSampleWords.from_tuple(w)
+    out = SphSampleParams.from_buffer_copy(sp)
+    msg = C.create_string_buffer(max(1, int(msg_bytes)))
+    rc = lib.sample_fold_words(len(words), arr, C.byref(out), msg, int(msg_bytes))
+    if rc != 0:
+        raise SphError(rc, msg.value.decode(errors="replace"))
+    return out
+
+
+def group_sample_grid(contexts, params: SphParams, sp: "SphSampleParams", raw: bool = False, host: "HostBuffers" = None):
+    """sph_group_sample_grid: the planes of the k slab contexts of this process (the group sph_group_step steps): every member scatters
+    its layer, member 0 adds them on the device -> (values, raw or None, SphSampleInfo) as Context.sample_grid returns them (`host` as
+    there)."""
+    contexts = list(contexts)
+    if not contexts:
+        raise SphError(1, "sph_group_sample_grid: n < 1 (no contexts)")
+    lib = _slab_sample_lib(contexts[0].lib)
+    k = len(contexts)
+    handles = (C.c_void_p * k)(*[c.handle for c in contexts])
+    values, planes = _sample_buffers(sp, raw, host)
+    info = SphSampleInfo()
+    rc = lib.group_sample_grid(handles, k, C.byref(params) if params is not None else None, C.byref(sp) if sp is not None else None,
+                               values.ctypes.data if values.size else None, values.nbytes, planes.ctypes.data if raw and planes.size else None,
+                               planes.nbytes if raw else 0, C.byref(info))
+    if rc != 0:   # (whichever member refused, the library leaves the sentence in member 0's last error)
+        raise SphError(rc, lib.last_error(contexts[0].handle).decode(errors="replace"))
+    for c in contexts:
+        c._sample_layer_shape = None   # (the members' layers were scattered again; their bands stayed in the library)
+    return values, planes, info

@@ -1,5 +1,6 @@
 """SPH fields on a regular grid, sampled on the device (include/sph_sample.h): the parameters of `Context.sample_grid`, named planes,
-and `resolve`, the host twin of the device's last kernel.
+and `resolve`, the host twin of the device's last kernel; `sample_group` and `sample_rank` give the same planes from slab contexts
+(include/sph_slab_sample.h).
 
 The device accumulates every sum as a 64-bit fixed-point integer, so the RAW planes do not depend on any order and the raw planes of
 disjoint particle sets add exactly: a host that holds the layers of several contexts adds them and resolves the sum with `resolve`.
@@ -97,9 +98,7 @@ def sample_grid(ctx, P, grid: GridSpec, channels: Sequence[str], volume="density
     sp = sample_params(grid, names, volume, normalize, min_weight, fill, exponents)
     p = P.to_ffi() if hasattr(P, "to_ffi") else P
     values, planes, info = ctx.sample_grid(p, sp, raw=raw, host=host)
-    keys = ["weight"] + names
-    return SampledPlanes(grid, {k: values[i] for i, k in enumerate(keys)}, {k: int(info.exponents[i]) for i, k in enumerate(names)},
-                         int(info.n_touching), int(info.max_footprint), int(info.n_pairs), {k: planes[i] for i, k in enumerate(keys)} if raw else None)
+    return _planes_of(grid, names, values, planes, info.exponents, (info.n_touching, info.max_footprint, info.n_pairs), raw)
 
 
 def resolve(raw: np.ndarray, exponents: Sequence[int], normalize=False, min_weight=0.5, fill=float("nan")) -> np.ndarray:
@@ -119,3 +118,60 @@ def resolve(raw: np.ndarray, exponents: Sequence[int], normalize=False, min_weig
                 v = np.where(keep, v / weight, np.float32(fill)).astype(np.float32)
         out[c + 1] = v
     return out
+
+
+# ---- the same planes from slab contexts (include/sph_slab_sample.h) --------------------------------------------------------------
+def _planes_of(grid, names, values, planes, exponents, counts, raw) -> SampledPlanes:
+    keys = ["weight"] + names
+    return SampledPlanes(grid, {k: values[i] for i, k in enumerate(keys)}, {k: int(exponents[i]) for i, k in enumerate(names)},
+                         int(counts[0]), int(counts[1]), int(counts[2]), {k: planes[i] for i, k in enumerate(keys)} if raw else None)
+
+
+def sample_group(contexts, P, grid: GridSpec, channels: Sequence[str], volume="density", normalize=False, min_weight=0.5, fill=float("nan"),
+                 exponents=None, raw=False, host=None) -> SampledPlanes:
+    """The planes of a slab group of ONE process (the contexts ffi.group_step steps): bit for bit what `sample_grid` returns for one
+    context that holds the same particles.  The members agree on the exponents and the preconditions through one set of words on the
+    device, every member scatters the particles it owns into a layer of int64 sums, member 0 adds the layers (sph_group_sample_grid);
+    only the planes cross the bus.  Keywords as `sample_grid`."""
+    names = expand_channels(channels)
+    sp = sample_params(grid, names, volume, normalize, min_weight, fill, exponents)
+    p = P.to_ffi() if hasattr(P, "to_ffi") else P
+    values, planes, info = ffi.group_sample_grid(contexts, p, sp, raw=raw, host=host)
+    return _planes_of(grid, names, values, planes, info.exponents, (info.n_touching, info.max_footprint, info.n_pairs), raw)
+
+
+def sample_rank(ctx, P, grid: GridSpec, channels: Sequence[str], volume="density", normalize=False, min_weight=0.5, fill=float("nan"),
+                exponents=None, raw=False, host=None, root: int = 0) -> Optional[SampledPlanes]:
+    """The same planes with ONE PROCESS PER RANK: every rank calls this behind the same step.  The ranks' verdict words are
+    all-gathered through the launcher's process group (torch.distributed all_gather_object) and folded on every rank -- every rank
+    takes the same exponents or raises the same refusal, naming the smallest offending global id --, every rank scatters its layer
+    and sends `root` its (band, counts, layer) (gather_object, as render.render_rank sends its layers), `root` composes them on its own
+    context.  Returns the planes on `root`, None elsewhere; a failure on the root is re-raised on every rank."""
+    import torch.distributed as dist
+    names = expand_channels(channels)
+    sp = sample_params(grid, names, volume, normalize, min_weight, fill, exponents)
+    p = P.to_ffi() if hasattr(P, "to_ffi") else P
+    rank, world = dist.get_rank(), dist.get_world_size()
+    words = [None] * world
+    dist.all_gather_object(words, ctx.slab_sample_range(p, sp).as_tuple())
+    sp = ffi.sample_fold_words(ctx.lib, words, sp)   # (raises the same SphError on every rank)
+    band, info = ctx.slab_sample_layer(p, sp)
+    layer = ctx.slab_sample_layer_download() if band.sx1 > band.sx0 else None
+    parts = [None] * world if rank == root else None
+    dist.gather_object((band.as_tuple(), (int(info.n_touching), int(info.max_footprint), int(info.n_pairs)), layer), parts, dst=root)
+    out, result = [None], None
+    if rank == root:
+        try:
+            bands = [ffi.SphSampleBand(b[0], b[1], b[2], 0) for b, _, _ in parts]
+            values, planes = ctx.sample_compose(sp, bands, [l for _, _, l in parts], raw=raw, host=host)
+            counts = (sum(c[0] for _, c, _ in parts), max(c[1] for _, c, _ in parts), sum(c[2] for _, c, _ in parts))
+            result = _planes_of(grid, names, values, planes, [sp.channels[k].exponent for k in range(len(names))], counts, raw)
+        except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
+            out = [(type(e).__name__, e.status if isinstance(e, ffi.SphError) else None, str(e))]
+    dist.broadcast_object_list(out, src=root)
+    if out[0] is not None:
+        kind, code, msg = out[0]
+        if code is not None:
+            raise ffi.SphError(code, f"sample failed on rank {root}: {msg}")
+        raise RuntimeError(f"sample failed on rank {root} ({kind}): {msg}")
+    return result

@@ -35,8 +35,8 @@
  *
  * EXPONENTS.  e_c is the smallest integer with max_j |a_j| < 2^e_c, or 0 when the maximum is 0.  The caller gives it, or gives
  * SPH_SAMPLE_AUTO_EXPONENT: the library then takes it from an exact reduction on the device (the maximum of the bit patterns of
- * |a_j|, which order like the values) -- sph_sample_field_range exposes the same reduction, for hosts whose ranks must agree on an
- * exponent.  Allowed: SPH_SAMPLE_MIN_EXPONENT .. SPH_SAMPLE_MAX_EXPONENT; an automatic exponent below the range is raised to its lower
+ * |a_j|, which order like the values) -- sph_sample_field_range exposes the same reduction on a plain context; the ranks of a slab
+ * decomposition agree on an exponent through sph_slab_sample.h.  Allowed: SPH_SAMPLE_MIN_EXPONENT .. SPH_SAMPLE_MAX_EXPONENT; an automatic exponent below the range is raised to its lower
  * end, one above it is refused.  The exponents used come back in sph_sample_info.
  *
  * THE RESOLVED OUTPUT (f32 planes, (C+1) x ny x nx, plane 0 = the weight):
@@ -65,8 +65,8 @@
  * Status codes are those of sph_ffi.h: SPH_ERR_INVALID_ARGUMENT (nx or ny outside 1..SPH_SAMPLE_MAX_SIDE, (C+1)*nx*ny*8 above 2 GiB,
  * spacing not finite or <= 0, origin not finite, an unknown field, a component the field does not have, more than
  * SPH_SAMPLE_MAX_CHANNELS channels, an unknown volume mode, an exponent outside the range, a short output buffer, a precondition),
- * SPH_ERR_POISONED, SPH_ERR_UNSUPPORTED (slab contexts: one rank holds a slab of the particles -- the composition of the ranks' RAW
- * planes is exact addition), SPH_ERR_DEVICE.  Nothing here reads a flag of the simulation state or changes it; every launch runs on
+ * SPH_ERR_POISONED, SPH_ERR_UNSUPPORTED (slab contexts: one rank holds a slab of the particles -- sph_slab_sample.h samples them: the
+ * composition of the ranks' RAW planes is exact addition), SPH_ERR_DEVICE.  Nothing here reads a flag of the simulation state or changes it; every launch runs on
  * the context's stream; the buffers are allocated on first use, reused, and freed by sph_destroy.
  */
 #ifndef SPH_SAMPLE_H
