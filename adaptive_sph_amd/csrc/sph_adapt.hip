@@ -31,6 +31,7 @@ static int slab_adapt_rank(sph_ctx* c, int op, const sph_params* p, const sph_ad
 #define ADAPT_CHECK(c, OP, PARTNER, COUNTER)                                                                                    \
     if (!(c) || !p || !ap) return SPH_ERR_INVALID_ARGUMENT;                                                                     \
     if ((c)->poisoned) return (c)->refuse_poisoned();                                                                           \
+    (c)->lvl_pristine = false; /* every adaptivity entry point: the reorders move the level fields again */                    \
     if ((c)->dist.on) return slab_adapt_rank((c), (OP), p, ap, (PARTNER), (COUNTER))
 
 // ---- exclusive prefix sum (u32), three launches: block sums, scan of the block sums, local scans ------------------------
@@ -357,6 +358,7 @@ int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* 
     int rc = check_status(c, "merge_partner holds an index outside the particle vector");
     // positions and masses changed: what the last step left behind no longer describes the state
     c->drop(DROPS_TRANSFER);
+    c->lvl_pristine = false;   // (an adaptivity entry point: the level fields may take other values)
     // (sharing neither reorders nor resizes the vector: stash and the step's flags keep describing the particles in their slots,
     //  as the reference's ParticleVec keeps them through share_particles -- snapshots taken after single_step show them)
     if (rc || !merging) {
@@ -373,6 +375,7 @@ int transfer_on_device(sph_ctx* c, const sph_params* p, const sph_adapt_params* 
         release();
         return SPH_OK;
     }
+    c->lvl_pristine = false;
     c->drop(DROPS_DELETION);   // the deletion reorders the vector: per-step outputs that do not travel (stash, flags) are gone
     // (the reference's loop never removes the particle it ends on when everything is deleted: last_particle_id is a usize that
     //  would underflow -- it panics there; an empty vector is what truncate(0) would leave)
@@ -709,6 +712,7 @@ static void slab_after_regather(sph_ctx* c, uint32_t n_new)
     c->dist.n_tot = n_new;
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
     c->drop(DROPS_REGATHER);
+    c->lvl_pristine = false;   // (the regather writes one half of the level fields only)
 }
 
 // The decisions of a COMPACT problem (include/sph_slab_partner_problem.h): k participants by ascending global id, a partner named by its
@@ -805,6 +809,7 @@ static int slab_adapt(Group& G, int op, const sph_params* p, const sph_adapt_par
             HIPCHK(c, hipMemcpyAsync(c->pm[c->pcur].p, c->pm[c->pcur ^ 1].p, (size_t)nt * sizeof(float4), hipMemcpyDeviceToDevice, s));
             HIPCHK(c, hipMemcpyAsync(c->vel[k].p, c->vel[k ^ 1].p, (size_t)nt * sizeof(float2), hipMemcpyDeviceToDevice, s));
             r = check_status(c, "merge_partner holds an index outside the particle vector, or a donor that is not a neighbour of its receiver");
+            c->lvl_pristine = false;
             c->drop(DROPS_TRANSFER);   // (also behind a failed check: the records were written)
             return r;
         });

@@ -498,6 +498,8 @@ Options options_from_env()
     o.ahead_build = num("SPH_AHEAD_BUILD", 1) != 0 ? 1 : 0;
     o.inc_sort = num("SPH_INC_SORT", 1);
     o.boundary_fused = num("SPH_BOUNDARY_FUSED", 1) != 0 ? 1 : 0;
+    o.fuse_records = num("SPH_FUSE_RECORDS", 1) != 0 ? 1 : 0;
+    o.level_move_always = num("SPH_LEVEL_MOVE_ALWAYS", 0) != 0 ? 1 : 0;
     o.slab_paced = num("SPH_SLAB_PACED", 1) != 0 ? 1 : 0;
     o.slab_records = num("SPH_SLAB_RECORDS", 1) != 0 ? 1 : 0;
     o.side_cus = num("SPH_SIDE_CUS", 0);
@@ -510,7 +512,7 @@ Options options_from_env()
     // libsph_hip.so would otherwise run the defaults in every row and report nothing)
     static const char* const lab_only[] = {"SPH_PACED", "SPH_PACE_LEAD", "SPH_PACE_PRED", "SPH_CHAIN", "SPH_ACCEL_GENERIC", "SPH_JACOBI_GENERIC", "SPH_SOURCE_GENERIC",
                                            "SPH_SLAB_GENERAL", "SPH_SLAB_LEVEL_PLAIN", "SPH_LEVEL_SERIAL", "SPH_LEVEL_BATCH8", "SPH_LEVEL_QUEUE", "SPH_OFFSET_LISTS",
-                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_BOUNDARY_FUSED", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
+                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_BOUNDARY_FUSED", "SPH_FUSE_RECORDS", "SPH_LEVEL_MOVE_ALWAYS", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
                                            "SPH_SIDE_CUS", "SPH_MAIN_EXCLUDE", "SPH_IPC_FUSE_MAX_BYTES", "SPH_IPC_COPY_MIN_BYTES"};
     static bool warned = false;
     if (!warned)
@@ -641,7 +643,7 @@ extern "C" void sph_destroy(sph_ctx* c)
     DevBuf* all[] = {&c->pm[0], &c->pm[1], &c->vel[0], &c->vel[1], &c->orig[0], &c->orig[1], &c->lvl[0], &c->lvl[1], &c->lvlold[0],
                      &c->lvlold[1], &c->vel_tmp, &c->key[0], &c->key[1], &c->val[0], &c->val[1], &c->sort_scratch, &c->cxy, &c->cell_start,
                      &c->cs_scratch, &c->hdr_ahead_partials, &c->h2n[0], &c->h2n[1], &c->lam_prev, &c->nl, &c->nlx, &c->tile_raw, &c->tile_h, &c->tile_h_ext, &c->lvl_changed_d, &c->lvl_tmp, &c->lvl_nrm, &c->lvl_state, &c->lvl_when, &c->lvl_mark, &c->lvl_queue, &c->nloff, &c->nlh, &c->flag_surface,
-                     &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
+                     &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->xvn, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->inc_local, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage,
@@ -719,6 +721,10 @@ extern "C" int sph_upload(sph_ctx* c, uint64_t n, const float* mass, const float
     hipLaunchKernelGGL(k_pack_upload, dim3((n + 255) / 256), dim3(256), 0, s, (uint32_t)n, c->key[1].as<float>(), c->scratch.as<float2>(),
                        c->vel_tmp.as<float2>(), c->pm[0].as<float4>(), c->vel[0].as<float2>(), c->orig[0].as<uint32_t>(),
                        c->lvl[0].as<float>(), c->lvlold[0].as<float>(), c->h2n[0].as<float>());
+    // (the other half of the level fields holds the same constants: while nothing writes another value, no reorder has to move them)
+    HIPCHK(c, hipMemcpyAsync(c->lvl[1].p, c->lvl[0].p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->lvlold[1].p, 0, n * sizeof(float), s));
+    c->lvl_pristine = true;
     HIPCHK(c, hipMemsetAsync(c->szc[0].p, 2, n, s));   // ParticleSizeClass::Optimal (simulation.rs:318)
     DevBuf* zero[] = {&c->rho, &c->lam_sum, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->dens_err, &c->ncount};
     for (auto b : zero) HIPCHK(c, hipMemsetAsync(b->p, 0, n * sizeof(float), s));
@@ -927,6 +933,7 @@ extern "C" int sph_apply_edits(sph_ctx* c, const sph_edit_op* ops, uint64_t n_op
     if (c->poisoned) return c->refuse_poisoned();
     HIPCHK(c, hipSetDevice(c->device));
     c->drop(DROPS_EDITS_EARLY);
+    c->lvl_pristine = false;   // (an edit may set either level field, and the regather writes one half only)
     const uint32_t n_old = (uint32_t)c->n;
     // ---- resolve the script: which object sits at which index, and the last value written to each field of an object
     std::vector<uint32_t> at(n_old);
@@ -1037,6 +1044,7 @@ int regather_host_order(sph_ctx* c, uint32_t n_new, const EditSrc* d_src, const 
     c->n = n_new;
     c->dist.n_tot = n_new;
     c->dist.n_ghost[0] = c->dist.n_ghost[1] = c->dist.n_halo[0] = c->dist.n_halo[1] = 0;
+    c->lvl_pristine = false;
     c->drop(DROPS_REGATHER);   // (slab context: owned particles only, in row order; the next step selects new ghosts)
     return SPH_OK;
 }
@@ -1054,6 +1062,7 @@ extern "C" int sph_upload_field(sph_ctx* c, int field, const void* src, uint64_t
     const uint32_t n = (uint32_t)c->n;
     static_assert(CARRY_F_MASS == SPH_F_MASS && CARRY_F_POSITION == SPH_F_POSITION && CARRY_F_PARTICLE_ID == SPH_F_PARTICLE_ID, "sph_carry.hpp: field codes");
     c->drop(drops_upload_field(field));
+    if (field == SPH_F_LEVEL_ESTIMATION || field == SPH_F_LEVEL_OLD) c->lvl_pristine = false;   // (from the next reorder on the level fields move again)
     if (bytes != (uint64_t)n * r.elem) return c->fail(SPH_ERR_INVALID_ARGUMENT, "field %d: size mismatch", field);
     if (n == 0) return SPH_OK;
     hipStream_t s = c->stream;

@@ -76,6 +76,8 @@ struct Options {
     int ahead_build = 1;        // SPH_AHEAD_BUILD=0        one context: never queue the next step's cell sort behind the integrating tail
     int inc_sort = 1;           // SPH_INC_SORT=0 | k       the cell sort queued ahead is always the radix sort (never the incremental merge); k > 1: the merge up to n / k movers (default n / 3: at 4M the merge still beats the radix sort with a third of the particles changing cell)
     int boundary_fused = 1;     // SPH_BOUNDARY_FUSED=0     the merge queued ahead in five launches (tail, k_header_ahead, count, k_inc_scan, place) instead of three (tail, count with the header reduction, place with the block sums' prefix)
+    int fuse_records = 1;       // SPH_FUSE_RECORDS=0       the fused a_ii / force sweep always through OpFuse (four gathers per neighbour); no record out of the place launch
+    int level_move_always = 0;  // SPH_LEVEL_MOVE_ALWAYS=1  every reorder moves the level fields, also while they hold the upload's constants (sph_ctx::lvl_pristine)
     int slab_paced = 1;         // SPH_SLAB_PACED=0         slabs: predicted queue instead of pacing
     int slab_records = 1;       // SPH_SLAB_RECORDS=0       slabs: sweep A through the generic form (p / rho^2 as a field of its own)
     int debug_sync = 0;         // SPH_DEBUG_SYNC=<mask>    synchronise and name the phases (fault hunting)
@@ -174,10 +176,16 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // persistent SoA (ping-pong across the per-step reorder)
     DevBuf pm[2], vel[2], orig[2], lvl[2], lvlold[2];
     int cur = 0;   // which of the (vel, orig, lvl, lvlold) ping-pong set is live
+    // lvl and lvlold hold the upload's constants (FluidInterior, 0) in every slot of BOTH halves: a permutation of them is a no-op and
+    // the reorders leave them where they are (sph_step.hip: reorder_io).  Set by sph_upload, which fills both halves; cleared, for good,
+    // by whatever may write another value: a step with a level estimation, an upload or an edit of either field, every adaptivity and
+    // regather entry point, a slab configuration.  Not a Carry bit: nothing a step leaves behind hangs on it.
+    bool lvl_pristine = false;
     int pcur = 0;  // which pm buffer is live; the other one holds the sorted PRE-step positions after a step
     DevBuf vel_tmp;
     // per-step
     DevBuf key[2], val[2], sort_scratch, cxy, cell_start, cs_scratch, nl, nl_ok, mrho, pt0, pt1, prec0, prec1, xv;
+    DevBuf xvn;   // the record of the fused a_ii / force sweep (OpFuseU): {x, y, v} out of the place launch of the build queued ahead, in the NEXT step's order; allocated by the first build that writes it
     bool uniform_h = false;
     float h_uniform = 0.f;
     DevBuf wall_pl, wall_cnt;   // EXACT policy only (MathExact, sph_device.h)
@@ -275,6 +283,7 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
         float h_max = 0.f, h_min = 0.f, rest_density = 0.f;
         int tile_ts = 0, tile_tsx = 0, tile_tsy = 0;   // multi-resolution scenes: the tiles of the predicted grid
         uint64_t n = 0;
+        bool xv_rec = false;   // its place launch left {x, y, v} in xvn (the step that adopts it may run OpFuseU; gone with ahead_valid)
     } ahead;
     DevBuf hdr_ahead_partials;   // per sweep block: next step's header terms from the integrating final sweep
     float hdr_ahead_rest_density = 0.f;   // (of the header computed ahead: hdr_ahead)

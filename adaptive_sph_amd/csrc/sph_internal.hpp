@@ -199,6 +199,10 @@ struct ReorderIO {   // the per-particle arrays a reorder moves (h2n, lam, szc: 
     float* lam_prev_out;
     const uint8_t* szc_in;
     uint8_t* szc_out;
+    // lvl_in == nullptr (launch-uniform): the level fields hold the upload's constants in every slot of both halves and are not moved
+    // (sph_ctx::lvl_pristine).  xv_out != nullptr: the merge's place launch also leaves {x, y, vx, vy} of every particle in its new
+    // slot, the record the next step's fused a_ii / force sweep gathers (OpFuseU)
+    float4* xv_out = nullptr;
 };
 size_t incremental_sort_block_sums(uint32_t ncells);
 // `fused` (the build a plain context queues ahead behind its integrating tail, classified by that tail): count and place in TWO
@@ -298,6 +302,9 @@ struct SweepArgs {
     float4* xv = nullptr;     // {x, y, vx, vy}: what the source-term sweep of such a scene gathers per neighbour (OpSourceU) -- written by whoever
     bool xv_ok = false;       // writes the velocities behind the step's sort (the non-pressure forces, the divergence solve's tail); xv_ok: it
                               // holds the current positions and velocities (set by the step driver behind those launches); nullptr: slabs, IISPH2
+    // the fused a_ii / force sweep of such a scene on records (OpFuseU): xv_in = {x, y, vx, vy} in this step's order, left by the place
+    // launch of the build this step adopted (nullptr: it left none -- another build, or something dropped it)
+    const float4* xv_in = nullptr;
     // boundary
     const BoundaryP* planes;
     const float* lam_lut;
@@ -318,6 +325,7 @@ struct SweepArgs {
 // in pt0 / pt1: what a slab decomposition exchanges for its ghosts per iteration is then word 2 of those records
 bool sweep_a_on_records(const SweepArgs& a);
 bool source_term_on_records(const SweepArgs& a);   // the step driver sets SweepArgs::xv_ok behind the launches that write the record
+bool fused_sweep_on_records(const SweepArgs& a);   // launch_aii_const_non_pressure runs OpFuseU (xv_in set by the step driver)
 size_t sweep_list_bytes(uint32_t n);
 size_t sweep_index_list_bytes(uint32_t n);   // explicit index lists (multi-resolution scenes)
 size_t sweep_offset_list_bytes(uint32_t n);  // relative-offset lists (uniform scenes whose solves run on records)

@@ -480,8 +480,10 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
         pm = io.pm_in[i];
         vel = io.vel_in[i];
         orig = io.orig_in[i];
-        lvl = io.lvl_in[i];
-        lvlold = io.lvlold_in[i];
+        if (io.lvl_in) {   // (launch-uniform; nullptr: both level fields hold the upload's constants in every slot of both halves)
+            lvl = io.lvl_in[i];
+            lvlold = io.lvlold_in[i];
+        }
     }
     const unsigned long long h = head[c];
     uint32_t first = cell_start_nxt[c];
@@ -535,8 +537,11 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
     io.pm_out[dst] = pm;
     io.vel_out[dst] = vel;
     io.orig_out[dst] = orig;
-    io.lvl_out[dst] = lvl;
-    io.lvlold_out[dst] = lvlold;
+    if (io.xv_out) io.xv_out[dst] = make_float4(pm.x, pm.y, vel.x, vel.y);   // (launch-uniform: the record of the next step's OpFuseU)
+    if (io.lvl_in) {
+        io.lvl_out[dst] = lvl;
+        io.lvlold_out[dst] = lvlold;
+    }
     if (io.h2n_in) io.h2n_out[dst] = io.h2n_in[i];
     if (io.lam_in) io.lam_prev_out[dst] = io.lam_in[i];
     if (io.szc_in) io.szc_out[dst] = io.szc_in[i];
@@ -635,8 +640,10 @@ __global__ __launch_bounds__(256) void k_reorder(uint32_t n, GridP g, const uint
     pm_out[i] = pm_in[src];
     vel_out[i] = vel_in[src];
     orig_out[i] = orig_in[src];
-    lvl_out[i] = lvl_in[src];
-    lvlold_out[i] = lvlold_in[src];
+    if (lvl_in) {   // (launch-uniform: see ReorderIO)
+        lvl_out[i] = lvl_in[src];
+        lvlold_out[i] = lvlold_in[src];
+    }
     uint32_t k = sorted_key[i];
     uint32_t cy = k / (uint32_t)g.sx;
     uint32_t cx = k - cy * (uint32_t)g.sx;

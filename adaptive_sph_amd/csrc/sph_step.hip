@@ -672,9 +672,12 @@ static int pressure_iterations(Group& G, std::vector<Member>& M, const SolveSpec
 ReorderIO reorder_io(sph_ctx* c, const float4* pm_in, float4* pm_out, uint32_t* cxy, bool lam)
 {
     const int k = c->cur;
-    return ReorderIO{pm_in, c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(), c->lvl[k].as<float>(), c->lvlold[k].as<float>(), pm_out, c->vel[k ^ 1].as<float2>(),
-                     c->orig[k ^ 1].as<uint32_t>(), c->lvl[k ^ 1].as<float>(), c->lvlold[k ^ 1].as<float>(), cxy, c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(),
-                     lam ? c->lam_sum.as<float>() : nullptr, lam ? c->lam_prev.as<float>() : nullptr, c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>()};
+    // (level fields that hold the upload's constants in every slot of both halves stay where they are: sph_ctx::lvl_pristine)
+    const bool lvl = !(c->lvl_pristine && !c->dist.on && !c->opt.level_move_always);
+    return ReorderIO{pm_in, c->vel[k].as<float2>(), c->orig[k].as<uint32_t>(), lvl ? c->lvl[k].as<float>() : nullptr, lvl ? c->lvlold[k].as<float>() : nullptr, pm_out,
+                     c->vel[k ^ 1].as<float2>(), c->orig[k ^ 1].as<uint32_t>(), lvl ? c->lvl[k ^ 1].as<float>() : nullptr, lvl ? c->lvlold[k ^ 1].as<float>() : nullptr, cxy,
+                     c->h2n[k].as<float>(), c->h2n[k ^ 1].as<float>(), lam ? c->lam_sum.as<float>() : nullptr, lam ? c->lam_prev.as<float>() : nullptr,
+                     c->szc[k].as<uint8_t>(), c->szc[k ^ 1].as<uint8_t>()};
 }
 
 // The build through the radix sort: cell keys (made by the sort's first pass) -> stable sort -> reorder -> cell ranges, on the buffers of
@@ -834,8 +837,14 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     for (auto c : G.m)
         if (c->poisoned) return c->refuse_poisoned();
     *started = true;   // from here on a failure leaves the state half-stepped
+    if (level_on)
+        for (auto c : G.m) c->lvl_pristine = false;   // (this step writes the level fields: every reorder from here on moves them)
     // measurement / test switches of the solves, read ONCE per step (never inside the iteration path)
     const bool no_records = c0->opt.accel_generic != 0;   // sweep A through the generic form
+    // the non-pressure acceleration directly follows constant_field + a_ii in every mode but HybridDFSPH-with-forces-behind-the-
+    // divergence-solve: then it shares the sweep (one replay of the lists, one gradient per pair)
+    const bool np_first = p->pressure_solver_method != SPH_SOLVER_HYBRID_DFSPH || p->hybrid_dfsph_non_pressure_accel_before_divergence_free;
+    const bool np_fused = np_first && !p->check_aii && !c0->opt.no_fuse;   // (no_fuse: measurement aid, the two sweeps apart)
     // (the progress word carries the iteration in 15 bits: a solve that may run longer keeps the predicted queue)
     // Slab decompositions pace too (Options::slab_paced; lead 1: nothing is ever queued in vain, so every rank queues the same
     // collectives) -- parameters only: the same on every rank
@@ -1123,6 +1132,9 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         if (p->pressure_solver_method == SPH_SOLVER_IISPH2 || no_records) m.a.rec0 = m.a.rec1 = m.a.xv = nullptr;   // (IISPH2's rescaling works on p and p / rho^2)
         m.a.h_mode = p->support_length_estimation;
         m.a.sp_check_aii = p->check_aii;
+        // the fused sweep on records (sph_sweeps.hip: OpFuseU): {x, y, v} is current exactly when this step adopted the queued build whose
+        // place launch wrote it -- whatever touched the state since dropped that build
+        if (adopt && c->ahead.xv_rec && np_fused && c->opt.fuse_records && n && sweep_a_on_records(m.a)) m.a.xv_in = c->xvn.as<float4>();
         m.st.n_particles = c->n;
         m.st.dt = dt;
         return SPH_OK;
@@ -1460,10 +1472,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             slab_ghost_mrho(c, m.a);
         }
     // ---- constant_field + a_ii (simulation.rs:2235-2259) ---------------------------------------------------
-    // the non-pressure acceleration directly follows in every mode but HybridDFSPH-with-forces-behind-the-divergence-solve:
-    // then it shares the sweep (one replay of the lists, one gradient per pair)
-    const bool np_first = p->pressure_solver_method != SPH_SOLVER_HYBRID_DFSPH || p->hybrid_dfsph_non_pressure_accel_before_divergence_free;
-    const bool np_fused = np_first && !p->check_aii && !c0->opt.no_fuse;   // (no_fuse: measurement aid, the two sweeps apart)
+    // (np_fused, at the head of the step: the non-pressure acceleration shares the sweep)
     for (auto& m : M) {
         (void)hipSetDevice(m.c->device);
         if (m.n && np_fused) {
@@ -1578,6 +1587,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const GridP g = plan.g;
         hipStream_t s = c->stream;
         const float4* integrated = c->pm[c->pcur ^ 1].as<float4>();   // (the tail's output; the step's end flips pcur)
+        bool xv_rec = false;
         if (plan.incremental) {
             // (without the lambda sums of this step: only FromDistribution* reads them next step, and a step in that mode does not adopt this build)
             // (fused: the header of the tail just queued, published to the wait that follows -- what solve_queue() left out)
@@ -1585,8 +1595,16 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             if (plan.fused) {
                 fused = IncFusedP{c->inc_local.as<uint32_t>(), header_ahead_args(c, (n + 255u) / 256u, c->hdr_host_dev, true)};
             }
+            // (fused, a scene whose solves run on records: the place launch holds x and v of every particle anyway and leaves them as one
+            //  record in the new order, for the fused a_ii / force sweep of the step that adopts this build -- OpFuseU)
+            ReorderIO io = reorder_io(c, integrated, c->pm2.as<float4>(), c->acxy.as<uint32_t>(), false);
+            xv_rec = plan.fused && c->opt.fuse_records && sweep_a_on_records(M[0].a);
+            if (xv_rec) {
+                HIPCHK(c, c->xvn.ensure((size_t)c->cap * sizeof(float4)));
+                io.xv_out = c->xvn.as<float4>();
+            }
             incremental_cell_sort_reorder(s, &c->prof, n, integrated, plan.q, /* classified by the tail */ true, c->cell_start.as<uint32_t>(), c->akey[0].as<uint32_t>(),
-                                          c->acell_start.as<uint32_t>(), reorder_io(c, integrated, c->pm2.as<float4>(), c->acxy.as<uint32_t>(), false),
+                                          c->acell_start.as<uint32_t>(), io,
                                           c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1, plan.fused ? &fused : nullptr);
             c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
         } else {
@@ -1606,6 +1624,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         c->ahead.tile_tsy = plan.tile_tsy;
         c->ahead.rest_density = p->rest_density;
         c->ahead.n = c->n;
+        c->ahead.xv_rec = xv_rec;
         return SPH_OK;
     };
 
@@ -1956,6 +1975,7 @@ extern "C" int sph_dist_configure(sph_ctx* c, int rank, int n_ranks, float cut_l
     c->dist.nranks = n_ranks;
     c->dist.cut_lo = cut_lo;
     c->dist.cut_hi = cut_hi;
+    c->lvl_pristine = false;   // (a slab rank's ghosts arrive with their owners' level fields)
     c->drop(DROPS_DIST_CONFIGURE);
     c->dist.n_tot = (uint32_t)c->n;
     if (c->dist.on) {

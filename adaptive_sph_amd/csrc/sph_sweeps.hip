@@ -1195,7 +1195,9 @@ struct OpAiiConst {
             a.a2 += Aj.z * (gx * gx + gy * gy);
         }
     }
-    __device__ bool finish(Acc& a, uint32_t i, float4 Ai, bool wall) const
+    __device__ bool finish(Acc& a, uint32_t i, float4 Ai, bool wall) const { return finish_rho(a, i, Ai, wall, rho[i]); }
+    // (rho_i: the particle's density, from rho[] or from the record the sweep holds anyway -- OpFuseU)
+    __device__ bool finish_rho(Acc& a, uint32_t i, float4 Ai, bool wall, const float rho_i) const
     {
         float ls = 0.f;
         float2 gl = make_float2(0.f, 0.f);
@@ -1205,7 +1207,7 @@ struct OpAiiConst {
         }
         if (!a.self_done) a.cf += a.self_cf;   // (offset list without a neighbour behind the particle)
         constf[i] = a.cf + ls / sp.rest_density;
-        const float mi = Ai.z, rho_i = rho[i], rho_b = sp.rest_density;
+        const float mi = Ai.z, rho_b = sp.rest_density;
         const float rho_i_sq = rho_i * rho_i;
         float v;
         if constexpr (MathT::EXACT) {   // the boundary sums entry by entry, as iisph_aii adds them (boundary_winchenbach2020.rs:236-304)
@@ -3161,6 +3163,88 @@ struct OpFuse {
     }
 };
 
+// The same fused sweep for uniform-h scenes with mass-derived smoothing lengths on one context -- the headline -- on THREE gathers per
+// neighbour instead of four (pm[j], mrho[j], rho[j], vel[j]): the record {x_j, y_j, v_j} as the place launch of the build this step
+// adopted left it (sph_sort.hip: k_inc_place_reorder, ReorderIO::xv_out), rho[j] and mrho[j].  The particle's own velocity comes from
+// its record.  The record holds no mass: m_j, and the particle's own, become the mass of particle 0 (see OpPressureAccelU: equal on
+// every particle of such a scene, and then every pair term is the generic sweep's bit for bit).  pair / pair_off / finish are
+// OpAiiConst's and OpNonPressure's own, called with the record (x, y, m, h) put together again, so the operations and their order are
+// the generic sweep's; a lane without an offset list replays its mask word through the same loadA / nb (sweep_particle).
+// (The form on TWO gathers -- {rho, m / rho} as one 8-byte payload out of the density sweep's finish -- was built and measured: the
+//  sweep 31.2 instead of 33.1 us, and what the density sweep pays for the store could not be told from its own run-to-run spread; by
+//  the rule set for it, it stayed out: profiles/fuse_records.md.)
+#ifndef SPH_FUSEU_WAVES
+#define SPH_FUSEU_WAVES 6   // (measured against 7: profiles/fuse_records.md)
+#endif
+template <class MathT>
+struct OpFuseU {
+    static_assert(MathT::UNIFORM, "OpFuseU: uniform-h scenes");
+    typedef OpAiiConst<MathT> A;
+    typedef OpNonPressure<MathT> B;
+    typedef MathT Math;
+    static constexpr bool TILE = false, HAS_EPILOGUE = false, SKIP_SELF = false, EXTENDED = false;
+    static constexpr bool OFF16 = true, OFF16_SELF = true;
+    static constexpr int OFF_WAVES = SPH_FUSEU_WAVES;
+    __device__ constexpr float krange() const { return 2.f; }
+    A a;
+    B b;
+    Math m;
+    const float4* __restrict__ xv_in;   // {x, y, vx, vy} in this step's order
+    typedef float2 NB;                  // {rho, m / rho}
+    struct Acc {
+        typename A::Acc x;
+        typename B::Acc y;
+        float mass, mrho_i;
+    };
+    __device__ bool skip() const { return false; }
+    __device__ bool lane_skip(uint32_t) const { return false; }
+    __device__ void init(Acc& c) const { c.mass = a.pm[0].z; }
+    __device__ void epilogue(Acc&, bool, uint32_t) const {}
+    __device__ float4 loadA(uint32_t j) const { return load_record(xv_in, j); }
+    __device__ NB nb(const Acc&, uint32_t j, float4) const
+    {
+        const uint32_t o = j << 2;   // (32-bit byte offsets from the uniform bases, as load_record)
+        return make_float2(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.rho) + o),
+                           *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.mrho) + o));
+    }
+    __device__ void begin(Acc& c, uint32_t i, float4 Ai) const
+    {
+        a.begin(c.x, i, Ai);
+        const NB own = nb(c, i, Ai);
+        c.mrho_i = own.y;
+        c.y.vx = c.y.vy = 0.f;   // (OpNonPressure::begin, the density and the velocity from the records)
+        c.y.rho_i = own.x;
+        c.y.vix = Ai.z;
+        c.y.viy = Ai.w;
+    }
+    __device__ void begin_off(Acc& c, uint32_t, float4) const
+    {
+        float wv, sc;   // (OpAiiConst::begin_off)
+        m.wg(0.f, m.h, wv, sc);
+        c.x.self_cf = c.mrho_i * wv;
+        c.x.self_done = false;
+    }
+    __device__ void pair(Acc& c, float4 Rj, NB n, float dx, float dy, float r2, float hij) const
+    {
+        const float4 Aj = make_float4(Rj.x, Rj.y, c.mass, m.h);
+        a.pair(c.x, Aj, n.y, dx, dy, r2, hij);
+        b.pair(c.y, Aj, NBRhoVel{n.x, Rj.z, Rj.w}, dx, dy, r2, hij);
+    }
+    __device__ void pair_off(Acc& c, float4 Rj, NB n, float dx, float dy, float r2, float hij, int off) const
+    {
+        const float4 Aj = make_float4(Rj.x, Rj.y, c.mass, m.h);
+        a.pair_off(c.x, Aj, n.y, dx, dy, r2, hij, off);
+        b.pair(c.y, Aj, NBRhoVel{n.x, Rj.z, Rj.w}, dx, dy, r2, hij);
+    }
+    __device__ bool finish(Acc& c, uint32_t i, float4 Ri, bool wall) const
+    {
+        const float4 Ai = make_float4(Ri.x, Ri.y, c.mass, m.h);
+        const bool w = a.finish_rho(c.x, i, Ai, wall, c.y.rho_i);
+        b.finish(c.y, i, Ai, wall);
+        return w;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -3193,6 +3277,8 @@ static bool solve_on_records(const SweepArgs& a)    // ... and sweep A {x, y, p 
 bool sweep_a_on_records(const SweepArgs& a) { return solve_on_records(a); }
 // ... and the source-term sweep {x, y, v} (OpSourceU): one context, the record kept current by the writers of the velocities
 bool source_term_on_records(const SweepArgs& a) { return solve_on_records(a) && a.xv != nullptr; }
+// ... and the fused a_ii / force sweep {x, y, v} (OpFuseU): the step driver sets xv_in while the record is current
+bool fused_sweep_on_records(const SweepArgs& a) { return solve_on_records(a) && a.xv_in != nullptr && a.nloff != nullptr && !a.sp_check_aii; }
 extern "C" int sph_set_sweep_variant(int mode)
 {
     if (mode < 0 || mode > 3) return SPH_ERR_INVALID_ARGUMENT;
@@ -3371,7 +3457,23 @@ static void launch_fused_aii_np(hipStream_t s, const SweepArgs& a, const M& math
 // constant_field + a_ii and the non-pressure acceleration in one sweep (see OpFuse)
 void launch_aii_const_non_pressure(hipStream_t s, Profiler* prof, const SweepArgs& a)
 {
+    const bool records = fused_sweep_on_records(a);
+#ifdef SPH_LAB   // (the laboratory build, which has the switch: an empty scope in front whose launch count says how often the record form
+                 //  ran -- the sweep's own scope keeps its name, and the product's profile its launches)
+    if (records) {
+        ProfScope count(prof, "aii_nonpressure_records", s);
+    }
+#endif
     ProfScope ps(prof, "aii_nonpressure", s, true);
+    if (records) {
+        const MathUniform math = uniform_math(a.h_uniform);
+        typedef OpFuseU<MathUniform> Op;
+        Op op{OpAiiConst<MathUniform>{math, a.pm, a.orig, a.rho, a.mrho, a.lam_sum, a.lam_grad, a.aii, a.constf, a.status, a.sp, nullptr},
+              OpNonPressure<MathUniform>{math, a.pm, a.orig, a.rho, a.vel, a.vel_tmp, a.status, a.sp, source_term_on_records(a) ? a.xv : nullptr}, math,
+              a.xv_in};
+        launch_sweep<Op, false>(s, a, op);
+        return;
+    }
     if (a.exact) launch_fused_aii_np(s, a, exact_math(a));
     else if (a.uniform_h) launch_fused_aii_np(s, a, uniform_math(a.h_uniform));
     else launch_fused_aii_np(s, a, MathFast{0.f});
