@@ -62,6 +62,13 @@ def build_parser() -> argparse.ArgumentParser:
     run.add_argument("--grid-spacing", type=_positive_float, default=None, help="sample spacing of --grid-vtk (default: the smallest block spacing of the scene)")
     run.add_argument("--grid-fields", default="density,pressure,velocity",
                      help="comma-separated fields of --grid-vtk: density, pressure, velocity, level, constant_field")
+    # not in the reference either: the state ledger, reduced on the device (ledger.py)
+    run.add_argument("--ledger", default=None, metavar="FILE.csv",
+                     help="write one row per N-th step: the exact sums (mass, momentum, moments, kinetic energy, angular momentum, volume, compression), "
+                          "centre of mass, potential energy, mean density error, the fastest / lowest / densest particle and its id, the pressure "
+                          "maximum, the particles outside the boundary; taken between the step and its adaptivity, like --grid-vtk; with adaptivity "
+                          "the change of mass and momentum across it (adapt_d_*)")
+    run.add_argument("--ledger-every", type=int, default=1, help="a row of --ledger every N-th step")
     img = sub.add_parser("image", help="Render images (and video frames) as described by export recipes")
     img.add_argument("RECIPE", nargs="+", help="ImageExportConfig list (YAML); paths inside are relative to its directory")
     img.add_argument("--split-patterns", default=None,
@@ -110,6 +117,13 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         grid_fields = [f.strip() for f in args.grid_fields.split(",") if f.strip()]
         sampling.expand_channels(grid_fields)   # (an unknown name stops the run here, not at the first snapshot)
         grid_vtk = VtkGridExporter(args.grid_vtk, "my-sph-grid")
+    ledger_file = None
+    if getattr(args, "ledger", None):
+        import csv
+        from . import ledger as ledger_mod
+        ledger_file = open(args.ledger, "w", newline="")
+        ledger_csv = csv.writer(ledger_file)
+        ledger_csv.writerow(ledger_mod.CSV_COLUMNS)
     steps, t0 = 0, time.perf_counter()
     while (args.max_seconds is None or sim.time < args.max_seconds) and (args.max_steps is None or steps < args.max_steps):
         dt = sim.single_step_without_adaptivity(p)
@@ -119,14 +133,23 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
             # between the step and its adaptivity (single_step, simulation.rs:1973-1978, taken apart): density and pressure are the
             # step's outputs and line up with the particles only until sharing / merging / splitting edit the vector
             grid_vtk.add_snapshot(sim.time, grid, sampling.sample_grid(sim.ctx, p, grid, grid_fields).planes)
+        led = None
+        if ledger_file is not None and steps % max(args.ledger_every, 1) == 0:
+            led = ledger_mod.ledger(sim.ctx, p)               # (the same place, for the same reason)
         if adaptive:
             sim.single_step_adaptivity(params, dt)
+        if led is not None:
+            # behind the adaptivity only what the particles carry is valid: mass and momentum before and after, exactly
+            after = ledger_mod.ledger(sim.ctx, p, what="carried") if adaptive else None
+            ledger_csv.writerow(ledger_mod.csv_row(steps, sim.time, dt, led, p, after))
         if vtk is not None and snapshot:
             vtk.add_snapshot(sim.time, sim, vtk_planes)       # main_loop.rs:302-309
     if vtk is not None:
         vtk.close()
     if grid_vtk is not None:
         grid_vtk.close()
+    if ledger_file is not None:
+        ledger_file.close()
     wall = time.perf_counter() - t0
     print(f"{steps} steps, simulated time {sim.time:.6f} s, {sim.num_fluid_particles()} particles, "
           f"{sim.num_fluid_particles() * steps / max(wall, 1e-9) / 1e6:.2f} M particle-steps/s", file=out)

@@ -328,6 +328,9 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     DevBuf smp_layer, smp_band, smp_stage;
     bool smp_have_layer = false;
     int smp_layer_sx0 = 0, smp_layer_sx1 = 0, smp_layer_ny = 0, smp_layer_planes = 0;
+    // the state ledger (sph_ledger.hip): one partial per block and quantity of a pass, and the words / sums its last launch folds them
+    // into -- allocated on first use, kept across calls, freed by sph_destroy
+    DevBuf led_part, led_out;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)

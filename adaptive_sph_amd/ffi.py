@@ -279,6 +279,59 @@ class SphSampleBand(C.Structure):
         return int(self.sx0), int(self.sx1), int(self.n_boxes)
 
 
+# include/sph_ledger.h: the state ledger -- exact 128-bit sums, extremes with their particle's id, counts (product only)
+LEDGER_SYMBOLS = ["ledger_compute", "slab_ledger_range", "slab_ledger_sums", "ledger_fold_words", "ledger_compose", "group_ledger"]
+LEDGER_N_SUMS, LEDGER_N_EXTREMES = 9, 13
+LEDGER_MIN_EXPONENT, LEDGER_MAX_EXPONENT, LEDGER_AUTO_EXPONENT = -200, 200, 0x7FFFFFFF
+LEDGER_NO_OFFENDER, LEDGER_NO_ID = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
+LEDGER_GROUPS = {"carried": 1, "step_outputs": 2, "outside": 4}   # SPH_LEDGER_CARRIED | _STEP_OUTPUTS | _OUTSIDE
+LEDGER_SUMS = ["mass", "momentum_x", "momentum_y", "moment_x", "moment_y", "kinetic", "angular", "volume", "compression"]
+LEDGER_EXTREMES = ["max_speed2", "min_x", "max_x", "min_y", "max_y", "min_mass", "max_mass", "min_density", "max_density", "min_pressure",
+                   "max_pressure", "min_h", "max_h"]
+
+
+class SphLedgerSpec(C.Structure):
+    """sph_ledger_spec: the groups asked for and the exponent of every sum (LEDGER_AUTO_EXPONENT: taken from the range pass)."""
+    _fields_ = [("what", C.c_uint32), ("exponent", C.c_int32 * LEDGER_N_SUMS)]
+
+
+class SphLedgerSum(C.Structure):
+    """sph_ledger_sum: the 128-bit two's-complement integer hi * 2^64 + lo."""
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
+
+    def as_int(self) -> int:
+        return (int(self.hi) << 64) + int(self.lo)
+
+    @classmethod
+    def from_int(cls, q: int):
+        lo = int(q) & 0xFFFFFFFFFFFFFFFF
+        return cls(lo, (int(q) - lo) >> 64)
+
+
+class SphLedgerExtreme(C.Structure):
+    _fields_ = [("value", C.c_float), ("id", C.c_uint32)]
+
+
+class SphLedgerWords(C.Structure):
+    """sph_ledger_words: what a rank's range pass says -- (id << 8 | reason) of its smallest offending particle (all ones: none), the
+    counts, max |t| per sum as f64 bits, the 13 extreme keys."""
+    _fields_ = [("first_bad", C.c_uint64), ("n", C.c_uint64), ("n_outside", C.c_uint64), ("max_bits", C.c_uint64 * LEDGER_N_SUMS),
+                ("extreme", C.c_uint64 * LEDGER_N_EXTREMES)]
+
+    def as_tuple(self):
+        return int(self.first_bad), int(self.n), int(self.n_outside), tuple(int(b) for b in self.max_bits), tuple(int(k) for k in self.extreme)
+
+    @classmethod
+    def from_tuple(cls, t):
+        return cls(int(t[0]), int(t[1]), int(t[2]), (C.c_uint64 * LEDGER_N_SUMS)(*[int(b) for b in t[3]]),
+                   (C.c_uint64 * LEDGER_N_EXTREMES)(*[int(k) for k in t[4]]))
+
+
+class SphLedgerResult(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("exponent", C.c_int32 * LEDGER_N_SUMS), ("n", C.c_uint64), ("n_outside", C.c_uint64),
+                ("raw", SphLedgerSum * LEDGER_N_SUMS), ("sum", C.c_double * LEDGER_N_SUMS), ("extreme", SphLedgerExtreme * LEDGER_N_EXTREMES)]
+
+
 ABI_SYMBOLS = [
     "create", "destroy", "upload", "upload_field", "download", "download_neighbors", "num_particles", "time",
     "set_time", "step", "classify", "share_particles", "merge_particles", "set_split_patterns", "split_particles", "host_find_partners", "last_error", "grid", "set_boundary_polygon", "set_math_policy", "get_math_policy", "apply_edits", "profile_enable", "profile_reset", "profile_get", "profile_event_overhead", "profile_dispatch_bracket", "profile_copy_bandwidth", "profile_list_forms", "set_sweep_variant",
@@ -477,6 +530,13 @@ class SphLibrary:
         self.sample_compose = sig("sample_compose", i32, [vp, spp, i32, sbp, C.POINTER(vp), vp, u64, vp, u64], required=False)
         self.group_sample_grid = sig("group_sample_grid", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), spp, vp, u64, vp, u64, C.POINTER(SphSampleInfo)],
                                      required=False)
+        lsp, lwp, lsu, lrp = C.POINTER(SphLedgerSpec), C.POINTER(SphLedgerWords), C.POINTER(SphLedgerSum), C.POINTER(SphLedgerResult)
+        self.ledger_compute = sig("ledger_compute", i32, [vp, C.POINTER(SphParams), lsp, lrp], required=False)
+        self.slab_ledger_range = sig("slab_ledger_range", i32, [vp, C.POINTER(SphParams), lsp, lwp], required=False)
+        self.slab_ledger_sums = sig("slab_ledger_sums", i32, [vp, C.POINTER(SphParams), lsp, lsu], required=False)
+        self.ledger_fold_words = sig("ledger_fold_words", i32, [i32, lwp, lsp, lwp, C.c_char_p, u64], required=False)
+        self.ledger_compose = sig("ledger_compose", i32, [i32, lwp, lsu, lsp, lrp], required=False)
+        self.group_ledger = sig("group_ledger", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), lsp, lrp], required=False)
 
 
 _PRODUCT = None
