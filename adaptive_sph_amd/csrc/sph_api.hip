@@ -646,8 +646,8 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->flag_insufficient, &c->con_thr, &c->con_consumed, &c->con_h, &c->flag_reduced, &c->szc[0], &c->szc[1], &c->omega, &c->stash, &c->nl_ext, &c->nlx_ext, &c->nl_ok, &c->mrho, &c->pt0, &c->pt1, &c->prec0, &c->prec1, &c->xv, &c->xvn, &c->rho, &c->lam_sum, &c->lam_grad, &c->wall_pl, &c->wall_cnt, &c->constf, &c->aii, &c->src, &c->p0, &c->p1, &c->pacc, &c->dens_err,
                      &c->stat, &c->ncount, &c->planes_d, &c->lam_lut, &c->dlam_lut, &c->hdr_partials, &c->hdr_out, &c->ctrl, &c->status,
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
-                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->inc_local, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_layer, &c->rnd_band, &c->rnd_words, &c->rnd_stage,
-                     &c->smp_planes, &c->smp_out, &c->smp_red, &c->smp_layer, &c->smp_band, &c->smp_stage,
+                     &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->inc_local, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_words, &c->rnd_layer.words, &c->rnd_layer.band, &c->rnd_layer.stage,
+                     &c->smp_planes, &c->smp_out, &c->smp_red, &c->smp_layer.words, &c->smp_layer.band, &c->smp_layer.stage,
                      &c->led_part, &c->led_out};
     for (auto b : all) b->release();
     for (DevBuf* b : c->export_bufs()) b->release();

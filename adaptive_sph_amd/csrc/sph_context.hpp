@@ -99,6 +99,20 @@ struct ProbBufs {
     DevBuf ids, cls, mass, level, pos, h2, off;
 };
 
+// The layer a slab rank drew or scattered last (sph_slab_layers.hpp), kept until its next layer call: `planes` planes of `rows` rows of
+// the sample columns [sx0, sx1), one 64-bit word per sample; the words of the band reduction; the staging of the layers that arrive
+// from the host for a compose on this context.
+struct SlabLayer {
+    DevBuf words, band, stage;
+    bool have = false;
+    int sx0 = 0, sx1 = 0, rows = 0, planes = 0;
+    void keep(int x0, int x1, int n_rows, int n_planes)
+    {
+        sx0 = x0, sx1 = x1, rows = n_rows, planes = n_planes;
+        have = true;
+    }
+};
+
 struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its validity flags and what each entry point drops of them)
     int device = 0;
     Options opt;
@@ -313,21 +327,15 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // positions kept for an interpolated frame (sph_render_snapshot) -- allocated on first use, kept across frames, freed by sph_destroy
     DevBuf rnd_rec, rnd_keys, rnd_out, rnd_max, rnd_prev;
     uint64_t rnd_prev_n = 0;
-    // frames from slab contexts (sph_slab_render.hip): this rank's layer -- rnd_layer_hs rows of the sample columns [rnd_layer_sx0,
-    // rnd_layer_sx1), one 64-bit word per sample -- kept until the next layer call; the three words of the band reduction; the
-    // WS x HS words a compose merges the layers into, and the staging of layers that arrive from the host
-    DevBuf rnd_layer, rnd_band, rnd_words, rnd_stage;
-    bool rnd_have_layer = false;
-    int rnd_layer_sx0 = 0, rnd_layer_sx1 = 0, rnd_layer_hs = 0;
+    // frames from slab contexts (sph_slab_render.hip): this rank's layer of HS rows (one plane), and the WS x HS words a compose merges
+    // the layers into
+    SlabLayer rnd_layer;
+    DevBuf rnd_words;
     // fields on a regular grid (sph_sample.hip): the int64 planes, the resolved f32 planes, the words of the range pass and the counts
     // -- allocated on first use, kept across calls, freed by sph_destroy
     DevBuf smp_planes, smp_out, smp_red;
-    // fields from slab contexts (sph_slab_sample.hip): this rank's layer -- smp_layer_planes planes of smp_layer_ny rows of the sample
-    // columns [smp_layer_sx0, smp_layer_sx1), one int64 word per sample -- kept until the next layer call; the words of the band
-    // reduction; the staging of layers that arrive from the host
-    DevBuf smp_layer, smp_band, smp_stage;
-    bool smp_have_layer = false;
-    int smp_layer_sx0 = 0, smp_layer_sx1 = 0, smp_layer_ny = 0, smp_layer_planes = 0;
+    // fields from slab contexts (sph_slab_sample.hip): this rank's layer of C + 1 planes of ny rows
+    SlabLayer smp_layer;
     // the state ledger (sph_ledger.hip): one partial per block and quantity of a pass, and the words / sums its last launch folds them
     // into -- allocated on first use, kept across calls, freed by sph_destroy
     DevBuf led_part, led_out;

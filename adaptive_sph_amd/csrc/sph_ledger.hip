@@ -26,8 +26,8 @@
 #include <cstring>
 #include <vector>
 
-#include "sph_context.hpp"
 #include "sph_ledger.h"
+#include "sph_slab_layers.hpp"
 
 static_assert(sizeof(sph_ledger_spec) == 40 && sizeof(sph_ledger_sum) == 16 && sizeof(sph_ledger_extreme) == 8, "the sizes sph_ledger.h states");
 static_assert(sizeof(sph_ledger_words) == 200 && sizeof(sph_ledger_result) == 376, "the sizes sph_ledger.h states");
@@ -464,10 +464,6 @@ int compose(int n, const sph_ledger_words* words, const sph_ledger_sum* sums, co
     return SPH_OK;
 }
 
-// slots in the arrays and their ownership flags: a plain context holds particles only; a slab context behind a step owned + ghosts,
-// else the owned particles alone (sph_slab_sample.hip)
-uint32_t ledger_slots(const sph_ctx* c) { return c->dist.on && c->have_flags ? c->dist.n_tot : (uint32_t)c->n; }
-const uint8_t* ledger_owned(const sph_ctx* c) { return c->dist.on && c->have_flags ? c->dist.owned.as<uint8_t>() : nullptr; }
 uint32_t ledger_blocks(uint32_t n) { return std::min(std::max((n + 255u) / 256u, 1u), kMaxBlocks); }
 
 LedgerIn make_ledger_in(sph_ctx* c, const sph_params* p, const sph_ledger_spec* spec)
@@ -506,11 +502,11 @@ int range_pass(sph_ctx* c, const sph_params* p, const sph_ledger_spec* spec, sph
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = ensure_buffers(c)) return rc;
     hipStream_t s = c->stream;
-    const uint32_t n = ledger_slots(c), nb = ledger_blocks(n);
+    const uint32_t n = owned_slots(c), nb = ledger_blocks(n);
     const LedgerIn a = make_ledger_in(c, p, spec);
     {
         ProfScope ps(&c->prof, "ledger_range", s);
-        if (c->dist.on) hipLaunchKernelGGL(k_ledger_range<true>, dim3(nb), dim3(256), 0, s, n, a, ledger_owned(c), c->led_part.as<unsigned long long>());
+        if (c->dist.on) hipLaunchKernelGGL(k_ledger_range<true>, dim3(nb), dim3(256), 0, s, n, a, owned_flags(c), c->led_part.as<unsigned long long>());
         else hipLaunchKernelGGL(k_ledger_range<false>, dim3(nb), dim3(256), 0, s, n, a, (const uint8_t*)nullptr, c->led_part.as<unsigned long long>());
         hipLaunchKernelGGL(k_ledger_fold_words, dim3(kWords), dim3(64), 0, s, nb, c->led_part.as<unsigned long long>(), c->led_out.as<unsigned long long>());
     }
@@ -526,12 +522,12 @@ int sum_pass(sph_ctx* c, const sph_params* p, const sph_ledger_spec* spec, sph_l
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = ensure_buffers(c)) return rc;
     hipStream_t s = c->stream;
-    const uint32_t n = ledger_slots(c), nb = ledger_blocks(n);
+    const uint32_t n = owned_slots(c), nb = ledger_blocks(n);
     const LedgerIn a = make_ledger_in(c, p, spec);
     U128* dst = (U128*)((char*)c->led_out.p + kOutSums);
     {
         ProfScope ps(&c->prof, "ledger_sums", s);
-        if (c->dist.on) hipLaunchKernelGGL(k_ledger_sums<true>, dim3(nb), dim3(256), 0, s, n, a, ledger_owned(c), c->led_part.as<U128>());
+        if (c->dist.on) hipLaunchKernelGGL(k_ledger_sums<true>, dim3(nb), dim3(256), 0, s, n, a, owned_flags(c), c->led_part.as<U128>());
         else hipLaunchKernelGGL(k_ledger_sums<false>, dim3(nb), dim3(256), 0, s, n, a, (const uint8_t*)nullptr, c->led_part.as<U128>());
         hipLaunchKernelGGL(k_ledger_fold_sums, dim3(kSums), dim3(64), 0, s, nb, c->led_part.as<U128>(), dst);
     }
@@ -635,12 +631,5 @@ extern "C" int sph_ledger_compose(int n, const sph_ledger_words* words, const sp
 
 extern "C" int sph_group_ledger(sph_ctx** ctxs, int n, const sph_params* p, const sph_ledger_spec* spec, sph_ledger_result* out)
 {
-    if (!ctxs || n < 1) return SPH_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < n; i++)
-        if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
-    // whichever member refuses, the sentence is found in member 0's sph_last_error
-    for (int i = 0; i < n; i++) ctxs[i]->err.clear();
-    const int rc = group_ledger(ctxs, n, p, spec, out);
-    for (int i = 1; rc != SPH_OK && ctxs[0]->err.empty() && i < n; i++) ctxs[0]->err = ctxs[i]->err;
-    return rc;
+    return group_call(ctxs, n, [&] { return group_ledger(ctxs, n, p, spec, out); });
 }

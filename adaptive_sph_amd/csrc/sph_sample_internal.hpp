@@ -196,7 +196,7 @@ constexpr int kRecF = 5;                      // x, y, h, norm, V; then the chan
 //          a wave for a pass of its own (measured: profiles/r15_sample_grid.md)
 //   rows   a box above kFlatMaxArea: the wave takes the particle alone, 64 columns of one row per pass
 // SLAB: n counts slots; a ghost lane (owned[i] == 0) has an empty box and writes nothing; `planes` are ny rows of the bw columns from
-// sx0 on, per plane.  The box of an owned particle lies inside the band by construction (k_sample_band reduced the same boxes); the
+// sx0 on, per plane.  The box of an owned particle lies inside the band by construction (k_layer_band reduced the same boxes); the
 // clamp to it keeps every address inside the buffer whatever the band says.
 template <int NCH, bool SLAB>
 __global__ __launch_bounds__(256) void k_sample_scatter(uint32_t n, SampleIn a, SampleGrid g, long long* __restrict__ planes,

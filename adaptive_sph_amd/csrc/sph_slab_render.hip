@@ -8,8 +8,8 @@
 //   k_render_pmax          Pressure only: max(0, max p) over the owned slots as float bits (one u32 atomicMax per block)
 //   k_render_color<true>   one thread per slot: colour, render position, radius -> rec[slot]; ghost slots write nothing; thread 0
 //                          resets the band words (no memset launch)
-//   k_slab_band            the clamped boxes of the owned discs -> [min column, max column + 1) and their count: block reduction in
-//                          LDS, three atomics per block that drew something
+//   k_layer_band<DiscColumns>  (sph_slab_layers.hpp) the clamped boxes of the owned discs -> [min column, max column + 1) and their
+//                          count: block reduction in LDS, three atomics per block that drew something
 //   k_slab_scatter         one thread per owned slot: 64-bit atomicMax((id + 1) << 32 | slot) over the band samples its outer disc covers
 //   k_slab_layer_resolve   one thread per band sample, in place: key -> (id + 1) << 32 | (fill ? rgb : 0)
 //   k_slab_merge           one launch per layer, in stream order: plain loads and stores of max(dst, src) over the layer's columns of the
@@ -23,46 +23,27 @@
 
 #include "sph_slab_render.h"
 #include "sph_render_internal.hpp"
+#include "sph_slab_layers.hpp"
 
 namespace {
 
 typedef unsigned long long u64;
 
-__global__ __launch_bounds__(256) void k_slab_band(uint32_t nt, const uint4* __restrict__ rec, const uint8_t* __restrict__ owned, FrameP f,
-                                                    uint32_t* __restrict__ out)
-{
-    __shared__ uint32_t lo[256], hi[256], cnt[256];
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    uint32_t l = 0xffffffffu, h = 0u, c = 0u;
-    if (i < nt && (!owned || owned[i])) {
-        const Disc d = disc_of(f, rec[i]);
+// k_layer_band's box of a slot: the sample columns of its colour record's outer disc
+struct DiscColumns {
+    const uint4* rec;
+    FrameP f;
+    __device__ bool operator()(uint32_t slot, int& x0, int& x1) const
+    {
         SampleBox b;
-        if (disc_box(f, d, b)) {
-            l = (uint32_t)b.x0;
-            h = (uint32_t)b.x1 + 1u;
-            c = 1u;
-        }
+        if (!disc_box(f, disc_of(f, rec[slot]), b)) return false;
+        x0 = b.x0;
+        x1 = b.x1;
+        return true;
     }
-    lo[threadIdx.x] = l;
-    hi[threadIdx.x] = h;
-    cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            lo[threadIdx.x] = min(lo[threadIdx.x], lo[threadIdx.x + s]);
-            hi[threadIdx.x] = max(hi[threadIdx.x], hi[threadIdx.x + s]);
-            cnt[threadIdx.x] += cnt[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && cnt[0]) {
-        atomicMin(&out[0], lo[0]);
-        atomicMax(&out[1], hi[0]);
-        atomicAdd(&out[2], cnt[0]);
-    }
-}
+};
 
-// keys: hs rows of the band's columns [sx0, sx1).  The box of an owned disc lies inside the band by construction (k_slab_band reduced
+// keys: hs rows of the band's columns [sx0, sx1).  The box of an owned disc lies inside the band by construction (k_layer_band reduced
 // the same boxes); the clamp to it keeps every address inside the buffer whatever the band says.
 __global__ __launch_bounds__(256) void k_slab_scatter(uint32_t nt, const uint4* __restrict__ rec, const uint8_t* __restrict__ owned,
                                                        const uint32_t* __restrict__ orig, FrameP f, int sx0, int sx1, u64* __restrict__ keys)
@@ -142,10 +123,6 @@ int slab_refuse(sph_ctx* c, const char* what)
     return SPH_OK;
 }
 
-// slots in the arrays and their ownership flags: behind a step owned + ghosts, else the owned particles alone
-uint32_t slab_slots(const sph_ctx* c) { return c->have_flags ? c->dist.n_tot : (uint32_t)c->n; }
-const uint8_t* slab_owned(const sph_ctx* c) { return c->have_flags ? c->dist.owned.as<uint8_t>() : nullptr; }
-
 // everything a layer call refuses, in sph_render's order where it refuses the same
 int check_layer(sph_ctx* c, const char* what, const sph_params* p, const sph_render_params* rp)
 {
@@ -169,12 +146,12 @@ int check_layer(sph_ctx* c, const char* what, const sph_params* p, const sph_ren
 // ---- a layer in two halves: up to the copy of the band words (queued), and from the band on (after the wait) ----
 int layer_front(sph_ctx* c, const sph_params* p, const sph_render_params* rp, const FrameP& f, float pmax, const uint32_t* pmax_dev, uint32_t* hb)
 {
-    const uint32_t nt = slab_slots(c);
+    const uint32_t nt = owned_slots(c);
     hipStream_t s = c->stream;
-    c->rnd_have_layer = false;
+    c->rnd_layer.have = false;
     hb[0] = hb[1] = hb[2] = 0u;
     HIPCHK(c, c->rnd_rec.ensure((size_t)(nt ? nt : 1) * sizeof(uint4)));
-    HIPCHK(c, c->rnd_band.ensure(4 * sizeof(uint32_t)));
+    HIPCHK(c, c->rnd_layer.band.ensure(4 * sizeof(uint32_t)));
     if (nt == 0) return SPH_OK;
     RenderIn a = make_render_in(c, p, rp);
     a.pmax_bits = pmax_dev;
@@ -183,60 +160,46 @@ int layer_front(sph_ctx* c, const sph_params* p, const sph_render_params* rp, co
     const dim3 grid((nt + 255) / 256), blk(256);
     {
         ProfScope ps(&c->prof, "slab_render_color", s);
-        hipLaunchKernelGGL(k_render_color<true>, grid, blk, 0, s, nt, a, m, c->rnd_rec.as<uint4>(), slab_owned(c), c->rnd_band.as<uint32_t>());
+        hipLaunchKernelGGL(k_render_color<true>, grid, blk, 0, s, nt, a, m, c->rnd_rec.as<uint4>(), owned_flags(c), c->rnd_layer.band.as<uint32_t>());
     }
     {
         ProfScope ps(&c->prof, "slab_render_band", s);
-        hipLaunchKernelGGL(k_slab_band, grid, blk, 0, s, nt, c->rnd_rec.as<uint4>(), slab_owned(c), f, c->rnd_band.as<uint32_t>());
+        hipLaunchKernelGGL(k_layer_band<DiscColumns>, grid, blk, 0, s, nt, owned_flags(c), DiscColumns{c->rnd_rec.as<uint4>(), f}, c->rnd_layer.band.as<uint32_t>());
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hb, c->rnd_band.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(hb, c->rnd_layer.band.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return SPH_OK;
 }
 
 int layer_back(sph_ctx* c, const FrameP& f, const uint32_t* hb, sph_render_band* band)
 {
     hipStream_t s = c->stream;
-    band->sx0 = band->sx1 = 0;
+    band_of(hb, f.ws, band->sx0, band->sx1);
     band->n_drawn = hb[2];
     band->reserved = 0;
-    if (hb[2]) {
-        // (what the device reduced are columns of boxes clamped to the frame; the clamp here guards the allocation all the same)
-        band->sx0 = (int32_t)std::min(hb[0], (uint32_t)f.ws);
-        band->sx1 = (int32_t)std::min(hb[1], (uint32_t)f.ws);
-        if (band->sx0 >= band->sx1) band->sx0 = band->sx1 = 0;
-    }
     const int bw = band->sx1 - band->sx0;
     if (bw > 0) {
-        const uint32_t nt = slab_slots(c);
+        const uint32_t nt = owned_slots(c);
         const size_t n_words = (size_t)bw * (size_t)f.hs;
-        HIPCHK(c, c->rnd_layer.ensure(n_words * sizeof(u64)));
-        HIPCHK(c, hipMemsetAsync(c->rnd_layer.p, 0, n_words * sizeof(u64), s));
+        HIPCHK(c, c->rnd_layer.words.ensure(n_words * sizeof(u64)));
+        HIPCHK(c, hipMemsetAsync(c->rnd_layer.words.p, 0, n_words * sizeof(u64), s));
         {
             ProfScope ps(&c->prof, "slab_render_scatter", s);
-            hipLaunchKernelGGL(k_slab_scatter, dim3((nt + 255) / 256), dim3(256), 0, s, nt, c->rnd_rec.as<uint4>(), slab_owned(c),
-                               c->orig[c->cur].as<uint32_t>(), f, band->sx0, band->sx1, c->rnd_layer.as<u64>());
+            hipLaunchKernelGGL(k_slab_scatter, dim3((nt + 255) / 256), dim3(256), 0, s, nt, c->rnd_rec.as<uint4>(), owned_flags(c),
+                               c->orig[c->cur].as<uint32_t>(), f, band->sx0, band->sx1, c->rnd_layer.words.as<u64>());
         }
         {
             ProfScope ps(&c->prof, "slab_render_layer", s);
-            hipLaunchKernelGGL(k_slab_layer_resolve, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, (uint32_t)n_words, c->rnd_layer.as<u64>(),
+            hipLaunchKernelGGL(k_slab_layer_resolve, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, (uint32_t)n_words, c->rnd_layer.words.as<u64>(),
                                c->rnd_rec.as<uint4>(), f, band->sx0, bw);
         }
         HIPCHK(c, hipGetLastError());
     }
-    c->rnd_layer_sx0 = band->sx0;
-    c->rnd_layer_sx1 = band->sx1;
-    c->rnd_layer_hs = f.hs;
-    c->rnd_have_layer = true;
+    c->rnd_layer.keep(band->sx0, band->sx1, f.hs, 1);
     return SPH_OK;
 }
 
 // ---- compose: layers that are on c's device and ordered before this point of c's stream -> the frame in rgb_out ----
-struct LayerRef {
-    const u64* words;
-    int sx0, sx1;
-};
-
 int merge_and_resolve(sph_ctx* c, const sph_render_params* rp, const FrameP& f, const std::vector<LayerRef>& L, uint8_t* rgb_out)
 {
     hipStream_t s = c->stream;
@@ -249,11 +212,11 @@ int merge_and_resolve(sph_ctx* c, const sph_render_params* rp, const FrameP& f, 
         ProfScope ps(&c->prof, "slab_render_merge", s);
         if (!any) {
             HIPCHK(c, c->rnd_words.ensure(n_samples * sizeof(u64)));
-            hipLaunchKernelGGL(k_slab_merge, dim3((uint32_t)((n_samples + 255) / 256)), dim3(256), 0, s, c->rnd_words.as<u64>(), f.ws, f.hs, l.words, l.sx0, l.sx1, 1);
+            hipLaunchKernelGGL(k_slab_merge, dim3((uint32_t)((n_samples + 255) / 256)), dim3(256), 0, s, c->rnd_words.as<u64>(), f.ws, f.hs, l.as<u64>(), l.sx0, l.sx1, 1);
             any = true;
         } else {
             const size_t n_band = (size_t)(l.sx1 - l.sx0) * (size_t)f.hs;
-            hipLaunchKernelGGL(k_slab_merge, dim3((uint32_t)((n_band + 255) / 256)), dim3(256), 0, s, c->rnd_words.as<u64>(), f.ws, f.hs, l.words, l.sx0, l.sx1, 0);
+            hipLaunchKernelGGL(k_slab_merge, dim3((uint32_t)((n_band + 255) / 256)), dim3(256), 0, s, c->rnd_words.as<u64>(), f.ws, f.hs, l.as<u64>(), l.sx0, l.sx1, 0);
         }
     }
     {
@@ -268,31 +231,18 @@ int merge_and_resolve(sph_ctx* c, const sph_render_params* rp, const FrameP& f, 
     return SPH_OK;
 }
 
-int check_band(sph_ctx* c, const FrameP& f, int k, const sph_render_band& b)
+// c's pressure maximum over its owned slots, on c's stream, into `max_bits` (its own word, or member 0's)
+int launch_pmax(sph_ctx* c, uint32_t* max_bits)
 {
-    if (b.sx0 > b.sx1 || b.sx0 < 0 || b.sx1 > f.ws)
-        return c->fail(SPH_ERR_INVALID_ARGUMENT, "render: band %d = [%d, %d) is no column range of the %d sample columns", k, b.sx0, b.sx1, f.ws);
+    const uint32_t nt = owned_slots(c);
+    if (nt) {
+        ProfScope ps(&c->prof, "slab_render_pmax", c->stream);
+        hipLaunchKernelGGL(k_render_pmax, dim3(std::min((nt + 255) / 256, 1024u)), dim3(256), 0, c->stream, nt, (c->pressure_cur ? c->p1 : c->p0).as<float>(),
+                           owned_flags(c), max_bits);
+    }
+    HIPCHK(c, hipGetLastError());
     return SPH_OK;
 }
-
-// events of one group render, destroyed on every path out
-struct Events {
-    std::vector<hipEvent_t> e;
-    hipError_t create(size_t n)
-    {
-        for (size_t i = 0; i < n; i++) {
-            hipEvent_t v = nullptr;
-            const hipError_t rc = hipEventCreateWithFlags(&v, hipEventDisableTiming);
-            if (rc != hipSuccess) return rc;
-            e.push_back(v);
-        }
-        return hipSuccess;
-    }
-    ~Events()
-    {
-        for (hipEvent_t v : e) (void)hipEventDestroy(v);
-    }
-};
 
 }  // namespace
 
@@ -304,15 +254,9 @@ extern "C" int sph_slab_render_pressure_max(sph_ctx* c, float* out)
     if (int rc = slab_refuse(c, "sph_slab_render_pressure_max")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const uint32_t nt = slab_slots(c);
     HIPCHK(c, c->rnd_max.ensure(sizeof(uint32_t)));
     HIPCHK(c, hipMemsetAsync(c->rnd_max.p, 0, sizeof(uint32_t), s));
-    if (nt) {
-        ProfScope ps(&c->prof, "slab_render_pmax", s);
-        hipLaunchKernelGGL(k_render_pmax, dim3(std::min((nt + 255) / 256, 1024u)), dim3(256), 0, s, nt, (c->pressure_cur ? c->p1 : c->p0).as<float>(),
-                           slab_owned(c), c->rnd_max.as<uint32_t>());
-    }
-    HIPCHK(c, hipGetLastError());
+    if (int rc = launch_pmax(c, c->rnd_max.as<uint32_t>())) return rc;
     uint32_t bits = 0;
     HIPCHK(c, hipMemcpyAsync(&bits, c->rnd_max.p, sizeof bits, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -339,17 +283,7 @@ extern "C" int sph_slab_render_layer(sph_ctx* c, const sph_params* p, const sph_
 extern "C" int sph_slab_render_layer_download(sph_ctx* c, uint64_t* words, uint64_t capacity_words)
 {
     if (!c) return SPH_ERR_INVALID_ARGUMENT;
-    if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "sph_slab_render_layer_download: not a slab context (sph_render draws a plain context)");
-    if (!c->rnd_have_layer) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_render_layer_download: no layer (sph_slab_render_layer comes first)");
-    const uint64_t n_words = (uint64_t)(c->rnd_layer_sx1 - c->rnd_layer_sx0) * (uint64_t)c->rnd_layer_hs;
-    if (n_words == 0) return SPH_OK;
-    if (!words || capacity_words < n_words)
-        return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_render_layer_download: capacity of %llu words, the layer holds %llu", (unsigned long long)capacity_words,
-                       (unsigned long long)n_words);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(words, c->rnd_layer.p, (size_t)n_words * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPH_OK;
+    return layer_download(c, c->rnd_layer, "sph_slab_render_layer", "sph_render draws a plain context", words, capacity_words);
 }
 
 extern "C" int sph_render_compose(sph_ctx* c, const sph_render_params* rp, int n_layers, const sph_render_band* bands, const uint64_t* const* layers,
@@ -363,31 +297,16 @@ extern "C" int sph_render_compose(sph_ctx* c, const sph_render_params* rp, int n
     if ((rc = check_frame_view(c, rp))) return rc;
     if (n_layers < 0 || (n_layers > 0 && !bands)) return c->fail(SPH_ERR_INVALID_ARGUMENT, "render: %d layers without their bands", n_layers);
     const FrameP f = make_frame(rp);
-    size_t total = 0;
-    for (int k = 0; k < n_layers; k++) {
-        if ((rc = check_band(c, f, k, bands[k]))) return rc;
-        const size_t n_words = (size_t)(bands[k].sx1 - bands[k].sx0) * (size_t)f.hs;
-        if (n_words && (!layers || !layers[k])) return c->fail(SPH_ERR_INVALID_ARGUMENT, "render: layer %d is NULL, its band [%d, %d) is not empty", k, bands[k].sx0, bands[k].sx1);
-        total += n_words;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // the layers side by side in one staging buffer: every copy has a place of its own, nothing waits for a merge
-    HIPCHK(c, c->rnd_stage.ensure((total ? total : 1) * sizeof(u64)));
     std::vector<LayerRef> L;
-    size_t at = 0;
-    for (int k = 0; k < n_layers; k++) {
-        const size_t n_words = (size_t)(bands[k].sx1 - bands[k].sx0) * (size_t)f.hs;
-        if (!n_words) continue;
-        u64* dst = c->rnd_stage.as<u64>() + at;
-        HIPCHK(c, hipMemcpyAsync(dst, layers[k], n_words * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-        L.push_back(LayerRef{dst, bands[k].sx0, bands[k].sx1});
-        at += n_words;
-    }
+    if ((rc = stage_layers(c, c->rnd_layer, n_layers, bands, f.ws, (size_t)f.hs, layers, "render", L))) return rc;
     return merge_and_resolve(c, rp, f, L, rgb_out);
 }
 
 extern "C" int sph_group_render(sph_ctx** ctxs, int n, const sph_params* p, const sph_render_params* rp, uint8_t* rgb_out, uint64_t out_bytes)
 {
+    // Unlike sph_group_sample_grid and sph_group_ledger this is no group_call, and a plain member is an invalid argument, not unsupported:
+    // the errors are neither cleared nor forwarded to member 0 (ffi.group_render joins every member's sentence and would print a
+    // forwarded one twice).  Left as it is: aligning the three changes what callers see.
     if (!ctxs || n < 1) return SPH_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < n; i++)
         if (!ctxs[i]) return SPH_ERR_INVALID_ARGUMENT;
@@ -400,10 +319,8 @@ extern "C" int sph_group_render(sph_ctx** ctxs, int n, const sph_params* p, cons
     if ((rc = check_frame_output(c0, rp, rgb_out, out_bytes))) return rc;
     const FrameP f = make_frame(rp);
     const bool pressure = rp->attribute == SPH_VIS_PRESSURE;
-    bool one_device = true;
-    for (int i = 1; i < n; i++) one_device = one_device && ctxs[i]->device == c0->device;
 
-    if (!one_device) {   // the per-rank calls: the layers pass through the host
+    if (!same_device(ctxs, n)) {   // the per-rank calls: the layers pass through the host
         float pmax = 0.f;
         if (pressure)
             for (int i = 0; i < n; i++) {
@@ -433,36 +350,22 @@ extern "C" int sph_group_render(sph_ctx** ctxs, int n, const sph_params* p, cons
     if (pressure) {   // every member's maximum into ONE word (member 0's); every colour pass behind all of them
         HIPCHK(c0, c0->rnd_max.ensure(sizeof(uint32_t)));
         HIPCHK(c0, hipMemsetAsync(c0->rnd_max.p, 0, sizeof(uint32_t), c0->stream));
-        HIPCHK(c0, hipEventRecord(ev.e[(size_t)n], c0->stream));
-        for (int i = 0; i < n; i++) {
-            sph_ctx* c = ctxs[i];
-            if (i) HIPCHK(c, hipStreamWaitEvent(c->stream, ev.e[(size_t)n], 0));
-            const uint32_t nt = slab_slots(c);
-            if (nt) {
-                ProfScope ps(&c->prof, "slab_render_pmax", c->stream);
-                hipLaunchKernelGGL(k_render_pmax, dim3(std::min((nt + 255) / 256, 1024u)), dim3(256), 0, c->stream, nt,
-                                   (c->pressure_cur ? c->p1 : c->p0).as<float>(), slab_owned(c), c0->rnd_max.as<uint32_t>());
-            }
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(ev.e[(size_t)i], c->stream));
-        }
-        for (int i = 0; i < n; i++)
+        if ((rc = fan_in_to_first(ev, ctxs, n, [&](int i) { return launch_pmax(ctxs[i], c0->rnd_max.as<uint32_t>()); }))) return rc;
+        for (int i = 1; i < n; i++)   // (member 0 has waited for every other; so does every other before it reads the word)
             for (int j = 0; j < n; j++)
                 if (j != i) HIPCHK(ctxs[i], hipStreamWaitEvent(ctxs[i]->stream, ev.e[(size_t)j], 0));
         pmax_dev = c0->rnd_max.as<uint32_t>();
     }
     std::vector<uint32_t> hb((size_t)n * 3, 0u);
-    for (int i = 0; i < n; i++)
-        if ((rc = layer_front(ctxs[i], p, rp, f, 0.f, pmax_dev, &hb[(size_t)i * 3]))) return rc;
     std::vector<LayerRef> L;
-    for (int i = 0; i < n; i++) {
-        sph_ctx* c = ctxs[i];
-        sph_render_band band;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((rc = layer_back(c, f, &hb[(size_t)i * 3], &band))) return rc;
-        HIPCHK(c, hipEventRecord(ev.e[(size_t)i], c->stream));
-        L.push_back(LayerRef{c->rnd_layer.as<u64>(), band.sx0, band.sx1});
-    }
-    for (int i = 1; i < n; i++) HIPCHK(c0, hipStreamWaitEvent(c0->stream, ev.e[(size_t)i], 0));
+    rc = group_layers(
+        ev, ctxs, n, [&](int i) { return layer_front(ctxs[i], p, rp, f, 0.f, pmax_dev, &hb[(size_t)i * 3]); },
+        [&](int i) {
+            sph_render_band band;
+            if (int rb = layer_back(ctxs[i], f, &hb[(size_t)i * 3], &band)) return rb;
+            L.push_back(LayerRef{ctxs[i]->rnd_layer.words.p, band.sx0, band.sx1});
+            return (int)SPH_OK;
+        });
+    if (rc) return rc;
     return merge_and_resolve(c0, rp, f, L, rgb_out);   // (ends with a wait for member 0's stream, which waited for every member's layer)
 }

@@ -685,6 +685,29 @@ def rank_single_step_adaptivity_on_slabs(ctx: ffi.Context, P, dt: float, step_nu
     return info
 
 
+def compose_on_root(mine, compose, what: str, root: int = 0):
+    """The tail of a per-process output flow (render.render_rank, sampling.sample_rank): every rank sends `root` its part through the
+    launcher's process group (torch.distributed gather_object), `root` runs compose(parts).  Returns its result on `root`, None
+    elsewhere; a failure on the root is re-raised on every rank as "<what> failed on rank <root>: ..."."""
+    import torch.distributed as dist
+    rank, world = dist.get_rank(), dist.get_world_size()
+    parts = [None] * world if rank == root else None
+    dist.gather_object(mine, parts, dst=root)
+    out, result = [None], None
+    if rank == root:
+        try:
+            result = compose(parts)
+        except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
+            out = [(type(e).__name__, e.status if isinstance(e, ffi.SphError) else None, str(e))]
+    dist.broadcast_object_list(out, src=root)
+    if out[0] is not None:
+        kind, code, msg = out[0]
+        if code is not None:
+            raise ffi.SphError(code, f"{what} failed on rank {root}: {msg}")
+        raise RuntimeError(f"{what} failed on rank {root} ({kind}): {msg}")
+    return result
+
+
 def _launcher_total(v):
     """the sum of `v` over the ranks of the launcher's process group"""
     import torch.distributed as dist

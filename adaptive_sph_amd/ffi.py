@@ -1067,33 +1067,25 @@ class Context:
     def slab_render_layer_download(self) -> np.ndarray:
         """sph_slab_render_layer_download: the layer drawn last as uint64[HS, sx1 - sx0], row 0 at the top:
         (global id + 1) << 32 | r | g << 8 | b << 16 of the sample's winner among the owned particles, 0 where none covers it."""
-        lib = self._slab_render_lib()
-        shape = getattr(self, "_layer_shape", None)
-        if shape is None:   # (no layer call through this object: the library says what is missing)
-            self._check(lib.slab_render_layer_download(self.handle, None, 0))
-            return np.zeros((0, 0), np.uint64)
-        out = np.empty(shape, np.uint64)
-        self._check(lib.slab_render_layer_download(self.handle, out.ctypes.data if out.size else None, out.size))
-        return out
+        return self._layer_download(self._slab_render_lib().slab_render_layer_download, getattr(self, "_layer_shape", None), np.uint64, (0, 0))
 
     def render_compose(self, rp: "SphRenderParams", bands, layers) -> np.ndarray:
         """sph_render_compose on this context (plain or slab): the ranks' layers -> the frame as uint8[height, width, 3].  layers[k]:
         uint64[HS, sx1 - sx0] of bands[k], or None for an empty band."""
         lib = self._slab_render_lib()
-        k = len(bands)
-        barr = (SphRenderBand * max(1, k))()
-        ptrs = (C.c_void_p * max(1, k))()
-        keep = []
-        for i, (b, l) in enumerate(zip(bands, layers)):
-            barr[i] = SphRenderBand(int(b.sx0), int(b.sx1), int(b.n_drawn), 0)
-            if l is not None and np.asarray(l).size:
-                a = np.ascontiguousarray(l, np.uint64)
-                keep.append(a)
-                ptrs[i] = a.ctypes.data
-            else:
-                ptrs[i] = None
+        barr, ptrs, _keep = _band_and_layer_args(bands, layers, SphRenderBand, "n_drawn", np.uint64)
         out = np.empty((int(rp.height), int(rp.width), 3), np.uint8)
-        self._check(lib.render_compose(self.handle, C.byref(rp), k, barr, ptrs, out.ctypes.data, out.nbytes))
+        self._check(lib.render_compose(self.handle, C.byref(rp), len(bands), barr, ptrs, out.ctypes.data, out.nbytes))
+        return out
+
+    def _layer_download(self, fn, shape, dtype, empty_shape) -> np.ndarray:
+        """The kept layer through `fn` (a sph_slab_*_layer_download) as dtype[shape]; shape None: no layer call went through this
+        object, the library says what is missing."""
+        if shape is None:
+            self._check(fn(self.handle, None, 0))
+            return np.zeros(empty_shape, dtype)
+        out = np.empty(shape, dtype)
+        self._check(fn(self.handle, out.ctypes.data if out.size else None, out.size))
         return out
 
     # ---- fields on a regular grid (include/sph_sample.h; adaptive_sph_amd/sampling.py builds the parameters) ----
@@ -1108,14 +1100,7 @@ class Context:
         into the same buffers.  Density, pressure and the density volume are the last STEP's outputs: sample right behind the step,
         before anything edits the particle vector (include/sph_sample.h, "which state")."""
         lib = self._sample_lib()
-        shape = (1, 1, 1) if sp is None else (max(0, int(sp.n_channels)) + 1, max(0, int(sp.ny)), max(0, int(sp.nx)))
-        if shape[0] > SAMPLE_MAX_CHANNELS + 1 or shape[1] > SAMPLE_MAX_SIDE or shape[2] > SAMPLE_MAX_SIDE:
-            shape = (1, 1, 1)   # (the library refuses the call before it looks at the buffers)
-        count = shape[0] * shape[1] * shape[2]
-        values = np.empty(shape, np.float32) if host is None else host.view("sample:values", np.float32, count).reshape(shape)
-        planes = None
-        if raw:
-            planes = np.empty(shape, np.int64) if host is None else host.view("sample:raw", np.int64, count).reshape(shape)
+        values, planes = _sample_buffers(sp, raw, host)
         info = SphSampleInfo()
         self._check(lib.sample_grid(self.handle, C.byref(params) if params is not None else None, C.byref(sp) if sp is not None else None,
                                     values.ctypes.data if values.size else None, values.nbytes,
@@ -1154,33 +1139,15 @@ class Context:
     def slab_sample_layer_download(self) -> np.ndarray:
         """sph_slab_sample_layer_download: the layer scattered last as int64[C+1, ny, sx1 - sx0], plane 0 = the weight's sums, row 0 = the
         lowest y: the sums of the rank's owned particles' terms at the band's samples."""
-        lib = self._slab_sample_lib()
-        shape = getattr(self, "_sample_layer_shape", None)
-        if shape is None:   # (no layer call through this object: the library says what is missing)
-            self._check(lib.slab_sample_layer_download(self.handle, None, 0))
-            return np.zeros((0, 0, 0), np.int64)
-        out = np.empty(shape, np.int64)
-        self._check(lib.slab_sample_layer_download(self.handle, out.ctypes.data if out.size else None, out.size))
-        return out
+        return self._layer_download(self._slab_sample_lib().slab_sample_layer_download, getattr(self, "_sample_layer_shape", None), np.int64, (0, 0, 0))
 
     def sample_compose(self, sp: "SphSampleParams", bands, layers, raw: bool = False, host: "HostBuffers" = None):
         """sph_sample_compose on this context (plain or slab): the ranks' layers -> (values float32[C+1, ny, nx], raw int64[C+1, ny, nx] or
         None).  layers[k]: int64[C+1, ny, sx1 - sx0] of bands[k], or None for an empty band; sp holds explicit exponents; `host` as in sample_grid."""
         lib = self._slab_sample_lib()
-        k = len(bands)
-        barr = (SphSampleBand * max(1, k))()
-        ptrs = (C.c_void_p * max(1, k))()
-        keep = []
-        for i, (b, l) in enumerate(zip(bands, layers)):
-            barr[i] = SphSampleBand(int(b.sx0), int(b.sx1), int(b.n_boxes), 0)
-            if l is not None and np.asarray(l).size:
-                a = np.ascontiguousarray(l, np.int64)
-                keep.append(a)
-                ptrs[i] = a.ctypes.data
-            else:
-                ptrs[i] = None
+        barr, ptrs, _keep = _band_and_layer_args(bands, layers, SphSampleBand, "n_boxes", np.int64)
         values, planes = _sample_buffers(sp, raw, host)
-        self._check(lib.sample_compose(self.handle, C.byref(sp) if sp is not None else None, k, barr, ptrs, values.ctypes.data if values.size else None,
+        self._check(lib.sample_compose(self.handle, C.byref(sp) if sp is not None else None, len(bands), barr, ptrs, values.ctypes.data if values.size else None,
                                        values.nbytes, planes.ctypes.data if raw and planes.size else None, planes.nbytes if raw else 0))
         return values, planes
 
@@ -1468,6 +1435,24 @@ def relay_plan(lib: "SphLibrary", n_ranks: int, root: int, rank: int, bytes_of_r
         raise SphError(rc, "sph_relay_plan refused its arguments")
     return [{"round": int(s.round), "sub_round": int(s.sub_round), "send": [s.send[0].as_tuple(), s.send[1].as_tuple()],
              "recv": [s.recv[0].as_tuple(), s.recv[1].as_tuple()]} for s in steps[:int(n.value)]]
+
+
+def _band_and_layer_args(bands, layers, band_type, count_field: str, dtype):
+    """The band array and the layer pointers of a compose call: (band_type[k], void*[k], the contiguous arrays the pointers point into
+    -- hold them until the call returns).  count_field: the band's count ("n_drawn", "n_boxes"); a layer that is None or empty
+    passes as NULL."""
+    k = len(bands)
+    barr = (band_type * max(1, k))()
+    ptrs = (C.c_void_p * max(1, k))()
+    keep = []
+    for i, (b, l) in enumerate(zip(bands, layers)):
+        barr[i] = band_type(int(b.sx0), int(b.sx1), int(getattr(b, count_field)), 0)
+        if l is not None and np.asarray(l).size:
+            keep.append(np.ascontiguousarray(l, dtype))
+            ptrs[i] = keep[-1].ctypes.data
+        else:
+            ptrs[i] = None
+    return barr, ptrs, keep
 
 
 def group_render(contexts, params: SphParams, rp: "SphRenderParams") -> np.ndarray:

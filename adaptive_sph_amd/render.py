@@ -21,6 +21,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import ffi
+from .distributed import compose_on_root
 
 f32 = np.float32
 
@@ -260,30 +261,19 @@ def render_rank(ctx: ffi.Context, simulation_params, vis: VisualizationParams, w
     Returns the frame on `root`, None elsewhere; a failure on the root is re-raised on every rank."""
     import torch.distributed as dist
     p, rp = _slab_frame_params("render_rank", simulation_params, vis, width, height, supersample, zoom_out, planes, alpha)
-    rank, world = dist.get_rank(), dist.get_world_size()
     pmax = 0.0
     if vis.visualized_attribute == "Pressure":
-        vals = [None] * world
+        vals = [None] * dist.get_world_size()
         dist.all_gather_object(vals, ctx.slab_render_pressure_max())
         pmax = max(vals)   # (an f32 maximum: the same on every rank whatever the order)
     band = ctx.slab_render_layer(p, rp, pmax)
     layer = ctx.slab_render_layer_download() if band.sx1 > band.sx0 else None
-    parts = [None] * world if rank == root else None
-    dist.gather_object((band.as_tuple(), layer), parts, dst=root)
-    out, frame = [None], None
-    if rank == root:
-        try:
-            bands = [ffi.SphRenderBand(b[0], b[1], b[2], 0) for b, _ in parts]
-            frame = ctx.render_compose(rp, bands, [l for _, l in parts])
-        except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
-            out = [(type(e).__name__, e.status if isinstance(e, ffi.SphError) else None, str(e))]
-    dist.broadcast_object_list(out, src=root)
-    if out[0] is not None:
-        kind, code, msg = out[0]
-        if code is not None:
-            raise ffi.SphError(code, f"render failed on rank {root}: {msg}")
-        raise RuntimeError(f"render failed on rank {root} ({kind}): {msg}")
-    return frame
+
+    def compose(parts):
+        bands = [ffi.SphRenderBand(b[0], b[1], b[2], 0) for b, _ in parts]
+        return ctx.render_compose(rp, bands, [l for _, l in parts])
+
+    return compose_on_root((band.as_tuple(), layer), compose, "render", root)
 
 
 def _u8(c) -> np.ndarray:

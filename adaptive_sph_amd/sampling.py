@@ -14,6 +14,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import ffi
+from .distributed import compose_on_root
 
 # the channel names `sample_grid` takes; "velocity" is short for its two components, "level" for "level_estimation"
 CHANNEL_ALIASES = {"velocity": ("velocity_x", "velocity_y"), "level": ("level_estimation",)}
@@ -151,27 +152,17 @@ def sample_rank(ctx, P, grid: GridSpec, channels: Sequence[str], volume="density
     names = expand_channels(channels)
     sp = sample_params(grid, names, volume, normalize, min_weight, fill, exponents)
     p = P.to_ffi() if hasattr(P, "to_ffi") else P
-    rank, world = dist.get_rank(), dist.get_world_size()
-    words = [None] * world
+    words = [None] * dist.get_world_size()
     dist.all_gather_object(words, ctx.slab_sample_range(p, sp).as_tuple())
     sp = ffi.sample_fold_words(ctx.lib, words, sp)   # (raises the same SphError on every rank)
     band, info = ctx.slab_sample_layer(p, sp)
     layer = ctx.slab_sample_layer_download() if band.sx1 > band.sx0 else None
-    parts = [None] * world if rank == root else None
-    dist.gather_object((band.as_tuple(), (int(info.n_touching), int(info.max_footprint), int(info.n_pairs)), layer), parts, dst=root)
-    out, result = [None], None
-    if rank == root:
-        try:
-            bands = [ffi.SphSampleBand(b[0], b[1], b[2], 0) for b, _, _ in parts]
-            values, planes = ctx.sample_compose(sp, bands, [l for _, _, l in parts], raw=raw, host=host)
-            counts = (sum(c[0] for _, c, _ in parts), max(c[1] for _, c, _ in parts), sum(c[2] for _, c, _ in parts))
-            result = _planes_of(grid, names, values, planes, [sp.channels[k].exponent for k in range(len(names))], counts, raw)
-        except Exception as e:  # noqa: BLE001 -- re-raised on every rank below
-            out = [(type(e).__name__, e.status if isinstance(e, ffi.SphError) else None, str(e))]
-    dist.broadcast_object_list(out, src=root)
-    if out[0] is not None:
-        kind, code, msg = out[0]
-        if code is not None:
-            raise ffi.SphError(code, f"sample failed on rank {root}: {msg}")
-        raise RuntimeError(f"sample failed on rank {root} ({kind}): {msg}")
-    return result
+
+    def compose(parts):
+        bands = [ffi.SphSampleBand(b[0], b[1], b[2], 0) for b, _, _ in parts]
+        values, planes = ctx.sample_compose(sp, bands, [l for _, _, l in parts], raw=raw, host=host)
+        counts = (sum(c[0] for _, c, _ in parts), max(c[1] for _, c, _ in parts), sum(c[2] for _, c, _ in parts))
+        return _planes_of(grid, names, values, planes, [sp.channels[k].exponent for k in range(len(names))], counts, raw)
+
+    mine = (band.as_tuple(), (int(info.n_touching), int(info.max_footprint), int(info.n_pairs)), layer)
+    return compose_on_root(mine, compose, "sample", root)
