@@ -188,8 +188,14 @@ struct MathExact {
 //   * the spline in truncated-power form -- W(q) = 2 [(1-q)+^3 - 4 (1/2-q)+^3], W'(q) = 6 [4 (1/2-q)+^2 - (1-q)+^2] -- two v_max
 //     instead of two compare + select pairs;
 //   * r^2 clamped away from zero instead of the reference's `q > 1e-5 ? .. : 0` select: with dx = dy = 0 the gradient s (dx, dy)
-//     is zero by itself, and W'(q) / r stays finite (-> -2 / (2h) as q -> 0); a pair closer than 1e-5 of the support -- below the
-//     resolution of f32 positions at these scales -- gets a gradient of relative size 1e-5 instead of exactly zero;
+//     is zero by itself, and W'(q) / r stays finite (-> -2 / (2h) as q -> 0).  This is a DEVIATION from the reference for pairs with
+//     about 3e-8 < q <= 1e-5: below 3e-8 d = 4 t^2 - u^2 rounds to exactly 0 and the gradient is zero as in the reference, above 1e-5
+//     the reference has no select either; in between such a pair gets |W'(q)| = 12 q - 18 q^2 <= 12 q, at most 1.2e-4 against the peak
+//     |W'(1/3)| = 2 -- at most 6e-5 of the peak -- where the reference has exactly zero.  f32 positions DO resolve such pairs (at
+//     spacing 0.03 and |x| ~ 0.3, q = 1e-5 is 23 ulps of the position), and ordinary input has them: two scene blocks on a common
+//     lattice give exact duplicates (r = 0: no deviation) and near-duplicates.  Measured on a block with 14 such pairs among 466
+//     particles, one step moves a^p, velocity and position by 2e-5 .. 5e-5 of their max-norm against the reference's cut-off, inside
+//     the FAST bars of 1e-4 (tests/test_gpu_branch_points.py bounds FAST by exactly that difference; profiles/branch_points.md);
 //   * constant factors folded, explicit fma.  `gscale` returns s with grad W_ij = s (dx, dy), so that a sweep whose pair term is
 //     (scalar) x grad W multiplies scalars first and needs two fma for the vector.
 // Stand-alone effect on the Jacobi sweep: 21.9 -> 20.0 us (profiles/r3_jacobi_lab.md).  EXACT mode keeps the reference's operations.

@@ -2166,6 +2166,42 @@ struct OpJacobiU : OpJacobi<MathT> {
     }
 };
 
+#ifdef SPH_LAB
+// Options::jacobi_generic on a scene OpJacobiU would take: OpJacobiU's ARITHMETIC through OpJacobi's gathers (the particle record and the
+// a^p payload beside it), so that the two can be compared bit for bit.  OpJacobiU adds up gscale x e over the neighbours and multiplies
+// the sum by m_i / rho_i (the density sweep's IEEE quotient) once; OpJacobi multiplies every pair by m_j x v_rcp(rho_i) inside the fma --
+// the same coefficient for equal masses, other roundings: 1.2e-7 of the pressure from the first iteration that starts from p != 0
+// (tests/test_gpu_branch_points.py found it; profiles/branch_points.md).  The neighbour's own mass stays in: m_j / m_i is exactly 1 for
+// equal masses, and for masses an ulp apart this form is still the per-neighbour sum tests/test_gpu_chain.py bounds OpJacobiU against.
+template <class MathT>
+struct OpJacobiG : OpJacobi<MathT> {
+    typedef OpJacobi<MathT> B;
+    typedef typename B::NB NB;
+    struct Acc : B::Acc {
+        float m_i;
+    };
+    __device__ void init(Acc&) const {}
+    __device__ NB nb(const Acc& a, uint32_t j, float4 Aj) const { return B::nb(a, j, Aj); }
+    __device__ void begin(Acc& a, uint32_t i, float4 Ai) const
+    {
+        B::begin(a, i, Ai);
+        a.inv_rho_i = this->mrho[i];   // m_i / rho_i
+        a.m_i = Ai.z;
+    }
+    __device__ void pair(Acc& a, float4 Aj, NB Bj, float dx, float dy, float r2, float hij) const
+    {
+        const float e = fmaf(Bj.qx - a.qx, dx, (Bj.qy - a.qy) * dy);
+        a.sum = fmaf(this->m.gscale(r2, hij) * (Aj.z / a.m_i), e, a.sum);
+    }
+    __device__ bool finish(Acc& a, uint32_t i, float4 Ai, bool wall) const
+    {
+        a.sum *= a.inv_rho_i;
+        return B::finish(a, i, Ai, wall);
+    }
+    __device__ void epilogue(Acc& a, bool active, uint32_t blk) const { B::epilogue(a, active, blk); }
+};
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // Op: check_aii (simulation.rs:1347-1375): a_ii against the operator applied to the unit pressure field e_i
 //   calculate_aii_inefficiently = div( a^p[e_i] )_i  (simulation.rs:1324-1345, 1594-1631), tolerance 0.01 in f32.
@@ -3262,7 +3298,8 @@ static int tile_mode(const SweepArgs& a) { return g_tile_mode >= 0 ? g_tile_mode
 #else
 static int tile_mode(const SweepArgs&) { return 0; }   // (the product ships the gather forms only)
 #endif
-// Options::jacobi_generic: the Jacobi update of uniform scenes through OpJacobi as well (measurement: what OpJacobiU is worth)
+// Options::jacobi_generic: the Jacobi update of uniform scenes through OpJacobi's gathers as well -- OpJacobiG, the same arithmetic as
+// OpJacobiU (measurement: what OpJacobiU's single gather is worth; and its twin in the bit-identity tests)
 // SPH_ACCEL_GENERIC (read once per step by the step driver, which then passes no record buffers: the tests compare both forms in one
 // process): sweep A of such scenes through OpPressureAccel, the solves' p / rho^2 as a field of its own
 static bool jacobi_on_records(const SweepArgs& a)   // sweep B gathers {x, y, a^p} whole (OpJacobiU)
@@ -3609,6 +3646,14 @@ void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int
         launch_sweep<OpJacobiU<MathUniform>, false>(s, a, op);
         return;
     }
+#ifdef SPH_LAB
+    if (a.opt_jacobi_generic && !a.exact && a.uniform_h && a.h_mode == SPH_H_FROM_MASS && a.sp.opdisc != SPH_OP_WINCHENBACH2020) {   // OpJacobiU's twin
+        OpJacobiG<MathUniform> op{{uniform_math(a.h_uniform), a.pm, a.orig, a.rho, a.mrho, a.pacc, a.lam_grad, a.aii, a.src, pin, pout, ptout, (float4*)nullptr, a.dens_err,
+                                   (SolverPartial*)a.partials, a.ctrl, a.status, a.sp, iter, residual_density, q, a.solver_tot, a.gate}};
+        launch_sweep<OpJacobiG<MathUniform>, false>(s, a, op);
+        return;
+    }
+#endif
     SPH_DISPATCH(OpJacobi, false, a.pm, a.orig, a.rho, a.mrho, a.pacc, a.lam_grad, a.aii, a.src, pin, pout, ptout, (float4*)nullptr, a.dens_err, (SolverPartial*)a.partials, a.ctrl,
                  a.status, a.sp, iter, residual_density, q, a.solver_tot, a.gate)
 }
