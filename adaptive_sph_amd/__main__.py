@@ -69,6 +69,18 @@ def build_parser() -> argparse.ArgumentParser:
                           "maximum, the particles outside the boundary; taken between the step and its adaptivity, like --grid-vtk; with adaptivity "
                           "the change of mass and momentum across it (adapt_d_*)")
     run.add_argument("--ledger-every", type=int, default=1, help="a row of --ledger every N-th step")
+    # not in the reference either: gauges and tracers, evaluated on the device at the points given (probes.py)
+    run.add_argument("--probes", default=None, metavar="SPEC.yaml",
+                     help="gauge points: `points: [[x, y], ...]`, `lines: [{from, to, count, name}]`, `fields: [...]`, `volume:`; needs --probe-csv")
+    run.add_argument("--probe-csv", default=None, metavar="FILE.csv",
+                     help="one row per N-th step: step, time, dt, then name_or_index:field for every point (the weight first); taken between the "
+                          "step and its adaptivity, like --ledger and --grid-vtk")
+    run.add_argument("--probe-every", type=int, default=1, help="a row of --probe-csv every N-th step")
+    run.add_argument("--tracers-every", type=int, default=None, metavar="K",
+                     help="seed a tracer at the initial position of every K-th particle and move it after each step with that step's dt and the "
+                          "interpolated velocity (explicit Euler; behind the step's adaptivity, rest volume); needs --tracer-vtk")
+    run.add_argument("--tracer-vtk", default=None, metavar="FOLDER",
+                     help="write FOLDER/my-sph-tracers-NNNNN.vtk + my-sph-tracers.vtk.series: the seeds first, then a frame at the cadence of --vtk-every")
     img = sub.add_parser("image", help="Render images (and video frames) as described by export recipes")
     img.add_argument("RECIPE", nargs="+", help="ImageExportConfig list (YAML); paths inside are relative to its directory")
     img.add_argument("--split-patterns", default=None,
@@ -124,6 +136,29 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         ledger_file = open(args.ledger, "w", newline="")
         ledger_csv = csv.writer(ledger_file)
         ledger_csv.writerow(ledger_mod.CSV_COLUMNS)
+    if bool(getattr(args, "probes", None)) != bool(getattr(args, "probe_csv", None)):
+        raise SystemExit("--probes and --probe-csv go together")
+    if (getattr(args, "tracers_every", None) is not None) != bool(getattr(args, "tracer_vtk", None)):
+        raise SystemExit("--tracers-every and --tracer-vtk go together")
+    probe_file, gauges = None, None
+    if getattr(args, "probes", None):
+        import csv
+        from . import probes as probes_mod
+        probe_spec = probes_mod.load_spec(args.probes)
+        gauges = probes_mod.ProbeSet(sim.ctx, probe_spec.points)
+        probe_file = open(args.probe_csv, "w", newline="")
+        probe_csv = csv.writer(probe_file)
+        probe_csv.writerow(probes_mod.csv_columns(probe_spec))
+    tracers, tracer_vtk = None, None
+    if getattr(args, "tracers_every", None) is not None:
+        if args.tracers_every < 1:
+            raise SystemExit("--tracers-every: a positive K")
+        from . import probes as probes_mod
+        from .scene import init_particles
+        from .vtk_exporter import VtkPointsExporter
+        tracers = probes_mod.ProbeSet(sim.ctx, init_particles(scene)[0][:: args.tracers_every])
+        tracer_vtk = VtkPointsExporter(args.tracer_vtk, "my-sph-tracers")
+        tracer_vtk.add_snapshot(sim.time, tracers.points())   # the seeds
     steps, t0 = 0, time.perf_counter()
     while (args.max_seconds is None or sim.time < args.max_seconds) and (args.max_steps is None or steps < args.max_steps):
         dt = sim.single_step_without_adaptivity(p)
@@ -136,8 +171,17 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         led = None
         if ledger_file is not None and steps % max(args.ledger_every, 1) == 0:
             led = ledger_mod.ledger(sim.ctx, p)               # (the same place, for the same reason)
+        if gauges is not None and steps % max(args.probe_every, 1) == 0:
+            # (between the step and its adaptivity too)
+            values = gauges.sample(p, probe_spec.fields, volume=probe_spec.volume)
+            probe_csv.writerow(probes_mod.csv_row(steps, sim.time, dt, probe_spec, values))
         if adaptive:
             sim.single_step_adaptivity(params, dt)
+        if tracers is not None:
+            # behind the adaptivity only what the particles carry is valid: the velocity under the rest volume
+            tracers.advect(p, dt, volume="rest")
+            if snapshot:
+                tracer_vtk.add_snapshot(sim.time, tracers.points())
         if led is not None:
             # behind the adaptivity only what the particles carry is valid: mass and momentum before and after, exactly
             after = ledger_mod.ledger(sim.ctx, p, what="carried") if adaptive else None
@@ -150,6 +194,12 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         grid_vtk.close()
     if ledger_file is not None:
         ledger_file.close()
+    if probe_file is not None:
+        probe_file.close()
+        gauges.close()
+    if tracers is not None:
+        tracer_vtk.close()
+        tracers.close()
     wall = time.perf_counter() - t0
     print(f"{steps} steps, simulated time {sim.time:.6f} s, {sim.num_fluid_particles()} particles, "
           f"{sim.num_fluid_particles() * steps / max(wall, 1e-9) / 1e6:.2f} M particle-steps/s", file=out)

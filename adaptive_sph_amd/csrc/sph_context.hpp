@@ -13,6 +13,8 @@
 #include "sph_carry.hpp"
 #include "sph_internal.hpp"
 
+struct sph_probe_set;   // include/sph_probe.h, sph_probe.hip
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -339,6 +341,11 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // the state ledger (sph_ledger.hip): one partial per block and quantity of a pass, and the words / sums its last launch folds them
     // into -- allocated on first use, kept across calls, freed by sph_destroy
     DevBuf led_part, led_out;
+    // probe sets (sph_probe.hip): the live sets of this context -- a handle that is not in the list is refused without being read --
+    // and the counts of a call (the planes are smp_planes / smp_out: one call at a time runs on the stream); sph_destroy frees what
+    // sph_probe_set_destroy has not
+    std::vector<struct sph_probe_set*> probe_sets;
+    DevBuf prb_stat;
     hipEvent_t ev[8];
 
     int fail(int code, const char* fmt, ...)
@@ -378,3 +385,4 @@ int export_lists_on_device(sph_ctx* c);
 // sets slab_lists_valid / slab_lists_rows / slab_lists_tot (sph_slab_candidates.hip checks the preconditions).
 int slab_lists_on_device(sph_ctx* c);
 void dist_release(sph_ctx* c);  // sph_step.hip
+void probe_sets_release(sph_ctx* c);   // sph_probe.hip: the probe sets sph_probe_set_destroy has not freed

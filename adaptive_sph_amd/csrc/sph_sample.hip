@@ -39,29 +39,6 @@ int check_context(sph_ctx* c, const sph_params* p)
     return SPH_OK;
 }
 
-// the range pass: clears the words, checks the preconditions, reduces max |a| per channel; `out`: the words as the pass left them
-int range_pass(sph_ctx* c, const SampleIn& a, SampleRed* out)
-{
-    hipStream_t s = c->stream;
-    const uint32_t n = (uint32_t)c->n;
-    HIPCHK(c, c->smp_red.ensure(sizeof(SampleRed)));
-    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0, sizeof(SampleRed), s));
-    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0xff, sizeof(unsigned long long), s));
-    if (n) {
-        ProfScope ps(&c->prof, "sample_range", s);
-        hipLaunchKernelGGL(k_sample_range<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, a, c->smp_red.as<SampleRed>(), (const uint8_t*)nullptr);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->smp_red.p, sizeof(SampleRed), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (out->first_bad != ~0ull) {
-        char msg[400];
-        format_offender(msg, sizeof msg, out->first_bad, a.field, a.limit);
-        return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s", msg);
-    }
-    return SPH_OK;
-}
-
 }  // namespace
 
 extern "C" int sph_sample_field_range(sph_ctx* c, const sph_params* p, int field, int component, float* max_abs, int32_t* exponent)

@@ -1,6 +1,6 @@
-// What the field sampling of one context (sph_sample.hip) and of slab contexts (sph_slab_sample.hip) share: the words of the range
-// pass, the terms of include/sph_sample.h, the box of a particle, the range and scatter kernels, the resolve kernel and its launcher,
-// the parameter checks and the exponent rule.  Every operation is one IEEE f32 operation in the header's order (the library is
+// What the field sampling of one context (sph_sample.hip), of slab contexts (sph_slab_sample.hip) and at the points of a probe set
+// (sph_probe.hip) share: the words of the range pass, the terms of include/sph_sample.h (point_pair: one pair once the point is known),
+// the box of a particle, the range and scatter kernels, the resolve kernel and its launcher, the parameter checks and the exponent rule.  Every operation is one IEEE f32 operation in the header's order (the library is
 // compiled with -ffp-contract=off, `/` and sqrtf are correctly rounded).
 //
 // The range and the scatter kernel come in two compile-time variants, in the style of k_render_color<SLAB>:
@@ -8,7 +8,7 @@
 //   <true>   a slab context: a slot takes part only where `owned` says so (nullptr: every slot), and the planes are a BAND of `bw`
 //            sample columns starting at column sx0 -- word (sy, sx - sx0) of a row of bw words
 //
-// Everything sits in an unnamed namespace: each of the two translation units compiles its own copy of the kernels it launches.
+// Everything sits in an unnamed namespace: each of the translation units compiles its own copy of the kernels it launches.
 #pragma once
 
 #include <algorithm>
@@ -156,7 +156,29 @@ __device__ __forceinline__ bool sample_box(const SampleGrid& g, float x, float y
     return true;
 }
 
-// One (particle, sample) pair: the predicate, w once, the adds to every plane.  True: the particle touches the sample.
+// One (particle, point) pair once the point (X, Y) is known -- a sample's centre (sample_pair) or a probe's own two floats
+// (sph_probe.hip: k_probe_scatter): the predicate, w once, the adds to every plane.  `q0`: the point's word of plane 0 (read only behind
+// the predicate), plane c + 1's word lies (c + 1) * plane_stride words behind it; scale[c] = 2^(32 - e_c).  True: the particle touches
+// the point.  THE terms of include/sph_sample.h: both forms call this, so they cannot drift.
+template <int NCH>
+__device__ __forceinline__ bool point_pair(float X, float Y, long long* __restrict__ q0, size_t plane_stride, const float* scale, float x, float y,
+                                           float h, float norm, float V, const float* av)
+{
+    const float dx = X - x, dy = Y - y;
+    const float r = sqrtf(dx * dx + dy * dy);
+    const float q = r / (2.f * h);
+    if (!(q < 1.f)) return false;
+    const float W = norm * cubic_unnorm(q);
+    const float w = V * W;
+    add_i64(q0, (long long)(w * 4294967296.f));
+    for (int c = 0; c < NCH; c++) {
+        const float t = w * av[c];
+        add_i64(q0 + (size_t)(c + 1) * plane_stride, (long long)(t * scale[c]));
+    }
+    return true;
+}
+
+// One (particle, sample) pair: the sample's centre, then point_pair.  True: the particle touches the sample.
 // (0 <= sx < nx, 0 <= sy < ny: the caller's box is clamped to the grid; SLAB: sx0 <= sx < sx0 + bw, clamped to the band)
 template <int NCH, bool SLAB>
 __device__ __forceinline__ bool sample_pair(const SampleGrid& g, long long* __restrict__ planes, size_t plane_stride, int sx0, int bw, int sx, int sy,
@@ -164,19 +186,8 @@ __device__ __forceinline__ bool sample_pair(const SampleGrid& g, long long* __re
 {
     const float X = g.ox + ((float)sx + 0.5f) * g.spacing;
     const float Y = g.oy + ((float)sy + 0.5f) * g.spacing;
-    const float dx = X - x, dy = Y - y;
-    const float r = sqrtf(dx * dx + dy * dy);
-    const float q = r / (2.f * h);
-    if (!(q < 1.f)) return false;
-    const float W = norm * cubic_unnorm(q);
-    const float w = V * W;
     long long* q0 = SLAB ? planes + (size_t)sy * (size_t)bw + (size_t)(sx - sx0) : planes + (size_t)sy * (size_t)g.nx + (size_t)sx;
-    add_i64(q0, (long long)(w * 4294967296.f));
-    for (int c = 0; c < NCH; c++) {
-        const float t = w * av[c];
-        add_i64(q0 + (size_t)(c + 1) * plane_stride, (long long)(t * g.scale[c]));
-    }
-    return true;
+    return point_pair<NCH>(X, Y, q0, plane_stride, g.scale, x, y, h, norm, V, av);
 }
 
 // boxes above this many samples take the row passes (64 of the others: below 2^21 slots).  -DSPH_SAMPLE_FLAT_MAX_AREA=0 builds the
@@ -484,6 +495,29 @@ inline int launch_resolve(sph_ctx* c, const sph_sample_params* sp, const int* ex
     for (int k = 0; k < sp->n_channels; k++) r.scale[k] = std::ldexp(1.0, expo[k] - 32);
     ProfScope ps(&c->prof, "sample_resolve", c->stream);
     hipLaunchKernelGGL(k_sample_resolve, dim3((r.n_samples + 255) / 256), dim3(256), 0, c->stream, r, planes, c->smp_out.as<float>());
+    return SPH_OK;
+}
+
+// the range pass of one context (sph_sample.hip, sph_probe.hip): clears the words, checks the preconditions, reduces max |a| per channel; `out`: the words as the pass left them
+inline int range_pass(sph_ctx* c, const SampleIn& a, SampleRed* out)
+{
+    hipStream_t s = c->stream;
+    const uint32_t n = (uint32_t)c->n;
+    HIPCHK(c, c->smp_red.ensure(sizeof(SampleRed)));
+    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0, sizeof(SampleRed), s));
+    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0xff, sizeof(unsigned long long), s));
+    if (n) {
+        ProfScope ps(&c->prof, "sample_range", s);
+        hipLaunchKernelGGL(k_sample_range<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, a, c->smp_red.as<SampleRed>(), (const uint8_t*)nullptr);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->smp_red.p, sizeof(SampleRed), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (out->first_bad != ~0ull) {
+        char msg[400];
+        format_offender(msg, sizeof msg, out->first_bad, a.field, a.limit);
+        return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s", msg);
+    }
     return SPH_OK;
 }
 

@@ -279,6 +279,28 @@ class SphSampleBand(C.Structure):
         return int(self.sx0), int(self.sx1), int(self.n_boxes)
 
 
+# include/sph_probe.h: the same terms at arbitrary points (probe sets) and the tracer step (product only)
+PROBE_SYMBOLS = ["probe_set_create", "probe_set_upload", "probe_set_download", "probe_set_size", "probe_set_bins", "probe_set_destroy", "probe_sample",
+                 "probe_advect"]
+PROBE_MAX_POINTS = 1 << 24
+PROBE_MAX_CELLS = 1 << 22
+
+
+class SphProbeParams(C.Structure):
+    _fields_ = [("volume", C.c_int32), ("flags", C.c_uint32), ("min_weight", C.c_float), ("fill", C.c_float), ("n_channels", C.c_int32),
+                ("channels", SphSampleChannel * SAMPLE_MAX_CHANNELS)]
+
+
+class SphProbeAdvectParams(C.Structure):
+    _fields_ = [("dt", C.c_float), ("volume", C.c_int32), ("min_weight", C.c_float), ("exponent_x", C.c_int32), ("exponent_y", C.c_int32)]
+
+
+class SphProbeInfo(C.Structure):
+    _fields_ = [("exponents", C.c_int32 * SAMPLE_MAX_CHANNELS), ("n_touching", C.c_uint64), ("n_pairs", C.c_uint64), ("n_touched_points", C.c_uint64),
+                ("n_moved", C.c_uint64), ("n_stalled", C.c_uint64), ("cell_size", C.c_float), ("cells_x", C.c_int32), ("cells_y", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # include/sph_ledger.h: the state ledger -- exact 128-bit sums, extremes with their particle's id, counts (product only)
 LEDGER_SYMBOLS = ["ledger_compute", "slab_ledger_range", "slab_ledger_sums", "ledger_fold_words", "ledger_compose", "group_ledger"]
 LEDGER_N_SUMS, LEDGER_N_EXTREMES = 9, 13
@@ -530,6 +552,15 @@ class SphLibrary:
         self.sample_compose = sig("sample_compose", i32, [vp, spp, i32, sbp, C.POINTER(vp), vp, u64, vp, u64], required=False)
         self.group_sample_grid = sig("group_sample_grid", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), spp, vp, u64, vp, u64, C.POINTER(SphSampleInfo)],
                                      required=False)
+        pip = C.POINTER(SphProbeInfo)
+        self.probe_set_create = sig("probe_set_create", i32, [vp, vp, u64, C.c_float, C.POINTER(vp)], required=False)
+        self.probe_set_upload = sig("probe_set_upload", i32, [vp, vp, vp, u64], required=False)
+        self.probe_set_download = sig("probe_set_download", i32, [vp, vp, vp, u64], required=False)
+        self.probe_set_size = sig("probe_set_size", i32, [vp, vp, pu64], required=False)
+        self.probe_set_bins = sig("probe_set_bins", i32, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)], required=False)
+        self.probe_set_destroy = sig("probe_set_destroy", i32, [vp, vp], required=False)
+        self.probe_sample = sig("probe_sample", i32, [vp, C.POINTER(SphParams), vp, C.POINTER(SphProbeParams), vp, u64, vp, u64, pip], required=False)
+        self.probe_advect = sig("probe_advect", i32, [vp, C.POINTER(SphParams), vp, C.POINTER(SphProbeAdvectParams), pip], required=False)
         lsp, lwp, lsu, lrp = C.POINTER(SphLedgerSpec), C.POINTER(SphLedgerWords), C.POINTER(SphLedgerSum), C.POINTER(SphLedgerResult)
         self.ledger_compute = sig("ledger_compute", i32, [vp, C.POINTER(SphParams), lsp, lrp], required=False)
         self.slab_ledger_range = sig("slab_ledger_range", i32, [vp, C.POINTER(SphParams), lsp, lwp], required=False)

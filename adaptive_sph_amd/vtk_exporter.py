@@ -142,6 +142,37 @@ def write_vtk_grid(path, grid, planes):
             f.write(b"\n")
 
 
+def write_vtk_points(path, points, data=None):
+    """Probe points or tracers (probes.ProbeSet) as legacy 4.2 BINARY POLYDATA: one VERTICES cell per point, an integer `id` array (the
+    point's index in the set: a tracer keeps it from frame to frame), then one float SCALARS array per entry of `data` (name ->
+    float32[n]) in the order given."""
+    pts2 = np.asarray(points, np.float32).reshape(-1, 2)
+    n = len(pts2)
+    data = dict(data or {})
+    for name, a in data.items():
+        if np.shape(a) != (n,):
+            raise ValueError(f"array {name!r} has shape {np.shape(a)}, there are {n} points")
+    pts = np.zeros((n, 3), ">f4")
+    pts[:, :2] = pts2
+    verts = np.empty((n, 2), ">i4")
+    verts[:, 0] = 1
+    verts[:, 1] = np.arange(n)
+    with open(path, "wb") as f:
+        f.write(b"# vtk DataFile Version 4.2\nSPH points 1.0\nBINARY\nDATASET POLYDATA\n")
+        f.write(f"POINTS {n} float\n".encode())
+        f.write(pts.tobytes())
+        f.write(f"\nVERTICES {n} {2 * n}\n".encode())
+        f.write(verts.tobytes())
+        f.write(f"\nPOINT_DATA {n}\n".encode())
+        f.write(b"SCALARS id int 1\nLOOKUP_TABLE default\n")
+        f.write(np.arange(n).astype(">i4").tobytes())
+        f.write(b"\n")
+        for name, a in data.items():
+            f.write(f"SCALARS {name} float 1\nLOOKUP_TABLE default\n".encode())
+            f.write(np.asarray(a).astype(">f4").tobytes())
+            f.write(b"\n")
+
+
 class _Series:
     """The ParaView `<basename>.vtk.series` index both exporters write (vtk_exporter.rs:31-80, 249-253)."""
 
@@ -183,6 +214,17 @@ class VtkGridExporter(_Series):
         name = self.next_name()
         path = os.path.join(self.folder, name)
         write_vtk_grid(path, grid, planes)
+        self.written(name, time)
+        return path
+
+
+class VtkPointsExporter(_Series):
+    """One `write_vtk_points` file per snapshot, `<basename>-NNNNN.vtk`, plus the same `.vtk.series` index as VtkExporter."""
+
+    def add_snapshot(self, time: float, points, data=None) -> str:
+        name = self.next_name()
+        path = os.path.join(self.folder, name)
+        write_vtk_points(path, points, data)
         self.written(name, time)
         return path
 
