@@ -1,7 +1,11 @@
 """Adaptivity data path on the device (sph_share_particles / sph_merge_particles / sph_split_particles, sph_ffi.h) against the
 CPU oracle's statement-by-statement restatement of share_particles / merge_particles / split_particles (oracle/adapt.c), with
 the partner decisions taken ONCE (adaptivity.py, from the oracle's state) and applied to both sides; then whole adaptive runs
-(single_step = step + single_step_adaptivity) of BASELINE configs[0] and of configs[4]'s scene."""
+(single_step = step + single_step_adaptivity) of BASELINE configs[0] and of configs[4]'s scene.
+
+These tests take the decisions that occur naturally.  The designed cases -- the branch points of the closed-form deletion, of the
+share's min, of the split's rounding, clamp and refusals, of the scan tiles, and of the slab form -- live in tests/adapt_cases.py and run
+bit for bit against the oracle in tests/test_gpu_adapt_branch_points.py (on the CPU against the sequential models: tests/test_adapt_cases.py)."""
 from pathlib import Path
 
 import numpy as np

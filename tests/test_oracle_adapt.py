@@ -8,6 +8,7 @@ import pytest
 
 from adaptive_sph_amd import adaptivity as A, ffi, scene as sc
 from adaptive_sph_amd.workloads import default_params
+from tests.adapt_cases import merge_model
 
 REPO = Path(__file__).resolve().parent.parent
 AV, DEL = ffi.MERGE_PARTNER_AVAILABLE, ffi.MERGE_PARTNER_DELETE
@@ -33,38 +34,6 @@ def test_split_patterns_file():
         sp.get(60)
     # a 1-to-2 split puts the children on opposite sides of the parent
     assert np.allclose(sp.get(2)[0], -sp.get(2)[1], atol=1e-6)
-
-
-def merge_model(mass, pos, vel, h2n, partner, counter, min_partners, rho0):
-    """particle_merging.rs:270-370 on python lists of per-particle records (everything swaps together)."""
-    f32 = np.float32
-    n = len(mass)
-    mass, pos, vel, h2n = mass.copy(), pos.copy(), vel.copy(), h2n.copy()
-    ident = np.arange(n)
-    partner, counter = partner.copy(), counter.copy()
-    m0, x0, v0 = mass.copy(), pos.copy(), vel.copy()
-    for i in range(n):
-        j = partner[i]
-        if j in (AV, DEL) or counter[j] < min_partners:
-            continue
-        mass_n = f32(m0[j]) / f32(counter[j])
-        m = f32(m0[i]) + mass_n
-        vel[i] = (f32(m0[i]) * v0[i] + mass_n * v0[j]) / m
-        pos[i] = (f32(m0[i]) * x0[i] + mass_n * x0[j]) / m
-        mass[i] = m
-        h2n[i] = f32(1.9) * np.sqrt((m / f32(rho0)) * f32(1 / np.pi), dtype=np.float32)
-    last, i = n - 1, 0
-    while i <= last:
-        if partner[i] == DEL and counter[i] >= min_partners:
-            mass[i] = mass[i] - mass[i]
-            if mass[i] < 0.000001:
-                for a in (mass, pos, vel, h2n, ident, partner, counter):
-                    a[[i, last]] = a[[last, i]]
-                last -= 1
-                continue
-        i += 1
-    k = last + 1
-    return mass[:k], pos[:k], vel[:k], h2n[:k], ident[:k]
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
