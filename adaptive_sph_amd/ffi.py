@@ -469,6 +469,8 @@ class SphLibrary:
                                       required=False)
         self.last_error = sig("last_error", C.c_char_p, [vp])
         self.grid = sig("grid", i32, [vp, C.POINTER(SphGridInfo)])
+        # oracle-only (beside the ABI): per-particle residual and class of the last iteration of one of the step's solves
+        self.solve_residuals = sig("solve_residuals", i32, [vp, i32, vp, vp, u64], required=False)
         # product-only entry points (the oracle has no device, profiler or communicator)
         self.profile_enable = sig("profile_enable", i32, [vp, i32], required=False)
         self.profile_reset = sig("profile_reset", i32, [vp], required=False)
@@ -727,6 +729,16 @@ class Context:
         st = SphStepStats()
         self._check(self.lib.step(self.handle, C.byref(params), C.byref(st)))
         return st
+
+    def solve_residuals(self, which: str):
+        """Oracle only: (residual, class) per particle of the LAST Jacobi iteration of the last step's "divergence" or "density" solve --
+        what its statistics added up (class 0 normal: in the sum; 1 singular; 2 negative)."""
+        if self.lib.solve_residuals is None:
+            raise SphError(30, "solve_residuals: the CPU oracle's entry point, not part of include/sph_ffi.h")
+        n = self.n
+        res, cls = np.empty(n, np.float32), np.empty(n, np.uint8)
+        self._check(self.lib.solve_residuals(self.handle, {"divergence": 0, "density": 1}[which], res.ctypes.data, cls.ctypes.data, n))
+        return res, cls
 
     def classify(self, params: SphParams) -> None:
         """classify_particles (adaptivity/mod.rs:50-59): the host's call, never part of the step."""

@@ -78,6 +78,7 @@ int oracle_create(uint64_t n_capacity, int device_id, const sph_plane* planes, i
     ALLOC(c->neighbor_count, n, uint32_t); ALLOC(c->lam_n, n, uint8_t);
     ALLOC(c->lam, n * ORC_MAX_PLANES, float); ALLOC(c->lam_gx, n * ORC_MAX_PLANES, float); ALLOC(c->lam_gy, n * ORC_MAX_PLANES, float);
     ALLOC(c->nb_off, n + 1, uint64_t); ALLOC(c->cell_index, n, uint32_t);
+    for (int k = 0; k < 2; k++) { ALLOC(c->solve_residual[k], n, float); ALLOC(c->solve_class[k], n, uint8_t); }
     c->nb_cap = 0;
     c->nb_idx = NULL;
     *out = c;
@@ -92,6 +93,7 @@ void oracle_destroy(oracle_ctx* c)
     free(c->level); free(c->level_tmp); free(c->level_old); free(c->constant_field); free(c->stash);
     free(c->flag_surface); free(c->flag_insufficient); free(c->size_class); free(c->flag_reduced); free(c->neighbor_count); free(c->lam_n);
     free(c->lam); free(c->lam_gx); free(c->lam_gy); free(c->nb_off); free(c->nb_idx); free(c->nb_idx2); free(c->cell_index);
+    for (int k = 0; k < 2; k++) { free(c->solve_residual[k]); free(c->solve_class[k]); }
     free(c);
 }
 
@@ -290,6 +292,19 @@ int oracle_classify(oracle_ctx* c, const sph_params* p)
 {
     if (!c || !p) return SPH_ERR_INVALID_ARGUMENT;
     return orc_classify_particles(c, p);
+}
+
+/* ORACLE ONLY (beside the ABI of include/sph_ffi.h): what the last Jacobi iteration of one of the last step's solves fed into its
+ * statistics, per particle in host order -- the residual (density: rho dt^2 (s - a_p); divergence: dt (s - a_p), which no field
+ * keeps) and the class (0 normal: enters the sum; 1 singular; 2 negative).  which: 0 the divergence solve, 1 the density solve. */
+int oracle_solve_residuals(oracle_ctx* c, int which, float* residual, uint8_t* cls, uint64_t n)
+{
+    if (!c || which < 0 || which > 1 || !residual || !cls) return SPH_ERR_INVALID_ARGUMENT;
+    if (!c->solve_ran[which]) return orc_fail(c, SPH_ERR_INVALID_ARGUMENT, "the last step ran no %s solve", which ? "density" : "divergence");
+    if (n != c->n) return orc_fail(c, SPH_ERR_INVALID_ARGUMENT, "solve residuals: size mismatch");
+    memcpy(residual, c->solve_residual[which], n * sizeof(float));
+    memcpy(cls, c->solve_class[which], n * sizeof(uint8_t));
+    return SPH_OK;
 }
 
 const char* oracle_last_error(const oracle_ctx* c) { return c ? c->err : "null context"; }

@@ -43,6 +43,11 @@ typedef struct oracle_ctx {
     float *constant_field, *stash;
     uint8_t *flag_surface, *flag_insufficient, *size_class, *flag_reduced;
     uint32_t* neighbor_count;
+    /* the LAST Jacobi iteration of each of the step's solves, per particle (oracle_solve_residuals; [0] the divergence solve, [1] the
+     * density solve): the residual as the statistics add it up, and its class -- 0 normal, 1 singular, 2 negative */
+    float* solve_residual[2];
+    uint8_t* solve_class[2];
+    int solve_ran[2];
 
     /* BoundaryWinchenbach2020.lambda: Vec<Vec<(FT, VF<2>)>> (boundary_winchenbach2020.rs:27) */
     uint8_t* lam_n;

@@ -532,6 +532,8 @@ static int single_pressure_iteration(oracle_ctx* c, const sph_params* p, float d
     const uint64_t nch = (n + CH - 1) / CH;
     solver_acc* part = (solver_acc*)calloc(nch ? nch : 1, sizeof(solver_acc));
     int bad_ap = 0, bad_p = 0;
+    float* const res_out = c->solve_residual[residual == RES_DENSITY];
+    uint8_t* const cls_out = c->solve_class[residual == RES_DENSITY];
 #pragma omp parallel for schedule(static) reduction(| : bad_ap, bad_p)
     for (int64_t cc = 0; cc < (int64_t)nch; cc++) {
         solver_acc a = {0, 0, 0, 0.f, 0.f};
@@ -540,6 +542,8 @@ static int single_pressure_iteration(oracle_ctx* c, const sph_params* p, float d
             if (fabsf(c->aii[i]) < 10e-4f) {
                 c->pressure_next[i] = 0.f;
                 a.singular++;
+                res_out[i] = 0.f;
+                cls_out[i] = 1;
                 continue;
             }
             float a_p = divergence_iisph(c, p, c->pacc, i);
@@ -554,6 +558,8 @@ static int single_pressure_iteration(oracle_ctx* c, const sph_params* p, float d
             } else {
                 err = dt * (s - a_p);
             }
+            res_out[i] = err;
+            cls_out[i] = pn <= 0.f && clamp ? 2 : 0;
             if (pn <= 0.f && clamp) {
                 c->pressure_next[i] = 0.f;
                 a.negative++;
@@ -590,6 +596,7 @@ static int pressure_iterations(oracle_ctx* c, const sph_params* p, float dt, flo
                                              (unsigned long long)i, (double)c->aii[i]);
     uint32_t iters = 0;
     solver_acc a;
+    c->solve_ran[residual == RES_DENSITY] = 1;
     for (;;) {
         int rc = single_pressure_iteration(c, p, dt, residual, clamp, &a);
         if (rc) return rc;
@@ -958,6 +965,7 @@ int orc_step(oracle_ctx* c, const sph_params* p, sph_step_stats* out)
     sph_step_stats st;
     memset(&st, 0, sizeof st);
     st.n_particles = c->n;
+    c->solve_ran[0] = c->solve_ran[1] = 0;
 
     if (c->n_planes == 0) return orc_fail(c, SPH_ERR_NO_BOUNDARY, "not implemented: NoBoundaryHandler::iisph_aii");
 

@@ -23,27 +23,13 @@ import pytest
 
 from adaptive_sph_amd import ffi, scene as sc
 from adaptive_sph_amd.workloads import dam_break_params, default_params
+from tests import solve_reference
+from tests.solve_reference import device_order, h_from_mass, model_avg_error, model_from_oracle   # (the order helpers live there: pure numpy)
 
 pytestmark = pytest.mark.gpu
 
 STEP_FIELDS = ["position", "velocity", "density", "pressure", "pressure_accel", "aii", "ppe_source_term", "constant_field",
                "lambda_sum", "lambda_grad_sum", "h2", "neighbor_count", "cell_index"]
-
-
-def h_from_mass(mass, rest_density=1.0):
-    """h_next_from_mass (simulation.rs:1865-1871) in f32: 1.9 sqrt((m / rho0) (1 / pi))"""
-    vol = mass.astype(np.float32) / np.float32(rest_density)
-    return np.float32(1.9) * np.sqrt(vol * np.float32(0.318309873342514038086), dtype=np.float32)
-
-
-def device_order(pos, h):
-    """The device's slot order for particles at `pos`: stable sort by the cell of the SORTING grid -- cell = the support 2 h of the
-    smallest particle, cell index floor(x / cs) per axis (IEEE f32 division, neighborhood_search.rs:253-255), cells ordered x fastest
-    (:383-395); ties keep the upload order."""
-    cs = np.float32(2.0) * np.float32(h.min())
-    cx = np.floor(pos[:, 0].astype(np.float32) / cs)
-    cy = np.floor(pos[:, 1].astype(np.float32) / cs)
-    return np.lexsort((cx, cy))
 
 
 def forced(base=dam_break_params, **kw):
@@ -61,6 +47,11 @@ def assert_bit_identical(g, o, fields, where=""):
 
 def solver_counts(s):
     return (int(s.iters), int(s.normal_count), int(s.negative_count), int(s.singular_count))
+
+
+def solves_of(solver):
+    """the residuals a step of `solver` reduces (IISPH2 is IISPH with another source term)"""
+    return solve_reference.solves_of("IISPH" if solver == "IISPH2" else solver)
 
 
 def stepwise(product_lib, oracle_lib, mass, pos, vel, planes, params, steps, fields=STEP_FIELDS, counts=True):
@@ -83,14 +74,26 @@ def stepwise(product_lib, oracle_lib, mass, pos, vel, planes, params, steps, fie
         if np.ptp(h_from_mass(m)) == 0:
             assert (np.diff(ci) >= 0).all(), where + "the upload order is not the device's slot order"
         assert_bit_identical(g, o, fields, where)
+        solves = solves_of(params.pressure_solver_method)
+        if "density" in solves:   # the density residual of the last Jacobi iteration, as sweep B left it
+            assert_bit_identical(g, o, ["density_error"], where)
         if counts:   # the residual classes of the last Jacobi iteration: integer counts of bit-identical pressures
             assert solver_counts(sg.div_solver) == solver_counts(so.div_solver), where
             assert solver_counts(sg.density_solver) == solver_counts(so.density_solver), where
-            # the residual sums are reduced in different orders (per-block partials on the device): a relative bar, not bits
+            # the ORACLE reduces the residual sums in another order (chunks of 1024) than the device (per-block partials): a relative
+            # bar against it, not bits ...
             for a, b in ((sg.div_solver, so.div_solver), (sg.density_solver, so.density_solver)):
                 if a.normal_count:   # (no "normal" particle: the average is NaN on both sides)
                     assert abs(a.avg_error - b.avg_error) <= 1e-5 * abs(b.avg_error) + 1e-12, where
                 assert a.max_error == b.max_error, where
+            # ... and BITS against the device's own order restated in numpy (tests/solve_reference.py) on the oracle's residuals
+            for which in solves:
+                a = sg.density_solver if which == "density" else sg.div_solver
+                _, totals = model_from_oracle(o, which)
+                assert (int(a.normal_count), int(a.negative_count), int(a.singular_count)) == (totals["normal"], totals["negative"], totals["singular"]), where + which
+                assert np.float32(a.max_error).view(np.uint32) == totals["max_err"].view(np.uint32), where + which
+                if a.normal_count:
+                    assert np.float32(a.avg_error).view(np.uint32) == model_avg_error(totals).view(np.uint32), where + which
         x, v = o.download("position"), o.download("velocity")
         g.close()
         o.close()

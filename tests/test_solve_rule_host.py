@@ -11,6 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.solve_reference import oracle_stop   # the oracle's statement of the rule in float32
+
 REPO = Path(__file__).resolve().parent.parent
 SOURCE = REPO / "tests" / "host" / "solve_rule_check.cpp"
 FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off", "-I", str(REPO / "adaptive_sph_amd" / "csrc")]
@@ -48,19 +50,6 @@ def check(tmp_path_factory):
 
 def bits(x):
     return "%x" % struct.unpack("<I", struct.pack("<f", float(F(x))))[0]
-
-
-def oracle_stop(residual_density, max_avg_error, max_iters, normal, sum_err, it, rest_density, dt):
-    """oracle/step.c, the end of the loop of iisph_pressure_iterations, in float32: the two `break`s of the residual mode, then max_iters"""
-    with np.errstate(all="ignore"):
-        avg = F(sum_err) / F(normal) if normal > 0 else F(np.nan)
-        if residual_density:
-            if normal == 0 or (np.abs(avg / F(rest_density)) < F(max_avg_error) and it > 1):
-                return True
-        else:
-            if normal == 0 or (np.abs(avg) < F(max_avg_error) / F(dt) and it > 1):
-                return True
-    return it == max_iters
 
 
 def below(x):
