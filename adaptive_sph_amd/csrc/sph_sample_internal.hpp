@@ -13,9 +13,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 
 #include "sph_context.hpp"
 #include "sph_sample.h"
+#include "sph_slab_sample.h"   // sph_slab_sample_words: the verdict the fold takes
 
 namespace {
 
@@ -518,6 +520,88 @@ inline int range_pass(sph_ctx* c, const SampleIn& a, SampleRed* out)
         format_offender(msg, sizeof msg, out->first_bad, a.field, a.limit);
         return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s", msg);
     }
+    return SPH_OK;
+}
+
+// ---- slab contexts (sph_slab_sample.hip, sph_slab_probe.hip): the words, the range pass over the owned slots, the fold ----
+// what a call on a slab context refuses of the context itself.  plain_hint: what serves a plain context instead
+inline int slab_refuse(sph_ctx* c, const char* what, const char* plain_hint)
+{
+    if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (%s)", what, plain_hint);
+    if (c->poisoned) return c->refuse_poisoned();
+    return SPH_OK;
+}
+
+// a layer or compose call takes explicit exponents only.  fold_first: the calls that give them ("... come first")
+inline int refuse_auto(sph_ctx* c, const char* what, const sph_sample_params* sp, const char* fold_first)
+{
+    for (int k = 0; k < sp->n_channels; k++)
+        if (sp->channels[k].exponent == SPH_SAMPLE_AUTO_EXPONENT)
+            return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: channel %d has an automatic exponent (%s: every rank must scatter with the exponents of the whole "
+                                                     "vector)", what, k, fold_first);
+    return SPH_OK;
+}
+
+inline void exponents_of(const sph_sample_params* sp, int* expo)
+{
+    for (int k = 0; k < kMaxCh; k++) expo[k] = k < sp->n_channels ? sp->channels[k].exponent : 0;
+}
+
+// clear c's words on its stream (the group call orders that before the range launches of the other members)
+inline int clear_words(sph_ctx* c)
+{
+    HIPCHK(c, c->smp_red.ensure(sizeof(SampleRed)));
+    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0, sizeof(SampleRed), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0xff, sizeof(unsigned long long), c->stream));
+    return SPH_OK;
+}
+
+// a slab context's range pass over its nt slots (owned: sph_slab_layers.hpp's owned_flags), on c's stream, into `red` (its own words, or
+// member 0's)
+inline int launch_range(sph_ctx* c, const SampleIn& a, SampleRed* red, uint32_t nt, const uint8_t* owned)
+{
+    if (nt) {
+        ProfScope ps(&c->prof, "slab_sample_range", c->stream);
+        hipLaunchKernelGGL(k_sample_range<true>, dim3((nt + 255) / 256), dim3(256), 0, c->stream, nt, a, red, owned);
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPH_OK;
+}
+
+// the verdict of the folded words: the offender's sentence, or the exponents of the whole vector in sp_io
+inline int fold_words(int n, const sph_slab_sample_words* words, sph_sample_params* sp_io, char* msg, size_t msg_bytes)
+{
+    sph_slab_sample_words w;
+    w.first_bad = ~0ull;
+    for (int k = 0; k < kMaxCh; k++) w.max_bits[k] = 0u;
+    for (int r = 0; r < n; r++) {
+        w.first_bad = std::min<uint64_t>(w.first_bad, words[r].first_bad);
+        for (int k = 0; k < kMaxCh; k++) w.max_bits[k] = std::max(w.max_bits[k], words[r].max_bits[k]);
+    }
+    const int C = std::min(std::max(sp_io->n_channels, 0), kMaxCh);
+    int fields[kMaxCh] = {0, 0, 0, 0, 0, 0};
+    float limit[kMaxCh];
+    for (int k = 0; k < kMaxCh; k++) {
+        const int e = k < C ? sp_io->channels[k].exponent : SPH_SAMPLE_AUTO_EXPONENT;
+        if (k < C) fields[k] = sp_io->channels[k].field;
+        limit[k] = e == SPH_SAMPLE_AUTO_EXPONENT ? INFINITY : std::ldexp(1.f, std::min(std::max(e, -200), 200));
+    }
+    if (w.first_bad != ~0ull) {
+        if (msg && msg_bytes) format_offender(msg, msg_bytes, w.first_bad, fields, limit);
+        return SPH_ERR_INVALID_ARGUMENT;
+    }
+    for (int k = 0; k < C; k++) {
+        if (sp_io->channels[k].exponent != SPH_SAMPLE_AUTO_EXPONENT) continue;
+        int e = 0;
+        if (!auto_exponent(w.max_bits[k], e)) {
+            if (msg && msg_bytes)
+                snprintf(msg, msg_bytes, "sample: channel %d (%s) needs the exponent %d (at most %d)", k, field_name(fields[k]) ? field_name(fields[k]) : "?", e,
+                         SPH_SAMPLE_MAX_EXPONENT);
+            return SPH_ERR_INVALID_ARGUMENT;
+        }
+        sp_io->channels[k].exponent = e;
+    }
+    if (msg && msg_bytes) msg[0] = 0;
     return SPH_OK;
 }
 

@@ -59,91 +59,16 @@ __global__ __launch_bounds__(256) void k_sample_merge(long long* __restrict__ ds
     dst[at] = dst[at] + src[t];
 }
 
-int slab_refuse(sph_ctx* c, const char* what)
-{
-    if (!c->dist.on) return c->fail(SPH_ERR_UNSUPPORTED, "%s: not a slab context (sph_sample_grid samples a plain context)", what);
-    if (c->poisoned) return c->refuse_poisoned();
-    return SPH_OK;
-}
+// what serves a plain context instead, and what gives a layer call its exponents
+const char* const kPlainHint = "sph_sample_grid samples a plain context";
+const char* const kFoldFirst = "sph_slab_sample_range and sph_sample_fold_words come first";
 
 // everything a per-rank call refuses before it launches, in sph_sample_grid's order where it refuses the same
 int check_rank_call(sph_ctx* c, const char* what, const sph_params* p, const sph_sample_params* sp)
 {
     if (!p) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sample: null parameters");
-    if (int rc = slab_refuse(c, what)) return rc;
+    if (int rc = slab_refuse(c, what, kPlainHint)) return rc;
     return check_sample_params(c, sp);
-}
-
-int refuse_auto(sph_ctx* c, const char* what, const sph_sample_params* sp)
-{
-    for (int k = 0; k < sp->n_channels; k++)
-        if (sp->channels[k].exponent == SPH_SAMPLE_AUTO_EXPONENT)
-            return c->fail(SPH_ERR_INVALID_ARGUMENT, "%s: channel %d has an automatic exponent (sph_slab_sample_range and sph_sample_fold_words come first: "
-                                                     "every rank must scatter with the exponents of the whole vector)", what, k);
-    return SPH_OK;
-}
-
-// clear c's words on its stream (the group call orders that before the range launches of the other members)
-int clear_words(sph_ctx* c)
-{
-    HIPCHK(c, c->smp_red.ensure(sizeof(SampleRed)));
-    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0, sizeof(SampleRed), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->smp_red.p, 0xff, sizeof(unsigned long long), c->stream));
-    return SPH_OK;
-}
-
-// c's range pass over its owned slots, on c's stream, into `red` (its own words, or member 0's)
-int launch_range(sph_ctx* c, const SampleIn& a, SampleRed* red)
-{
-    const uint32_t nt = owned_slots(c);
-    if (nt) {
-        ProfScope ps(&c->prof, "slab_sample_range", c->stream);
-        hipLaunchKernelGGL(k_sample_range<true>, dim3((nt + 255) / 256), dim3(256), 0, c->stream, nt, a, red, owned_flags(c));
-    }
-    HIPCHK(c, hipGetLastError());
-    return SPH_OK;
-}
-
-// the verdict of the folded words: the offender's sentence, or the exponents of the whole vector in sp_io
-int fold_words(int n, const sph_slab_sample_words* words, sph_sample_params* sp_io, char* msg, size_t msg_bytes)
-{
-    sph_slab_sample_words w;
-    w.first_bad = ~0ull;
-    for (int k = 0; k < kMaxCh; k++) w.max_bits[k] = 0u;
-    for (int r = 0; r < n; r++) {
-        w.first_bad = std::min<uint64_t>(w.first_bad, words[r].first_bad);
-        for (int k = 0; k < kMaxCh; k++) w.max_bits[k] = std::max(w.max_bits[k], words[r].max_bits[k]);
-    }
-    const int C = std::min(std::max(sp_io->n_channels, 0), kMaxCh);
-    int fields[kMaxCh] = {0, 0, 0, 0, 0, 0};
-    float limit[kMaxCh];
-    for (int k = 0; k < kMaxCh; k++) {
-        const int e = k < C ? sp_io->channels[k].exponent : SPH_SAMPLE_AUTO_EXPONENT;
-        if (k < C) fields[k] = sp_io->channels[k].field;
-        limit[k] = e == SPH_SAMPLE_AUTO_EXPONENT ? INFINITY : std::ldexp(1.f, std::min(std::max(e, -200), 200));
-    }
-    if (w.first_bad != ~0ull) {
-        if (msg && msg_bytes) format_offender(msg, msg_bytes, w.first_bad, fields, limit);
-        return SPH_ERR_INVALID_ARGUMENT;
-    }
-    for (int k = 0; k < C; k++) {
-        if (sp_io->channels[k].exponent != SPH_SAMPLE_AUTO_EXPONENT) continue;
-        int e = 0;
-        if (!auto_exponent(w.max_bits[k], e)) {
-            if (msg && msg_bytes)
-                snprintf(msg, msg_bytes, "sample: channel %d (%s) needs the exponent %d (at most %d)", k, field_name(fields[k]) ? field_name(fields[k]) : "?", e,
-                         SPH_SAMPLE_MAX_EXPONENT);
-            return SPH_ERR_INVALID_ARGUMENT;
-        }
-        sp_io->channels[k].exponent = e;
-    }
-    if (msg && msg_bytes) msg[0] = 0;
-    return SPH_OK;
-}
-
-void exponents_of(const sph_sample_params* sp, int* expo)
-{
-    for (int k = 0; k < kMaxCh; k++) expo[k] = k < sp->n_channels ? sp->channels[k].exponent : 0;
 }
 
 // ---- a layer in two halves: up to the copy of the band words (queued), and from the band on (after the wait) ----
@@ -250,7 +175,7 @@ extern "C" int sph_slab_sample_range(sph_ctx* c, const sph_params* p, const sph_
     HIPCHK(c, hipSetDevice(c->device));
     const SampleIn a = make_sample_in(c, p, sp);
     if (int rc = clear_words(c)) return rc;
-    if (int rc = launch_range(c, a, c->smp_red.as<SampleRed>())) return rc;
+    if (int rc = launch_range(c, a, c->smp_red.as<SampleRed>(), owned_slots(c), owned_flags(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->smp_red.p, sizeof *out, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SPH_OK;
@@ -272,7 +197,7 @@ extern "C" int sph_slab_sample_layer(sph_ctx* c, const sph_params* p, const sph_
     if (!band) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sph_slab_sample_layer: null band");
     *band = sph_sample_band{0, 0, 0, 0};
     if (int rc = check_rank_call(c, "sph_slab_sample_layer", p, sp)) return rc;
-    if (int rc = refuse_auto(c, "sph_slab_sample_layer", sp)) return rc;
+    if (int rc = refuse_auto(c, "sph_slab_sample_layer", sp, kFoldFirst)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     int expo[kMaxCh];
     exponents_of(sp, expo);
@@ -304,7 +229,7 @@ extern "C" int sph_sample_compose(sph_ctx* c, const sph_sample_params* sp, int n
     if (!c) return SPH_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_sample_params(c, sp))) return rc;
-    if ((rc = refuse_auto(c, "sph_sample_compose", sp))) return rc;
+    if ((rc = refuse_auto(c, "sph_sample_compose", sp, kFoldFirst))) return rc;
     if ((rc = check_sample_buffers(c, sp, values_out, values_bytes, raw_out, raw_bytes))) return rc;
     if (n_layers < 0 || (n_layers > 0 && !bands)) return c->fail(SPH_ERR_INVALID_ARGUMENT, "sample: %d layers without their bands", n_layers);
     std::vector<LayerRef> L;
@@ -354,7 +279,7 @@ int group_sample_grid(sph_ctx** ctxs, int n, const sph_params* p, const sph_samp
         HIPCHK(c0, ev.create((size_t)n + 1));
         // every member's range pass into ONE set of words (member 0's): the atomic minimum and maxima fold by themselves
         if ((rc = clear_words(c0))) return rc;
-        rc = fan_in_to_first(ev, ctxs, n, [&](int i) { return launch_range(ctxs[i], make_sample_in(ctxs[i], p, sp), c0->smp_red.as<SampleRed>()); });
+        rc = fan_in_to_first(ev, ctxs, n, [&](int i) { return launch_range(ctxs[i], make_sample_in(ctxs[i], p, sp), c0->smp_red.as<SampleRed>(), owned_slots(ctxs[i]), owned_flags(ctxs[i])); });
         if (rc) return rc;
         sph_slab_sample_words words;
         HIPCHK(c0, hipMemcpyAsync(&words, c0->smp_red.p, sizeof words, hipMemcpyDeviceToHost, c0->stream));

@@ -146,6 +146,7 @@ class SphError(RuntimeError):
 
     def __init__(self, status: int, message: str):
         self.status = status
+        self.message = message   # (without the status name that str() puts in front)
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {message}")
 
 
@@ -299,6 +300,16 @@ class SphProbeInfo(C.Structure):
     _fields_ = [("exponents", C.c_int32 * SAMPLE_MAX_CHANNELS), ("n_touching", C.c_uint64), ("n_pairs", C.c_uint64), ("n_touched_points", C.c_uint64),
                 ("n_moved", C.c_uint64), ("n_stalled", C.c_uint64), ("cell_size", C.c_float), ("cells_x", C.c_int32), ("cells_y", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+# include/sph_slab_probe.h: probe sets on slab contexts -- compact rank layers of int64 sums added per point (product only)
+SLAB_PROBE_SYMBOLS = ["slab_probe_range", "probe_fold_words", "slab_probe_layer", "slab_probe_layer_download", "probe_compose", "probe_compose_advect",
+                      "group_probe_sample", "group_probe_advect"]
+
+
+class SphSlabProbeLayerInfo(C.Structure):
+    """sph_slab_probe_layer_info: the entries of a rank's compact layer, the exponents used, the rank's own counts."""
+    _fields_ = [("exponents", C.c_int32 * SAMPLE_MAX_CHANNELS), ("n_entries", C.c_uint64), ("n_touching", C.c_uint64), ("n_pairs", C.c_uint64)]
 
 
 # include/sph_ledger.h: the state ledger -- exact 128-bit sums, extremes with their particle's id, counts (product only)
@@ -563,6 +574,16 @@ class SphLibrary:
         self.probe_set_destroy = sig("probe_set_destroy", i32, [vp, vp], required=False)
         self.probe_sample = sig("probe_sample", i32, [vp, C.POINTER(SphParams), vp, C.POINTER(SphProbeParams), vp, u64, vp, u64, pip], required=False)
         self.probe_advect = sig("probe_advect", i32, [vp, C.POINTER(SphParams), vp, C.POINTER(SphProbeAdvectParams), pip], required=False)
+        ppp, app, lip = C.POINTER(SphProbeParams), C.POINTER(SphProbeAdvectParams), C.POINTER(SphSlabProbeLayerInfo)
+        self.slab_probe_range = sig("slab_probe_range", i32, [vp, C.POINTER(SphParams), ppp, swp], required=False)
+        self.probe_fold_words = sig("probe_fold_words", i32, [i32, swp, ppp, C.c_char_p, u64], required=False)
+        self.slab_probe_layer = sig("slab_probe_layer", i32, [vp, C.POINTER(SphParams), vp, ppp, lip], required=False)
+        self.slab_probe_layer_download = sig("slab_probe_layer_download", i32, [vp, vp, vp, vp, u64], required=False)
+        self.probe_compose = sig("probe_compose", i32, [vp, vp, ppp, i32, pu64, C.POINTER(vp), C.POINTER(vp), vp, u64, vp, u64, pip], required=False)
+        self.probe_compose_advect = sig("probe_compose_advect", i32, [vp, vp, app, i32, pu64, C.POINTER(vp), C.POINTER(vp), pip], required=False)
+        self.group_probe_sample = sig("group_probe_sample", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), C.POINTER(vp), ppp, vp, u64, vp, u64, pip],
+                                      required=False)
+        self.group_probe_advect = sig("group_probe_advect", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), C.POINTER(vp), app, pip], required=False)
         lsp, lwp, lsu, lrp = C.POINTER(SphLedgerSpec), C.POINTER(SphLedgerWords), C.POINTER(SphLedgerSum), C.POINTER(SphLedgerResult)
         self.ledger_compute = sig("ledger_compute", i32, [vp, C.POINTER(SphParams), lsp, lrp], required=False)
         self.slab_ledger_range = sig("slab_ledger_range", i32, [vp, C.POINTER(SphParams), lsp, lwp], required=False)
@@ -1194,6 +1215,58 @@ class Context:
                                        values.nbytes, planes.ctypes.data if raw and planes.size else None, planes.nbytes if raw else 0))
         return values, planes
 
+    # ---- probe sets on slab contexts (include/sph_slab_probe.h; adaptive_sph_amd/probes.py: sample_group, ProbeSet.sample_rank, ...) ----
+    def slab_probe_range(self, params: SphParams, pp: "SphProbeParams") -> "SphSlabSampleWords":
+        """sph_slab_probe_range: this rank's verdict over its owned particles for pp's channels and volume.  The ranks' words go to
+        probe_fold_words."""
+        w = SphSlabSampleWords()
+        self._check(_slab_probe_lib(self.lib).slab_probe_range(self.handle, C.byref(params) if params is not None else None,
+                                                               C.byref(pp) if pp is not None else None, C.byref(w)))
+        return w
+
+    def slab_probe_layer(self, params: SphParams, set_handle, pp: "SphProbeParams") -> "SphSlabProbeLayerInfo":
+        """sph_slab_probe_layer: scatter this rank's owned particles onto the set's points with pp's EXPLICIT exponents and pack the
+        touched points into the set's compact layer (kept on the device) -> SphSlabProbeLayerInfo."""
+        info = SphSlabProbeLayerInfo()
+        shapes = self.__dict__.setdefault("_probe_layer_shape", {})
+        key = getattr(set_handle, "value", set_handle)
+        shapes.pop(key, None)
+        self._check(_slab_probe_lib(self.lib).slab_probe_layer(self.handle, C.byref(params) if params is not None else None, set_handle,
+                                                               C.byref(pp) if pp is not None else None, C.byref(info)))
+        shapes[key] = (int(pp.n_channels) + 1, int(info.n_entries))
+        return info
+
+    def slab_probe_layer_download(self, set_handle):
+        """sph_slab_probe_layer_download: the layer the last slab_probe_layer call on this set kept -> (uint32[n_entries] ascending point
+        indices, int64[C+1, n_entries]).  The shape is the one that call reported; without such a call the library is asked with no
+        room at all and refuses."""
+        planes, n_entries = self.__dict__.get("_probe_layer_shape", {}).get(getattr(set_handle, "value", set_handle), (1, 0))
+        idx, words = np.empty(n_entries, np.uint32), np.empty((planes, n_entries), np.int64)
+        self._check(_slab_probe_lib(self.lib).slab_probe_layer_download(self.handle, set_handle, idx.ctypes.data if idx.size else None,
+                                                                        words.ctypes.data if words.size else None, idx.size))
+        return idx, words
+
+    def probe_compose(self, set_handle, pp: "SphProbeParams", n_points: int, layers, raw: bool = False):
+        """sph_probe_compose on this context (plain or slab), which owns the set: layers = [(indices, words[C+1, n_entries]) or None]
+        -> (values float32[C+1, n_points], raw int64[C+1, n_points] or None, SphProbeInfo).  pp holds explicit exponents."""
+        ne, pi, pw, _keep = _probe_layer_args(layers)
+        planes = min(max(int(pp.n_channels), 0), SAMPLE_MAX_CHANNELS) + 1 if pp is not None else 1
+        values = np.zeros((planes, int(n_points)), np.float32)
+        words = np.zeros((planes, int(n_points)), np.int64) if raw else None
+        info = SphProbeInfo()
+        self._check(_slab_probe_lib(self.lib).probe_compose(self.handle, set_handle, C.byref(pp) if pp is not None else None, len(layers), ne, pi, pw,
+                                                            values.ctypes.data if values.size else None, values.nbytes,
+                                                            words.ctypes.data if raw and words.size else None, words.nbytes if raw else 0, C.byref(info)))
+        return values, words, info
+
+    def probe_compose_advect(self, set_handle, ap: "SphProbeAdvectParams", layers) -> "SphProbeInfo":
+        """sph_probe_compose_advect: the ranks' 3-plane layers (weight, x, y) summed, then the tracer step of the set's own points."""
+        ne, pi, pw, _keep = _probe_layer_args(layers)
+        info = SphProbeInfo()
+        self._check(_slab_probe_lib(self.lib).probe_compose_advect(self.handle, set_handle, C.byref(ap) if ap is not None else None, len(layers), ne, pi, pw,
+                                                                   C.byref(info)))
+        return info
+
     def grid(self) -> SphGridInfo:
         g = SphGridInfo()
         self._check(self.lib.grid(self.handle, C.byref(g)))
@@ -1575,3 +1648,84 @@ def group_sample_grid(contexts, params: SphParams, sp: "SphSampleParams", raw: b
     for c in contexts:
         c._sample_layer_shape = None   # (the members' layers were scattered again; their bands stayed in the library)
     return values, planes, info
+
+
+# ---- probe sets on slab contexts (include/sph_slab_probe.h) ----------------------------------------------------------------------
+def _slab_probe_lib(lib):
+    if any(getattr(lib, s, None) is None for s in SLAB_PROBE_SYMBOLS):
+        raise SphError(30, f"{lib.path.name} probes no slab contexts (sph_slab_probe.h is implemented by the product library only)")
+    return lib
+
+
+def _probe_layer_args(layers):
+    """The arrays of a compose call: (uint64[k] entry counts, void*[k] indices, void*[k] words, the contiguous arrays the pointers point
+    into -- hold them until the call returns).  layers[i]: (indices, words[planes, n_entries]), or None for a layer without entries."""
+    k = len(layers)
+    ne = (C.c_uint64 * max(1, k))()
+    pi, pw = (C.c_void_p * max(1, k))(), (C.c_void_p * max(1, k))()
+    keep = []
+    for i, l in enumerate(layers):
+        if l is None or np.asarray(l[0]).size == 0:
+            ne[i], pi[i], pw[i] = 0, None, None
+            continue
+        idx, words = np.ascontiguousarray(l[0], np.uint32), np.ascontiguousarray(l[1], np.int64)
+        keep += [idx, words]
+        ne[i], pi[i], pw[i] = idx.size, idx.ctypes.data, words.ctypes.data
+    return ne, pi, pw, keep
+
+
+def probe_fold_words(lib: "SphLibrary", words, pp: "SphProbeParams", msg_bytes: int = 512) -> "SphProbeParams":
+    """sph_probe_fold_words (no device, no context): the ranks' verdicts -> a copy of `pp` whose automatic exponents are those of the
+    whole vector.  Raises SphError(1) with the sentence sph_probe_sample writes when a particle offends (the smallest global id over
+    the ranks) or an exponent is out of range: the same on every rank that folds the same words."""
+    lib = _slab_probe_lib(lib)
+    words = list(words)
+    arr = (SphSlabSampleWords * max(1, len(words)))()
+    for i, w in enumerate(words):
+        arr[i] = w if isinstance(w, SphSlabSampleWords) else SphSlabSampleWords.from_tuple(w)
+    out = SphProbeParams.from_buffer_copy(pp)
+    msg = C.create_string_buffer(max(1, int(msg_bytes)))
+    rc = lib.probe_fold_words(len(words), arr, C.byref(out), msg, int(msg_bytes))
+    if rc != 0:
+        raise SphError(rc, msg.value.decode(errors="replace"))
+    return out
+
+
+def _group_probe_args(contexts, set_handles, what):
+    contexts = list(contexts)
+    if not contexts:
+        raise SphError(1, f"{what}: n < 1 (no contexts)")
+    set_handles = list(set_handles)
+    if len(set_handles) != len(contexts):
+        raise ValueError("one probe set per context")
+    k = len(contexts)
+    return contexts, _slab_probe_lib(contexts[0].lib), (C.c_void_p * k)(*[c.handle for c in contexts]), (C.c_void_p * k)(*set_handles)
+
+
+def group_probe_sample(contexts, params: SphParams, set_handles, pp: "SphProbeParams", n_points: int, raw: bool = False):
+    """sph_group_probe_sample: the k slab contexts of this process (the group sph_group_step steps) and one replica of the point set per
+    member -> (values float32[C+1, n_points], raw int64 or None, SphProbeInfo) as sph_probe_sample gives them for one context that
+    holds the same particles."""
+    contexts, lib, handles, sets = _group_probe_args(contexts, set_handles, "sph_group_probe_sample")
+    planes = min(max(int(pp.n_channels), 0), SAMPLE_MAX_CHANNELS) + 1 if pp is not None else 1
+    values = np.zeros((planes, int(n_points)), np.float32)
+    words = np.zeros((planes, int(n_points)), np.int64) if raw else None
+    info = SphProbeInfo()
+    rc = lib.group_probe_sample(handles, len(contexts), C.byref(params) if params is not None else None, sets, C.byref(pp) if pp is not None else None,
+                                values.ctypes.data if values.size else None, values.nbytes, words.ctypes.data if raw and words.size else None,
+                                words.nbytes if raw else 0, C.byref(info))
+    if rc != 0:   # (whichever member refused, the library leaves the sentence in member 0's last error)
+        raise SphError(rc, lib.last_error(contexts[0].handle).decode(errors="replace"))
+    return values, words, info
+
+
+def group_probe_advect(contexts, params: SphParams, set_handles, ap: "SphProbeAdvectParams") -> "SphProbeInfo":
+    """sph_group_probe_advect: one tracer step of every member's replica from the group's summed planes; afterwards every member's set
+    holds the same points."""
+    contexts, lib, handles, sets = _group_probe_args(contexts, set_handles, "sph_group_probe_advect")
+    info = SphProbeInfo()
+    rc = lib.group_probe_advect(handles, len(contexts), C.byref(params) if params is not None else None, sets, C.byref(ap) if ap is not None else None,
+                                C.byref(info))
+    if rc != 0:
+        raise SphError(rc, lib.last_error(contexts[0].handle).decode(errors="replace"))
+    return info

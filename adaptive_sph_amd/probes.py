@@ -9,6 +9,10 @@ gets that sample's words.
 
 Which state: density and pressure (and the "density" volume) are a step's outputs -- sample right behind the step, before its
 adaptivity; velocity under volume="rest" is valid at any time, which is what `advect` defaults to.
+
+Slab contexts (include/sph_slab_probe.h): every rank holds a replica of the set -- the same points in the same order -- and
+`sample_group` / `advect_group` (the group of one process) or `ProbeSet.sample_rank` / `ProbeSet.advect_rank` (one process per rank)
+give the words of one context that holds the same particles, bit for bit.
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import ffi
+from .distributed import compose_on_root
 from .sampling import expand_channels
 
 
@@ -69,6 +74,47 @@ def probe_params(channels: Sequence[str], volume="density", normalize=False, min
         e = None if exponents is None else exponents[k]
         pp.channels[k] = ffi.SphSampleChannel(ffi.FIELDS[fld][0], comp, ffi.SAMPLE_AUTO_EXPONENT if e is None else int(e))
     return pp
+
+
+def _values_of(names, values, words, info) -> ProbeValues:
+    keys = ["weight"] + list(names)
+    return ProbeValues(list(names), {k: values[i + 1] for i, k in enumerate(names)}, values[0],
+                       {k: int(info.exponents[i]) for i, k in enumerate(names)}, int(info.n_touching), int(info.n_pairs),
+                       int(info.n_touched_points), {k: words[i] for i, k in enumerate(keys)} if words is not None else None, info)
+
+
+def _advect_params(dt, volume="rest", min_weight=0.5, exponents=None) -> "ffi.SphProbeAdvectParams":
+    ap = ffi.SphProbeAdvectParams()
+    ap.dt, ap.min_weight = float(dt), float(min_weight)
+    ap.volume = ffi.SAMPLE_VOLUMES[volume] if isinstance(volume, str) else int(volume)
+    ex = (None, None) if exponents is None else exponents
+    ap.exponent_x, ap.exponent_y = (ffi.SAMPLE_AUTO_EXPONENT if e is None else int(e) for e in ex)
+    return ap
+
+
+def _velocity_params(ap) -> "ffi.SphProbeParams":
+    """The sph_probe_params a tracer step folds: the two velocity channels with ap's exponents, as sph_probe_advect builds them."""
+    pp = ffi.SphProbeParams()
+    pp.volume, pp.min_weight, pp.n_channels = ap.volume, ap.min_weight, 2
+    vel = ffi.FIELDS["velocity"][0]
+    pp.channels[0] = ffi.SphSampleChannel(vel, 0, ap.exponent_x)
+    pp.channels[1] = ffi.SphSampleChannel(vel, 1, ap.exponent_y)
+    return pp
+
+
+class _naming_the_slab_forms:
+    """A slab context refuses sample / advect (status 30): the error then names the calls that serve it, around the library's sentence."""
+
+    def __init__(self, forms):
+        self.forms = forms
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, e, tb):
+        if isinstance(e, ffi.SphError) and e.status == 30 and "slab contexts" in str(e):
+            raise ffi.SphError(30, f"{e.message} [on slab contexts: probes.{self.forms} (include/sph_slab_probe.h)]") from None
+        return False
 
 
 class ProbeSet:
@@ -135,28 +181,108 @@ class ProbeSet:
         values = np.zeros((planes, n), np.float32)
         words = np.zeros((planes, n), np.int64) if raw else None
         info = ffi.SphProbeInfo()
-        self.ctx._check(self.lib.probe_sample(self.ctx.handle, C.byref(p) if p is not None else None, self.handle, C.byref(pp) if pp is not None else None,
-                                              values.ctypes.data if values.size else None, values.nbytes,
-                                              words.ctypes.data if raw and words.size else None, words.nbytes if raw else 0, C.byref(info)))
+        with _naming_the_slab_forms("sample_group / ProbeSet.sample_rank"):
+            self.ctx._check(self.lib.probe_sample(self.ctx.handle, C.byref(p) if p is not None else None, self.handle, C.byref(pp) if pp is not None else None,
+                                                  values.ctypes.data if values.size else None, values.nbytes,
+                                                  words.ctypes.data if raw and words.size else None, words.nbytes if raw else 0, C.byref(info)))
         self.info = info
-        keys = ["weight"] + list(names)
-        return ProbeValues(list(names), {k: values[i + 1] for i, k in enumerate(names)}, values[0],
-                           {k: int(info.exponents[i]) for i, k in enumerate(names)}, int(info.n_touching), int(info.n_pairs),
-                           int(info.n_touched_points), {k: words[i] for i, k in enumerate(keys)} if raw else None, info)
+        return _values_of(names, values, words if raw else None, info)
 
     def advect(self, P, dt: float, volume="rest", min_weight=0.5, exponents=None) -> "ffi.SphProbeInfo":
         """sph_probe_advect: one explicit Euler step of every point with the interpolated velocity; a point whose weight is below
         `min_weight` stays where it is.  -> the info struct (n_moved, n_stalled, the exponents of x and y)."""
         p = P.to_ffi() if hasattr(P, "to_ffi") else P
-        ap = ffi.SphProbeAdvectParams()
-        ap.dt, ap.min_weight = float(dt), float(min_weight)
-        ap.volume = ffi.SAMPLE_VOLUMES[volume] if isinstance(volume, str) else int(volume)
-        ex = (None, None) if exponents is None else exponents
-        ap.exponent_x, ap.exponent_y = (ffi.SAMPLE_AUTO_EXPONENT if e is None else int(e) for e in ex)
+        ap = _advect_params(dt, volume, min_weight, exponents)
         info = ffi.SphProbeInfo()
-        self.ctx._check(self.lib.probe_advect(self.ctx.handle, C.byref(p) if p is not None else None, self.handle, C.byref(ap), C.byref(info)))
+        with _naming_the_slab_forms("advect_group / ProbeSet.advect_rank"):
+            self.ctx._check(self.lib.probe_advect(self.ctx.handle, C.byref(p) if p is not None else None, self.handle, C.byref(ap), C.byref(info)))
         self.info = info
         return info
+
+    # ---- one process per rank (include/sph_slab_probe.h): every rank calls these behind the same step, on its replica of the set ----
+    def _layer(self, p, pp):
+        """This rank's compact layer for pp's explicit exponents -> (indices, words, (n_touching, n_pairs))"""
+        info = self.ctx.slab_probe_layer(p, self.handle, pp)
+        n = int(info.n_entries)
+        layer = self.ctx.slab_probe_layer_download(self.handle) if n else (None, None)
+        return layer[0], layer[1], (int(info.n_touching), int(info.n_pairs))
+
+    def sample_rank(self, P, channels: Sequence[str], volume="density", normalize=False, min_weight=0.5, fill=float("nan"), raw=False,
+                    exponents=None, root: int = 0) -> Optional[ProbeValues]:
+        """`sample` with ONE PROCESS PER RANK.  The ranks' verdict words are all-gathered through the launcher's process group and folded
+        on every rank -- every rank takes the same exponents or raises the same refusal, naming the smallest offending global id --,
+        every rank packs its compact layer and sends it to `root` (distributed.compose_on_root), `root` adds the layers on its own
+        replica.  Returns the values on `root`, None elsewhere; a failure on the root is re-raised on every rank."""
+        import torch.distributed as dist
+        names = expand_channels(channels)
+        pp = probe_params(names, volume, normalize, min_weight, fill, exponents)
+        p = P.to_ffi() if hasattr(P, "to_ffi") else P
+        words = [None] * dist.get_world_size()
+        dist.all_gather_object(words, self.ctx.slab_probe_range(p, pp).as_tuple())
+        pp = ffi.probe_fold_words(self.ctx.lib, words, pp)   # (raises the same SphError on every rank)
+        idx, lay, counts = self._layer(p, pp)
+
+        def compose(parts):
+            values, raw_words, info = self.ctx.probe_compose(self.handle, pp, len(self), [None if i is None else (i, w) for i, w, _ in parts], raw=raw)
+            info.n_touching, info.n_pairs = sum(c[0] for _, _, c in parts), sum(c[1] for _, _, c in parts)
+            self.info = info
+            return _values_of(names, values, raw_words if raw else None, info)
+
+        return compose_on_root((idx, lay, counts), compose, "probe sample", root)
+
+    def advect_rank(self, P, dt: float, volume="rest", min_weight=0.5, exponents=None) -> "ffi.SphProbeInfo":
+        """`advect` with ONE PROCESS PER RANK: the words all-gathered and folded, every rank's 3-plane layer (weight, x, y) all-gathered,
+        every rank adds all layers and moves its own replica (sph_probe_compose_advect).  The move is a per-point function of integer
+        sums: afterwards every rank's set holds the same points bit for bit.  -> the info struct on every rank."""
+        import torch.distributed as dist
+        p = P.to_ffi() if hasattr(P, "to_ffi") else P
+        ap = _advect_params(dt, volume, min_weight, exponents)
+        pp = _velocity_params(ap)
+        world = dist.get_world_size()
+        words = [None] * world
+        dist.all_gather_object(words, self.ctx.slab_probe_range(p, pp).as_tuple())
+        pp = ffi.probe_fold_words(self.ctx.lib, words, pp)
+        ap.exponent_x, ap.exponent_y = int(pp.channels[0].exponent), int(pp.channels[1].exponent)
+        parts = [None] * world
+        dist.all_gather_object(parts, self._layer(p, pp))
+        info = self.ctx.probe_compose_advect(self.handle, ap, [None if i is None else (i, w) for i, w, _ in parts])
+        info.n_touching, info.n_pairs = sum(c[0] for _, _, c in parts), sum(c[1] for _, _, c in parts)
+        self.info = info
+        return info
+
+
+# ---- the slab group of ONE process (the contexts ffi.group_step steps); sets[i]: a replica on contexts[i] ----
+def _group_sets(contexts, sets):
+    contexts, sets = list(contexts), list(sets)
+    if len(contexts) != len(sets):
+        raise ValueError("one probe set per context")
+    return contexts, sets, [s.handle for s in sets]
+
+
+def sample_group(contexts, sets, P, channels: Sequence[str], volume="density", normalize=False, min_weight=0.5, fill=float("nan"), raw=False,
+                 exponents=None) -> ProbeValues:
+    """`ProbeSet.sample` for a slab group: bit for bit what one context that holds the same particles returns.  The members agree on the
+    exponents and the preconditions through one set of words on the device, every member scatters the particles it owns straight into
+    member 0's planes (sph_group_probe_sample); only the values cross the bus."""
+    contexts, sets, handles = _group_sets(contexts, sets)
+    names = expand_channels(channels)
+    pp = probe_params(names, volume, normalize, min_weight, fill, exponents)
+    p = P.to_ffi() if hasattr(P, "to_ffi") else P
+    values, words, info = ffi.group_probe_sample(contexts, p, handles, pp, len(sets[0]) if sets else 0, raw=raw)
+    for s in sets:
+        s.info = info
+    return _values_of(names, values, words, info)
+
+
+def advect_group(contexts, sets, P, dt: float, volume="rest", min_weight=0.5, exponents=None) -> "ffi.SphProbeInfo":
+    """`ProbeSet.advect` for a slab group (sph_group_probe_advect): every member's replica moves from the group's summed planes;
+    afterwards all of them hold the same points."""
+    contexts, sets, handles = _group_sets(contexts, sets)
+    p = P.to_ffi() if hasattr(P, "to_ffi") else P
+    info = ffi.group_probe_advect(contexts, p, handles, _advect_params(dt, volume, min_weight, exponents))
+    for s in sets:
+        s.info = info
+    return info
 
 
 def line(p0, p1, count: int) -> np.ndarray:

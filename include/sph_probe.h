@@ -48,7 +48,8 @@
  *
  * Status codes are those of sph_sample.h: SPH_ERR_INVALID_ARGUMENT (arguments, points, a handle that is not a live set of the context,
  * a short buffer, a precondition), SPH_ERR_POISONED, SPH_ERR_UNSUPPORTED (slab contexts: one rank holds a slab of the particles; the
- * raw sums of disjoint particle sets add exactly, so a later slab form composes the ranks' raw words), SPH_ERR_DEVICE.  The calls read
+ * raw sums of disjoint particle sets add exactly, so sph_slab_probe.h composes the ranks' raw words: sph_group_probe_sample / _advect
+ * for the group of one process, the range, layer and compose calls for one process per rank), SPH_ERR_DEVICE.  The calls read
  * the simulation state and change none of it (no row of the carry table is involved); every launch runs on the context's stream.
  */
 #ifndef SPH_PROBE_H
