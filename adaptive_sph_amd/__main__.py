@@ -11,6 +11,7 @@ partner decisions on the host (adaptivity.py), the particle data on the device; 
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 import time
 from typing import Optional, Sequence
@@ -76,6 +77,16 @@ def build_parser() -> argparse.ArgumentParser:
                      help="one row per N-th step: step, time, dt, then name_or_index:field for every point (the weight first); taken between the "
                           "step and its adaptivity, like --ledger and --grid-vtk")
     run.add_argument("--probe-every", type=int, default=1, help="a row of --probe-csv every N-th step")
+    # not in the reference either: the load on every boundary element, reduced on the device (wall_loads.py)
+    run.add_argument("--wall-loads", default=None, metavar="FILE.csv",
+                     help="write one row per N-th step: per boundary element k (the planes of the box: left, right, floor, ceiling; or the one "
+                          "polygon) fx_k, fy_k, torque_k, normal_k, n_wet_k, peak_p_k, peak_id_k -- the force the pressure solve exchanges with "
+                          "the wall; taken between the step and its adaptivity, like --ledger")
+    run.add_argument("--wall-load-every", type=int, default=1, help="a row of --wall-loads every N-th step")
+    run.add_argument("--wall-load-profile", default=None, metavar="DIR",
+                     help="write DIR/wall-load-NNNNN.csv at the cadence of --vtk-every: the line pressure along every plane of the box in "
+                          "--wall-load-bins bins over the plane's extent inside the box")
+    run.add_argument("--wall-load-bins", type=int, default=64, metavar="B", help="bins per plane of --wall-load-profile (1..4096)")
     run.add_argument("--tracers-every", type=int, default=None, metavar="K",
                      help="seed a tracer at the initial position of every K-th particle and move it after each step with that step's dt and the "
                           "interpolated velocity (explicit Euler; behind the step's adaptivity, rest volume); needs --tracer-vtk")
@@ -136,6 +147,23 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         ledger_file = open(args.ledger, "w", newline="")
         ledger_csv = csv.writer(ledger_file)
         ledger_csv.writerow(ledger_mod.CSV_COLUMNS)
+    wall_file, wall_profile_dir = None, getattr(args, "wall_load_profile", None)
+    if getattr(args, "wall_loads", None) or wall_profile_dir:
+        import csv
+        from . import wall_loads as wall_mod
+        from .scene import boundary_planes
+        wall_planes = boundary_planes(scene.boundary, params.init_boundary_handler)
+        if getattr(args, "wall_loads", None):
+            wall_file = open(args.wall_loads, "w", newline="")
+            wall_csv = csv.writer(wall_file)
+            wall_csv.writerow(wall_mod.csv_columns(1 if hasattr(wall_planes, "points") else len(wall_planes)))
+        if wall_profile_dir:
+            if hasattr(wall_planes, "points"):
+                raise SystemExit("--wall-load-profile: a profile runs along a plane; this boundary is one polygon")
+            if not 1 <= args.wall_load_bins <= ffi.WALL_LOAD_MAX_BINS:
+                raise SystemExit(f"--wall-load-bins: 1..{ffi.WALL_LOAD_MAX_BINS}")
+            os.makedirs(wall_profile_dir, exist_ok=True)
+            wall_ranges = wall_mod.plane_ranges(wall_planes, scene.boundary)
     if bool(getattr(args, "probes", None)) != bool(getattr(args, "probe_csv", None)):
         raise SystemExit("--probes and --probe-csv go together")
     if (getattr(args, "tracers_every", None) is not None) != bool(getattr(args, "tracer_vtk", None)):
@@ -171,6 +199,11 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         led = None
         if ledger_file is not None and steps % max(args.ledger_every, 1) == 0:
             led = ledger_mod.ledger(sim.ctx, p)               # (the same place, for the same reason)
+        if wall_file is not None and steps % max(args.wall_load_every, 1) == 0:
+            wall_csv.writerow(wall_mod.csv_row(steps, sim.time, dt, wall_mod.wall_load(sim.ctx, p)))   # (the same place too)
+        if wall_profile_dir and snapshot:
+            with open(os.path.join(wall_profile_dir, f"wall-load-{steps:05d}.csv"), "w", newline="") as fh:
+                csv.writer(fh).writerows(wall_mod.profile_rows(wall_mod.wall_load(sim.ctx, p, args.wall_load_bins, wall_ranges)))
         if gauges is not None and steps % max(args.probe_every, 1) == 0:
             # (between the step and its adaptivity too)
             values = gauges.sample(p, probe_spec.fields, volume=probe_spec.volume)
@@ -194,6 +227,8 @@ def run(args, lib: Optional[ffi.SphLibrary] = None, out=sys.stdout) -> int:
         grid_vtk.close()
     if ledger_file is not None:
         ledger_file.close()
+    if wall_file is not None:
+        wall_file.close()
     if probe_file is not None:
         probe_file.close()
         gauges.close()

@@ -648,7 +648,7 @@ extern "C" void sph_destroy(sph_ctx* c)
                      &c->n_tiles, &c->red_partials, &c->scratch, &c->split_patterns, &c->akey[0], &c->akey[1], &c->aval[0], &c->aval[1], &c->acxy, &c->acell_start, &c->pm2,
                      &c->atile_raw, &c->atile_h, &c->inc_head, &c->inc_next, &c->inc_bsum, &c->inc_movers, &c->inc_local, &c->cand_red, &c->rnd_rec, &c->rnd_keys, &c->rnd_out, &c->rnd_max, &c->rnd_prev, &c->rnd_words, &c->rnd_layer.words, &c->rnd_layer.band, &c->rnd_layer.stage,
                      &c->smp_planes, &c->smp_out, &c->smp_red, &c->smp_layer.words, &c->smp_layer.band, &c->smp_layer.stage,
-                     &c->led_part, &c->led_out, &c->prb_stat};
+                     &c->led_part, &c->led_out, &c->prb_stat, &c->wl_part, &c->wl_out, &c->wl_profile};
     probe_sets_release(c);
     for (auto b : all) b->release();
     for (DevBuf* b : c->export_bufs()) b->release();

@@ -341,6 +341,9 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     // the state ledger (sph_ledger.hip): one partial per block and quantity of a pass, and the words / sums its last launch folds them
     // into -- allocated on first use, kept across calls, freed by sph_destroy
     DevBuf led_part, led_out;
+    // wall loads (sph_wall_load.hip): the same two, and the int64 words of the profile -- allocated on first use, kept across calls, freed by
+    // sph_destroy
+    DevBuf wl_part, wl_out, wl_profile;
     // probe sets (sph_probe.hip): the live sets of this context -- a handle that is not in the list is refused without being read --
     // and the counts of a call (the planes are smp_planes / smp_out: one call at a time runs on the stream); sph_destroy frees what
     // sph_probe_set_destroy has not

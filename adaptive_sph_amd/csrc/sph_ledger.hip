@@ -26,6 +26,7 @@
 #include <cstring>
 #include <vector>
 
+#include "sph_fixed_sums.hpp"
 #include "sph_ledger.h"
 #include "sph_slab_layers.hpp"
 
@@ -68,17 +69,6 @@ __host__ __device__ inline unsigned long long word_fold(int q, unsigned long lon
     return op == OP_ADD ? a + b : op == OP_MIN ? (a < b ? a : b) : (a > b ? a : b);
 }
 
-struct U128 {
-    unsigned long long lo;
-    long long hi;
-};
-__host__ __device__ inline void add128(U128& a, unsigned long long lo, long long hi)
-{
-    const unsigned long long s = a.lo + lo;
-    a.hi += hi + (long long)(s < lo);
-    a.lo = s;
-}
-
 // the state a pass reads (device order)
 struct LedgerIn {
     const float4* pm;      // {x, y, mass, h}
@@ -116,29 +106,6 @@ __device__ __forceinline__ void ledger_terms(uint32_t what, float x, float y, fl
     } else {
         t[7] = t[8] = 0.0;
     }
-}
-
-__device__ __forceinline__ uint32_t ord_f32(float a)
-{
-    const uint32_t b = __float_as_uint(a);
-    return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
-}
-__device__ __forceinline__ void key_max(unsigned long long& w, float a, uint32_t id)
-{
-    const unsigned long long k = ((unsigned long long)ord_f32(a) << 32) | (unsigned long long)(0xffffffffu - id);
-    w = k > w ? k : w;
-}
-__device__ __forceinline__ void key_min(unsigned long long& w, float a, uint32_t id)
-{
-    const unsigned long long k = ((unsigned long long)ord_f32(a) << 32) | (unsigned long long)id;
-    w = k < w ? k : w;
-}
-__device__ __forceinline__ bool finite_f32(float a) { return fabsf(a) < INFINITY; }
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 // n: the slots; part: kWords rows of gridDim.x partials
@@ -242,16 +209,6 @@ __global__ __launch_bounds__(64) void k_ledger_fold_words(uint32_t nb, const uns
     for (uint32_t b = threadIdx.x; b < nb; b += 64) v = word_fold(q, v, part[(size_t)q * nb + b]);
     for (int o = 32; o > 0; o >>= 1) v = word_fold(q, v, shfl_xor_u64(v, o));
     if (threadIdx.x == 0) out[q] = v;
-}
-
-__device__ __forceinline__ U128 wave_add128(U128 v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long lo = shfl_xor_u64(v.lo, o);
-        const long long hi = (long long)shfl_xor_u64((unsigned long long)v.hi, o);
-        add128(v, lo, hi);
-    }
-    return v;
 }
 
 // n: the slots; part: kSums rows of gridDim.x partials.  Checks nothing: the range pass and its verdict come first
@@ -360,16 +317,6 @@ void format_offender(char* buf, size_t bytes, unsigned long long first_bad, cons
     }
 }
 
-// e with m < 2^e <= 2 m for m > 0 (frexp: m = f 2^e, 0.5 <= f < 1), 0 for m = 0
-int exponent_of_bits(uint64_t bits)
-{
-    const double m = __builtin_bit_cast(double, bits);
-    if (!(m > 0.0)) return 0;
-    int e = 0;
-    (void)std::frexp(m, &e);
-    return e;
-}
-
 void fold_only(int n, const sph_ledger_words* words, sph_ledger_words* w)
 {
     uint64_t* f = (uint64_t*)w;
@@ -407,28 +354,6 @@ int fold_words(int n, const sph_ledger_words* words, sph_ledger_spec* spec_io, s
     }
     if (msg && msg_bytes) msg[0] = 0;
     return SPH_OK;
-}
-
-// the 128-bit integer -> the nearest f64, ties to even, times 2^shift
-double resolve128(const sph_ledger_sum& q, int shift)
-{
-    const bool neg = q.hi < 0;
-    unsigned __int128 mag = ((unsigned __int128)(uint64_t)q.hi << 64) | q.lo;
-    if (neg) mag = (unsigned __int128)0 - mag;
-    if (mag == 0) return 0.0;
-    int top = 127;
-    while (!((mag >> top) & 1)) top--;
-    double v;
-    if (top <= 52) v = (double)(uint64_t)mag;
-    else {
-        const int sh = top - 52;
-        uint64_t mant = (uint64_t)(mag >> sh);                                   // 53 bits
-        const unsigned __int128 rem = mag & (((unsigned __int128)1 << sh) - 1), half = (unsigned __int128)1 << (sh - 1);
-        if (rem > half || (rem == half && (mant & 1u))) mant++;                  // (2^53 after the carry is still exact)
-        v = std::ldexp((double)mant, sh);
-    }
-    v = std::ldexp(v, shift);
-    return neg ? -v : v;
 }
 
 // the ranks' words and sums -> the result; spec holds explicit exponents

@@ -365,6 +365,39 @@ class SphLedgerResult(C.Structure):
                 ("raw", SphLedgerSum * LEDGER_N_SUMS), ("sum", C.c_double * LEDGER_N_SUMS), ("extreme", SphLedgerExtreme * LEDGER_N_EXTREMES)]
 
 
+# include/sph_wall_load.h: force, torque, normal force and peak pressure per boundary element, a binned profile along a plane (product only)
+WALL_LOAD_SYMBOLS = ["wall_load_compute"]
+WALL_LOAD_MAX_ELEMENTS, WALL_LOAD_N_SUMS, WALL_LOAD_MAX_BINS, WALL_LOAD_BIN_SHIFT = 8, 4, 4096, 40
+WALL_LOAD_MAX_BINNED_ENTRIES = 1 << 23
+WALL_LOAD_SUMS = ["force_x", "force_y", "torque", "normal"]
+
+
+class SphWallLoadSpec(C.Structure):
+    """sph_wall_load_spec: the exponent of every (element, sum) (LEDGER_AUTO_EXPONENT: taken from the range pass) and the profile's bins."""
+    _fields_ = [("flags", C.c_uint32), ("bins", C.c_int32), ("exponent", (C.c_int32 * WALL_LOAD_N_SUMS) * WALL_LOAD_MAX_ELEMENTS),
+                ("n_bins", C.c_int32 * WALL_LOAD_MAX_ELEMENTS), ("s_lo", C.c_float * WALL_LOAD_MAX_ELEMENTS), ("s_hi", C.c_float * WALL_LOAD_MAX_ELEMENTS)]
+
+
+class SphWallLoadElementWords(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_wet", C.c_uint64), ("n_unbinned", C.c_uint64), ("max_bits", C.c_uint64 * WALL_LOAD_N_SUMS),
+                ("max_pressure", C.c_uint64)]
+
+
+class SphWallLoadWords(C.Structure):
+    """sph_wall_load_words: what the range pass says (the layout a fold over slab ranks would take)."""
+    _fields_ = [("first_bad", C.c_uint64), ("n", C.c_uint64), ("element", SphWallLoadElementWords * WALL_LOAD_MAX_ELEMENTS)]
+
+
+class SphWallLoadElement(C.Structure):
+    _fields_ = [("exponent", C.c_int32 * WALL_LOAD_N_SUMS), ("raw", SphLedgerSum * WALL_LOAD_N_SUMS), ("sum", C.c_double * WALL_LOAD_N_SUMS),
+                ("n_entries", C.c_uint64), ("n_wet", C.c_uint64), ("n_unbinned", C.c_uint64), ("max_pressure", SphLedgerExtreme),
+                ("inv_ds", C.c_float), ("n_bins", C.c_int32)]
+
+
+class SphWallLoadResult(C.Structure):
+    _fields_ = [("n_elements", C.c_uint32), ("bins", C.c_int32), ("n", C.c_uint64), ("element", SphWallLoadElement * WALL_LOAD_MAX_ELEMENTS)]
+
+
 ABI_SYMBOLS = [
     "create", "destroy", "upload", "upload_field", "download", "download_neighbors", "num_particles", "time",
     "set_time", "step", "classify", "share_particles", "merge_particles", "set_split_patterns", "split_particles", "host_find_partners", "last_error", "grid", "set_boundary_polygon", "set_math_policy", "get_math_policy", "apply_edits", "profile_enable", "profile_reset", "profile_get", "profile_event_overhead", "profile_dispatch_bracket", "profile_copy_bandwidth", "profile_list_forms", "set_sweep_variant",
@@ -591,6 +624,8 @@ class SphLibrary:
         self.ledger_fold_words = sig("ledger_fold_words", i32, [i32, lwp, lsp, lwp, C.c_char_p, u64], required=False)
         self.ledger_compose = sig("ledger_compose", i32, [i32, lwp, lsu, lsp, lrp], required=False)
         self.group_ledger = sig("group_ledger", i32, [C.POINTER(vp), i32, C.POINTER(SphParams), lsp, lrp], required=False)
+        self.wall_load_compute = sig("wall_load_compute", i32, [vp, C.POINTER(SphParams), C.POINTER(SphWallLoadSpec), C.POINTER(SphWallLoadResult), vp],
+                                     required=False)
 
 
 _PRODUCT = None
