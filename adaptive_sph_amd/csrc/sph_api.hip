@@ -452,7 +452,7 @@ static int alloc_particle_buffers(sph_ctx* c)
     HIPCHK(c, c->nl.ensure(sweep_list_bytes((uint32_t)n)));
     HIPCHK(c, c->nl_ok.ensure(n));
     HIPCHK(c, c->red_partials.ensure(sizeof(SolverPartial) * (size_t)solver_reduce_blocks((uint32_t)n)));
-    HIPCHK(c, c->hdr_ahead_partials.ensure(sizeof(HeaderOut) * (((size_t)n + 255) / 256)));   // one per 256-thread block of k_solver_tail (not a sweep block)
+    HIPCHK(c, c->hdr_ahead_partials.ensure(sizeof(HeaderOut) * (size_t)solver_tail_partials((uint32_t)n, c->opt.boundary_chains)));   // one per workgroup of k_solver_tail (not a sweep block)
     return SPH_OK;
 }
 
@@ -498,6 +498,7 @@ Options options_from_env()
     o.ahead_build = num("SPH_AHEAD_BUILD", 1) != 0 ? 1 : 0;
     o.inc_sort = num("SPH_INC_SORT", 1);
     o.boundary_fused = num("SPH_BOUNDARY_FUSED", 1) != 0 ? 1 : 0;
+    o.boundary_chains = num("SPH_BOUNDARY_CHAINS", 1) != 0 ? 1 : 0;
     o.fuse_records = num("SPH_FUSE_RECORDS", 1) != 0 ? 1 : 0;
     o.level_move_always = num("SPH_LEVEL_MOVE_ALWAYS", 0) != 0 ? 1 : 0;
     o.slab_paced = num("SPH_SLAB_PACED", 1) != 0 ? 1 : 0;
@@ -512,7 +513,7 @@ Options options_from_env()
     // libsph_hip.so would otherwise run the defaults in every row and report nothing)
     static const char* const lab_only[] = {"SPH_PACED", "SPH_PACE_LEAD", "SPH_PACE_PRED", "SPH_CHAIN", "SPH_ACCEL_GENERIC", "SPH_JACOBI_GENERIC", "SPH_SOURCE_GENERIC",
                                            "SPH_SLAB_GENERAL", "SPH_SLAB_LEVEL_PLAIN", "SPH_LEVEL_SERIAL", "SPH_LEVEL_BATCH8", "SPH_LEVEL_QUEUE", "SPH_OFFSET_LISTS",
-                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_BOUNDARY_FUSED", "SPH_FUSE_RECORDS", "SPH_LEVEL_MOVE_ALWAYS", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
+                                           "SPH_NO_FUSE", "SPH_SIDE_STREAM_NORMAL", "SPH_TILE", "SPH_AHEAD_BUILD", "SPH_INC_SORT", "SPH_BOUNDARY_FUSED", "SPH_BOUNDARY_CHAINS", "SPH_FUSE_RECORDS", "SPH_LEVEL_MOVE_ALWAYS", "SPH_SLAB_PACED", "SPH_SLAB_RECORDS",
                                            "SPH_SIDE_CUS", "SPH_MAIN_EXCLUDE", "SPH_IPC_FUSE_MAX_BYTES", "SPH_IPC_COPY_MIN_BYTES"};
     static bool warned = false;
     if (!warned)

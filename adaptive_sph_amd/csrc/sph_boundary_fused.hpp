@@ -50,3 +50,19 @@ SPH_HD void header_merge(HeaderOut& o, const HeaderOut& q)
 #define INC_CELLS (1 << INC_CELLS_LOG2)
 SPH_HD uint32_t inc_cell_first(const uint32_t* local, const uint32_t* bpre, uint32_t c) { return local[c] + bpre[c >> INC_CELLS_LOG2]; }
 SPH_HD uint32_t inc_count_blocks(uint32_t ncells) { return (ncells + (uint32_t)INC_CELLS - 1u) >> INC_CELLS_LOG2; }
+
+// ---- a particle's rank among the stayers of its new cell (k_inc_place_reorder) ------------------
+// The slot of particle i = first slot of its new cell + the stayers (flag byte 0) of that cell in front of it + the listed movers in
+// front of it.  The stayers in front of it are flag bytes [b, e) of the CURRENT order:
+//   a stayer: those of its own cell in front of it -- b = the cell's start, e = i;
+//   a mover:  all stayers of the cell it enters, old range [b, eb), if it comes from behind that range, none if from in front of it.
+SPH_HD uint32_t inc_mover_range_end(uint32_t i, uint32_t b, uint32_t eb) { return i >= eb ? eb : b; }
+// A stayer's range ends at itself and the particles of a cell are consecutive, so the part of [b, i) that lies inside the particle's
+// wave -- lane l holds particle w0 + l, the particle is lane i - w0 -- is read off the wave's ballot of "is a stayer": the lanes
+// [max(b, w0) - w0, i - w0) count.  Only a cell that starts in front of the wave leaves a part outside, the bytes [b, w0), for a loop.
+SPH_HD uint64_t inc_rank_ballot_lanes(uint32_t w0, uint32_t b, uint32_t i)
+{
+    const uint32_t lo = b > w0 ? b - w0 : 0u, hi = i - w0;   // (w0 <= i < w0 + 64, b <= i)
+    return ((1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+}
+SPH_HD uint32_t inc_rank_outside_end(uint32_t w0, uint32_t b) { return b < w0 ? w0 : b; }   // the loop's range is [b, this): empty unless b < w0

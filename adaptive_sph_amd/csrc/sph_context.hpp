@@ -78,7 +78,8 @@ struct Options {
     int ahead_build = 1;        // SPH_AHEAD_BUILD=0        one context: never queue the next step's cell sort behind the integrating tail
     int inc_sort = 1;           // SPH_INC_SORT=0 | k       the cell sort queued ahead is always the radix sort (never the incremental merge); k > 1: the merge up to n / k movers (default n / 3: at 4M the merge still beats the radix sort with a third of the particles changing cell)
     int boundary_fused = 1;     // SPH_BOUNDARY_FUSED=0     the merge queued ahead in five launches (tail, k_header_ahead, count, k_inc_scan, place) instead of three (tail, count with the header reduction, place with the block sums' prefix)
-    int fuse_records = 1;       // SPH_FUSE_RECORDS=0       the fused a_ii / force sweep always through OpFuse (four gathers per neighbour); no record out of the place launch
+    int boundary_chains = 1;    // SPH_BOUNDARY_CHAINS=0    the solve's tail one particle per lane with its loads one behind the other (k_solver_tail_serial) instead of the tiled form (k_solver_tail<TAIL, U>); the place launch counts a stayer's rank byte by byte instead of from the wave's ballot
+    int fuse_records = 1;       // SPH_FUSE_RECORDS=0      the fused a_ii / force sweep always through OpFuse (four gathers per neighbour); no record out of the place launch
     int level_move_always = 0;  // SPH_LEVEL_MOVE_ALWAYS=1  every reorder moves the level fields, also while they hold the upload's constants (sph_ctx::lvl_pristine)
     int slab_paced = 1;         // SPH_SLAB_PACED=0         slabs: predicted queue instead of pacing
     int slab_records = 1;       // SPH_SLAB_RECORDS=0       slabs: sweep A through the generic form (p / rho^2 as a field of its own)

@@ -68,11 +68,12 @@ __device__ __forceinline__ void inc_register(const IncClassifyP& q, uint32_t i, 
     }
 }
 // ... of particle i at (x, y), an element of the array that is sorted by q.cxy_cur
-__device__ __forceinline__ void inc_classify_particle(const IncClassifyP& q, uint32_t i, float x, float y)
+__device__ __forceinline__ void inc_classify_particle(const IncClassifyP& q, uint32_t i, float x, float y, uint32_t cxy /* q.cxy_cur[i], loaded by the caller */)
 {
     const uint32_t k = cell_key_clamped(q.nxt, x, y);
-    inc_register(q, i, k, k != inc_key_of_cur_cell(q.cur, q.nxt, q.cxy_cur[i]));
+    inc_register(q, i, k, k != inc_key_of_cur_cell(q.cur, q.nxt, cxy));
 }
+__device__ __forceinline__ void inc_classify_particle(const IncClassifyP& q, uint32_t i, float x, float y) { inc_classify_particle(q, i, x, y, q.cxy_cur[i]); }
 
 // Multi-resolution scenes sort by a grid whose cell is the support of the SMALLEST particle.  A tile is
 // ts x ts cells with ts * cs >= the largest support, so every neighbour of a particle lives in the 3 x 3

@@ -215,14 +215,15 @@ struct IncFusedP {
 };
 void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, const float4* pm_new, const IncClassifyP& q, bool classified,
                                    const uint32_t* cell_start_cur, uint32_t* key_out, uint32_t* cell_start_out, const ReorderIO& io, uint32_t* bsum, uint32_t* movers,
-                                   uint32_t* movers_host, const IncFusedP* fused = nullptr);
+                                   uint32_t* movers_host, const IncFusedP* fused = nullptr,
+                                   bool serial_flags = false /* laboratory: the flag bytes of a cell one per round trip (Options::boundary_chains = 0) */);
 
 // ... for a slab rank behind its fused refresh: slots [0, n_prev) are last step's sorted array (those of class >= kg.gone_from in
 // kg.gone[0 .. kg.n_gone) left the rank and are not placed), [n_prev, n) this step's arrivals; sorted keys and the permutation
 // (slot -> current index) of the live slots, and the cell-range table -- what radix_sort_pairs (with the key `ncells` for the slots
 // that left) + launch_cell_start produce for them
 void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint32_t n_prev, const CellKeyGen& kg, const IncClassifyP& q, const uint32_t* cell_start_cur,
-                                uint32_t* key_out, uint32_t* perm_out, uint32_t* cell_start_out, uint32_t* bsum, uint32_t* movers, uint32_t* movers_host);
+                                uint32_t* key_out, uint32_t* perm_out, uint32_t* cell_start_out, uint32_t* bsum, uint32_t* movers, uint32_t* movers_host, bool serial_flags = false);
 
 // out[i] = in[perm[i]] for every array of `io`, cxy_out[i] = the cell of sorted_key[i] in grid g; cell_start_scratch != nullptr: also
 // clears the work-list counter of the launch_cell_start that follows
@@ -318,6 +319,7 @@ struct SweepArgs {
     uint32_t* prog_host = nullptr;
     uint32_t prog_epoch = 0;
     int opt_tile = 0, opt_jacobi_generic = 0;   // Options::tile / ::jacobi_generic of the context (sph_context.hpp)
+    int opt_boundary_chains = 1;                // Options::boundary_chains (the tail's form: launch_solver_tail, solver_tail_partials)
     Profiler* prof = nullptr;                   // host side only: the context's profiler (launch_sweep asks it for a timestamp slot)
 };
 
@@ -355,6 +357,26 @@ void launch_solver_handoff(hipStream_t s, Profiler* prof, SolverCtrl* ctrl, Solv
 // the integrate map of the solver mode, once the solve is done; gate_out: the tail also does k_solver_handoff's job
 void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, SolveTail tail, float4* pm_out, SolverCtrl* handoff_host = nullptr,
                         uint32_t* gate_out = nullptr);
+// A workgroup of the tail owns a tile of U x 256 consecutive particles (k_solver_tail): U of the integrating tails and of TAIL_VEL, as
+// measured (profiles/step_boundary_chains.md; a variant build sets another one, scripts/variants).  `chains` =
+// Options::boundary_chains: 0 (laboratory build) the one-particle form the tiled one replaced.
+#ifndef SOLVER_TAIL_U
+#define SOLVER_TAIL_U 2       // (1: 16.5, 2: 16.0, 4: 16.6 us for the integrating tail at 2^20 particles, the one-particle form 17.1)
+#endif
+#ifndef SOLVER_TAIL_VEL_U
+#define SOLVER_TAIL_VEL_U 2   // (1: 10.5, 2: 9.1, 4: 9.9 us, the one-particle form 11.4 in the same traces)
+#endif
+inline uint32_t solver_tail_tile(SolveTail tail, int chains)
+{
+    if (chains == 0) return 1u;
+    return tail == TAIL_VEL ? (uint32_t)SOLVER_TAIL_VEL_U : (uint32_t)SOLVER_TAIL_U;
+}
+// the header partials an integrating tail leaves for n particles: one per workgroup -- what every reader of SweepArgs::hdr_partials is told
+inline uint32_t solver_tail_partials(uint32_t n, int chains)
+{
+    const uint32_t tile = 256u * solver_tail_tile(TAIL_VX, chains);
+    return (n + tile - 1u) / tile;
+}
 void launch_jacobi_update(hipStream_t s, Profiler* prof, const SweepArgs& a, int iter, const SolveRule& rule);   // sweep B
 // level estimation (sorted order)
 struct LevelArgs {

@@ -285,6 +285,30 @@ __device__ __forceinline__ void inc_cur_range(const IncGrid& G, uint32_t c, cons
     }
 }
 
+// stayers (flag 0) among the flag bytes mv[b, e) of a cell's old range: BATCH bytes requested together, so a cell of up to BATCH
+// particles costs one load round trip where a loop over single bytes costs one per particle (the addresses are clamped into the
+// range, the bytes behind its end do not count).  `serial` (launch-uniform; laboratory build only, Options::boundary_chains = 0): the
+// loop over single bytes.
+template <uint32_t BATCH>
+__device__ __forceinline__ uint32_t inc_count_stayers(const uint8_t* __restrict__ mv, uint32_t b, uint32_t e, bool serial)
+{
+    uint32_t r = 0;
+#ifdef SPH_LAB
+    if (serial) {
+        for (uint32_t j = b; j < e; j++) r += mv[j] ? 0u : 1u;
+        return r;
+    }
+#endif
+    for (uint32_t j = b; j < e; j += BATCH) {
+        uint32_t f[BATCH];
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; u++) f[u] = mv[min(j + u, e - 1u)];
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; u++) r += (j + u < e && f[u] == 0u) ? 1u : 0u;
+    }
+    return r;
+}
+
 // 1. new key and mover flag of every particle; a mover hangs itself into the list of the cell it enters (head[c]: epoch-tagged, so
 //    the table is never cleared -- an entry of another step reads as "empty").  inc_classify_particle, sph_device.h; the integrating
 //    tail of the step's last solve does the same for the positions it has just computed, and this launch is then not needed.
@@ -435,7 +459,7 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
                                                             const unsigned long long* __restrict__ head, uint32_t epoch, const uint32_t* __restrict__ cxy_cur,
                                                             uint32_t* __restrict__ key_out, ReorderIO io, uint32_t* __restrict__ perm_out,
                                                             const uint32_t* __restrict__ bsum, uint32_t* __restrict__ cell_start_fin, uint32_t* __restrict__ movers,
-                                                            uint32_t* __restrict__ movers_host)
+                                                            uint32_t* __restrict__ movers_host, bool serial_flags)
 {
     __shared__ uint32_t s_w[4];
     const uint32_t fin_blocks = FUSED ? inc_count_blocks(G.nxt.ncells) : 0u;   // (in FRONT of the particles': they run beside the first of them, not behind the last)
@@ -466,16 +490,16 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
     if (!FUSED && i_raw >= n) return;
     const bool past = FUSED && i_raw >= n;
     const uint32_t i = past ? n - 1u : i_raw;
-    // (everything that does not depend on the slot is requested first)
+    // (everything that does not depend on the slot is requested first, and nothing waits for the flag byte in front of it: the cell
+    //  word is in bounds for every i < n -- an arrival has no current cell and does not use what it reads)
     const uint32_t flag = mv[i];
-    if (PERM && flag == 2u) return;
     const uint32_t c = nk[i];
-    const bool mover = flag != 0u;
-    const uint32_t own = mover ? 0u : cxy_cur[i];   // (an arrival has no current cell)
+    const uint32_t own = cxy_cur[i];
     float4 pm;
     float2 vel;
     uint32_t orig = 0;
-    float lvl = 0.f, lvlold = 0.f;
+    float lvl = 0.f, lvlold = 0.f, h2n = 0.f, lam = 0.f;
+    uint8_t szc = 0;
     if (!PERM) {
         pm = io.pm_in[i];
         vel = io.vel_in[i];
@@ -484,9 +508,36 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
             lvl = io.lvl_in[i];
             lvlold = io.lvlold_in[i];
         }
+        if (io.h2n_in) h2n = io.h2n_in[i];   // (launch-uniform, like the next two)
+        if (io.lam_in) lam = io.lam_in[i];
+        if (io.szc_in) szc = io.szc_in[i];
     }
+    if (PERM && flag == 2u) return;
+    const bool mover = flag != 0u;
+    // the stayers of the wave: a stayer reads its rank among those of its cell off this word (sph_boundary_fused.hpp).  A lane that has
+    // left -- past the end, a slot that left the rank -- or goes along past the last particle is no stayer.
+    const uint64_t stay = __ballot(!mover && !past);
     const unsigned long long h = head[c];
     uint32_t first = cell_start_nxt[c];
+    // the flag bytes in front of the particle in its new cell: [b, e) to be counted by loads, r_in already counted from the ballot
+    uint32_t b = 0, e = 0, r_in = 0;
+    if (!mover && !past) {   // the particle's own cell: no division
+        const uint32_t k = (own & 0xffffu) + (own >> 16) * (uint32_t)G.cur.sx;
+        b = cell_start_cur[k];
+        const uint32_t w0 = i - lane;
+        e = inc_rank_outside_end(w0, b);   // (only a cell that starts in front of the wave leaves bytes for the loop)
+        r_in = (uint32_t)__popcll(stay & inc_rank_ballot_lanes(w0, b, i));
+#ifdef SPH_LAB
+        if (serial_flags) {
+            e = i;
+            r_in = 0;
+        }
+#endif
+    } else if (mover) {   // stayers of the cell it enters: all of them if it comes from behind the cell's old range, none if from before it
+        uint32_t eb;
+        inc_cur_range(G, c, cell_start_cur, b, eb);
+        e = inc_mover_range_end(i, b, eb);
+    }
     if (FUSED) {   // + the block sums in front of the cell's count block: every WAVE for itself, no barrier -- lane l takes the sums 4l .. 4l + 3 of a chunk of 256
         const uint32_t cb = c >> INC_CELLS_LOG2;
         uint32_t carry = 0, mine = 0;
@@ -514,17 +565,7 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
         }
         first += mine;
     }
-    uint32_t b, e, r = 0;
-    if (!mover) {   // the particle's own cell: no division
-        const uint32_t k = (own & 0xffffu) + (own >> 16) * (uint32_t)G.cur.sx;
-        b = cell_start_cur[k];
-        e = i;
-    } else {        // stayers of the cell it enters: all of them if it comes from behind the cell's old range, none if from before it
-        uint32_t eb;
-        inc_cur_range(G, c, cell_start_cur, b, eb);
-        e = i >= eb ? eb : b;
-    }
-    for (uint32_t j = b; j < e; j++) r += mv[j] ? 0u : 1u;
+    uint32_t r = r_in + inc_count_stayers<4u>(mv, b, e, serial_flags);
     if ((uint32_t)(h >> 32) == epoch)
         for (uint32_t m = (uint32_t)h; m; m = next[m - 1u]) r += (m - 1u < i) ? 1u : 0u;
     const uint32_t dst = first + r;
@@ -542,9 +583,9 @@ __global__ __launch_bounds__(256) void k_inc_place_reorder(uint32_t n, IncGrid G
         io.lvl_out[dst] = lvl;
         io.lvlold_out[dst] = lvlold;
     }
-    if (io.h2n_in) io.h2n_out[dst] = io.h2n_in[i];
-    if (io.lam_in) io.lam_prev_out[dst] = io.lam_in[i];
-    if (io.szc_in) io.szc_out[dst] = io.szc_in[i];
+    if (io.h2n_in) io.h2n_out[dst] = h2n;
+    if (io.lam_in) io.lam_prev_out[dst] = lam;
+    if (io.szc_in) io.szc_out[dst] = szc;
     const uint32_t cy = c / (uint32_t)G.nxt.sx;
     io.cxy_out[dst] = (c - cy * (uint32_t)G.nxt.sx) | (cy << 16);
 }
@@ -553,7 +594,7 @@ size_t incremental_sort_block_sums(uint32_t ncells) { return inc_count_blocks(nc
 
 void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, const float4* pm_new, const IncClassifyP& q, bool classified,
                                    const uint32_t* cell_start_cur, uint32_t* key_out, uint32_t* cell_start_out, const ReorderIO& io, uint32_t* bsum, uint32_t* movers,
-                                   uint32_t* movers_host, const IncFusedP* fused)
+                                   uint32_t* movers_host, const IncFusedP* fused, bool serial_flags)
 {
     const IncGrid G{q.cur, q.nxt};
     const uint32_t ncells = q.nxt.ncells, cblocks = (uint32_t)incremental_sort_block_sums(ncells);
@@ -566,7 +607,7 @@ void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, co
         {
             ProfScope ps(prof, "inc_reorder", s);
             hipLaunchKernelGGL((k_inc_place_reorder<false, true>), dim3((n + 255) / 256 + cblocks), dim3(256), 0, s, n, G, cell_start_cur, (const uint32_t*)fused->local,
-                               q.nk, q.mv, q.next, q.head, q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)bsum, cell_start_out, movers, movers_host);
+                               q.nk, q.mv, q.next, q.head, q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)bsum, cell_start_out, movers, movers_host, serial_flags);
         }
         return;
     }
@@ -586,12 +627,12 @@ void incremental_cell_sort_reorder(hipStream_t s, Profiler* prof, uint32_t n, co
     {
         ProfScope ps(prof, "inc_reorder", s);
         hipLaunchKernelGGL((k_inc_place_reorder<false, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head,
-                           q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+                           q.epoch, q.cxy_cur, key_out, io, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, serial_flags);
     }
 }
 
 void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint32_t n_prev, const CellKeyGen& kg, const IncClassifyP& q, const uint32_t* cell_start_cur,
-                                uint32_t* key_out, uint32_t* perm_out, uint32_t* cell_start_out, uint32_t* bsum, uint32_t* movers, uint32_t* movers_host)
+                                uint32_t* key_out, uint32_t* perm_out, uint32_t* cell_start_out, uint32_t* bsum, uint32_t* movers, uint32_t* movers_host, bool serial_flags)
 {
     const IncGrid G{q.cur, q.nxt};
     const uint32_t ncells = q.nxt.ncells, cblocks = (uint32_t)incremental_sort_block_sums(ncells);
@@ -611,7 +652,7 @@ void incremental_cell_sort_perm(hipStream_t s, Profiler* prof, uint32_t n, uint3
     {
         ProfScope ps(prof, "inc_place", s);
         hipLaunchKernelGGL((k_inc_place_reorder<true, false>), dim3((n + 255) / 256), dim3(256), 0, s, n, G, cell_start_cur, cell_start_out, q.nk, q.mv, q.next, q.head,
-                           q.epoch, q.cxy_cur, key_out, ReorderIO{}, perm_out, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+                           q.epoch, q.cxy_cur, key_out, ReorderIO{}, perm_out, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, serial_flags);
     }
 }
 

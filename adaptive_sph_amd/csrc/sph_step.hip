@@ -105,6 +105,7 @@ SweepArgs make_args(sph_ctx* c, const StepP& sp)
     }
     a.opt_tile = c->opt.tile;
     a.opt_jacobi_generic = c->opt.jacobi_generic;
+    a.opt_boundary_chains = c->opt.boundary_chains;
     a.prof = &c->prof;
     return a;
 }
@@ -514,7 +515,7 @@ static int solve_queue(Group& G, std::vector<Member>& M, SolveQ& q, bool handoff
         launch_solver_tail(m.c->stream, &m.c->prof, m.a, tail, m.c->pm[m.c->pcur ^ 1].as<float4>(), hand_host, gate_out);
         if (tail == TAIL_VEL && source_term_on_records(m.a)) m.a.xv_ok = true;   // (the tail rewrote the {x, y, v} record with the velocities it left)
         if (tail >= TAIL_VX /* the integrating tails */ && m.a.hdr_partials && !q.header_in_build)
-            launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev, publish_next && !G.multi());
+            launch_header_ahead(m.c, solver_tail_partials(m.n, m.a.opt_boundary_chains), m.c->hdr_host_dev, publish_next && !G.multi());
     }
     return SPH_OK;
 }
@@ -1094,7 +1095,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
                                      c->inc_head.as<unsigned long long>(), c->inc_epoch};
                 incremental_cell_sort_perm(s, prof, n_sort, n_prev, kg, q, c->cell_start.as<uint32_t>(), c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(),
                                            c->acell_start.as<uint32_t>(), c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(),
-                                           (uint32_t*)(c->ctrl_host_dev + 2) + 1);
+                                           (uint32_t*)(c->ctrl_host_dev + 2) + 1, c->opt.boundary_chains == 0);
                 c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
                 std::swap(c->cell_start, c->acell_start);   // (the old table was read while the new one was written)
                 if (n) launch_reorder(s, prof, n, g, c->key[0].as<uint32_t>(), c->val[0].as<uint32_t>(), io, c->cs_scratch.p);
@@ -1593,7 +1594,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             // (fused: the header of the tail just queued, published to the wait that follows -- what solve_queue() left out)
             IncFusedP fused{};
             if (plan.fused) {
-                fused = IncFusedP{c->inc_local.as<uint32_t>(), header_ahead_args(c, (n + 255u) / 256u, c->hdr_host_dev, true)};
+                fused = IncFusedP{c->inc_local.as<uint32_t>(), header_ahead_args(c, solver_tail_partials(n, c->opt.boundary_chains), c->hdr_host_dev, true)};
             }
             // (fused, a scene whose solves run on records: the place launch holds x and v of every particle anyway and leaves them as one
             //  record in the new order, for the fused a_ii / force sweep of the step that adopts this build -- OpFuseU)
@@ -1605,7 +1606,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             }
             incremental_cell_sort_reorder(s, &c->prof, n, integrated, plan.q, /* classified by the tail */ true, c->cell_start.as<uint32_t>(), c->akey[0].as<uint32_t>(),
                                           c->acell_start.as<uint32_t>(), io,
-                                          c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1, plan.fused ? &fused : nullptr);
+                                          c->inc_bsum.as<uint32_t>(), c->inc_movers.as<uint32_t>(), (uint32_t*)(c->ctrl_host_dev + 2) + 1, plan.fused ? &fused : nullptr,
+                                          c->opt.boundary_chains == 0);
             c->inc_count_valid = true;   // (a count of the current state is on its way, behind any stale one on the same stream)
         } else {
             const CellKeyGen kg{integrated, g, nullptr, 0u, (uint32_t)SC_GONE_FROM, 1};   // (clamped keys: the grid is a prediction)
@@ -1655,7 +1657,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             if (!m.n) continue;
             launch_pressure_accel(m.c->stream, &m.c->prof, m.a, -1, solve.rule, DECIDE_NOT_HERE);   // (the solve is over: nothing to decide)
             launch_solver_tail(m.c->stream, &m.c->prof, m.a, TAIL_VX, m.c->pm[m.c->pcur ^ 1].as<float4>());
-            if (m.a.hdr_partials) launch_header_ahead(m.c, (m.n + 255u) / 256u, m.c->hdr_host_dev);
+            if (m.a.hdr_partials) launch_header_ahead(m.c, solver_tail_partials(m.n, m.a.opt_boundary_chains), m.c->hdr_host_dev);
         }
         if ((rc = solve_wait(G, !level_on))) return rc;
         rec(5);

@@ -1906,7 +1906,117 @@ struct OpPressureAccelU : OpPressureAccel<MathT> {
 // The integrating tails know the positions and velocities the NEXT step starts from: they also reduce that step's header
 // (bounding box, h range, CFL term -- what k_header computes) per block, so the next step starts without the header kernels
 // and without the host wait behind them (hdr_partials == nullptr: not wanted).
-__global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, SolveTail tail, float dt, float vfactor, const float4* __restrict__ pm, float4* __restrict__ pm_out,
+// One tile of U x 256 consecutive particles per workgroup, lane t owns particles tile + t + 256 k (every instruction coalesced), the
+// copy kernel's structure (sph_api.hip: k_copy4u).  The tail is a compile-time parameter, so everything a lane reads of its U
+// particles -- record, a^p record, velocity, the cell word the classification compares with, the slab's owned flag -- is requested
+// together behind the `done` test, before the first use: one vector round trip where the one-particle form had four (pm; pacc + vel;
+// cxy_cur inside the classification; profiles/step_boundary_chains.md).  Per particle the operations and their order are unchanged.
+// The block's header partial covers its U x 256 particles: solver_tail_partials() of them (minima and maxima: exact in any grouping).
+template <int TAIL, int U>
+__global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, float dt, float vfactor, const float4* __restrict__ pm, float4* __restrict__ pm_out,
+                                                      float2* __restrict__ vel, const float4* __restrict__ pacc, const uint32_t* __restrict__ orig,
+                                                      const uint8_t* __restrict__ owned, const SolverCtrl* __restrict__ ctrl, HeaderOut* __restrict__ hdr_partials,
+                                                      DeviceStatus* status, const uint32_t* __restrict__ gate, SolverCtrl* __restrict__ handoff_host,
+                                                      uint32_t* __restrict__ gate_out, IncClassifyP inc, float4* __restrict__ xv)
+{
+    constexpr bool INTEGRATES = TAIL >= TAIL_VX;
+    if (gate && *gate == 0u) return;
+    const bool b0t0 = blockIdx.x == 0 && threadIdx.x == 0;
+    const bool done = ctrl->done != 0u;   // (the decision was taken by the last sweep A's block 0, or the launch that stood in for it)
+    // chained solves: this is the FIRST solve's tail -- hand its control block to the host and open (or keep shut) the gate of
+    // the second solve's launches (k_solver_handoff's job; the next kernel starts after every block of this one has finished)
+    if (gate_out && b0t0) {
+        const SolverCtrl v = *ctrl;
+        *handoff_host = v;
+        __threadfence_system();
+        *gate_out = done ? 1u : 0u;
+    }
+    if (!done) return;
+    const uint32_t i0 = blockIdx.x * (uint32_t)(U * 256) + threadIdx.x;
+    const bool classify = INTEGRATES && inc.head != nullptr;   // (launch-uniform)
+    // every load of the lane's U particles, in bounds for every i < n whoever owns the particle
+    float4 Ai[U], rec[U];
+    float2 v[U];
+    uint32_t cxy[U], own[U];
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+        const uint32_t i = i0 + 256u * (uint32_t)k;
+        const bool in = i < n;
+        Ai[k] = make_float4(0.f, 0.f, 0.f, 0.f);   // (TAIL_VEL moves no particle and reduces no header: it does not need the record)
+        rec[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[k] = make_float2(0.f, 0.f);
+        cxy[k] = 0u;
+        own[k] = in ? 1u : 0u;
+        if (in) {
+            if (INTEGRATES) Ai[k] = pm[i];
+            rec[k] = pacc[i];
+            v[k] = vel[i];
+            if (classify) cxy[k] = inc.cxy_cur[i];
+            if (owned) own[k] = owned[i];
+        }
+    }
+    const float INF = __uint_as_float(0x7f800000u);
+    float mnx = INF, mxx = -INF, mny = INF, mxy = -INF, hmx = 0.f, hmn = INF, cfl = INF;
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+        if (own[k] == 0u) continue;   // (past the end, or a slab's ghost)
+        const uint32_t i = i0 + 256u * (uint32_t)k;
+        const float2 ap = make_float2(rec[k].z, rec[k].w);
+        float2 w = v[k];
+        float4 p = Ai[k];
+        if (TAIL == TAIL_VEL) {
+            w.x += dt * ap.x;
+            w.y += dt * ap.y;
+            if (!isfinite(w.x) || !isfinite(w.y)) raise_error(status, SPH_ERR_VELOCITY_NOT_FINITE, orig[i]);
+            if (xv) xv[i] = make_float4(rec[k].x, rec[k].y, w.x, w.y);   // (the a^p record carries the position: sweep A's finish; OpSourceU gathers this)
+        } else if (TAIL == TAIL_VX) {
+            w.x += dt * ap.x;
+            w.y += dt * ap.y;
+            p.x += dt * w.x;
+            p.y += dt * w.y;
+            if (!isfinite(w.x) || !isfinite(w.y)) raise_error(status, SPH_ERR_VELOCITY_NOT_FINITE, orig[i]);
+            pm_out[i] = p;
+        } else {
+            p.x += dt * w.x + dt * dt * ap.x;
+            p.y += dt * w.y + dt * dt * ap.y;
+            w.x += dt * ap.x * vfactor;
+            w.y += dt * ap.y * vfactor;
+            if (!isfinite(p.x) || !isfinite(p.y)) raise_error(status, SPH_ERR_POSITION_NOT_FINITE, orig[i]);
+            pm_out[i] = p;
+        }
+        vel[i] = w;
+        // the incremental cell sort queued behind this launch (sph_sort.hip) wants every particle's new cell: the position is at hand
+        if (classify) inc_classify_particle(inc, i, p.x, p.y, cxy[k]);
+        if (INTEGRATES) {
+            const float nh = Ai[k].w;
+            const float sr = nh * 2.f;
+            const float ncfl = sr * sr / ((w.x * w.x + w.y * w.y) + 0.01f);   // simulation.rs:2182-2189
+            mnx = fminf(mnx, p.x); mxx = fmaxf(mxx, p.x); mny = fminf(mny, p.y); mxy = fmaxf(mxy, p.y);
+            hmx = fmaxf(hmx, nh); hmn = fminf(hmn, nh);
+            cfl = fminf(cfl, ncfl);
+        }
+    }
+    if (!INTEGRATES || !hdr_partials) return;   // launch-uniform
+    // (every thread of the block is here -- the exits above are launch- or block-uniform: the DPP network sees full waves)
+    mnx = wave_min_dpp(mnx); mny = wave_min_dpp(mny); mxx = wave_max_dpp(mxx); mxy = wave_max_dpp(mxy);
+    hmx = wave_max_dpp(hmx); hmn = wave_min_dpp(hmn); cfl = wave_min_dpp(cfl);
+    __shared__ HeaderOut s_h[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) s_h[wv] = HeaderOut{mnx, mny, mxx, mxy, hmx, hmn, cfl, 0};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        HeaderOut o = s_h[0];
+        for (int k = 1; k < 4; k++) {
+            o.min_x = fminf(o.min_x, s_h[k].min_x); o.min_y = fminf(o.min_y, s_h[k].min_y);
+            o.max_x = fmaxf(o.max_x, s_h[k].max_x); o.max_y = fmaxf(o.max_y, s_h[k].max_y);
+            o.h_max = fmaxf(o.h_max, s_h[k].h_max); o.h_min = fminf(o.h_min, s_h[k].h_min);
+            o.min_cfl = fminf(o.min_cfl, s_h[k].min_cfl);
+        }
+        hdr_partials[blockIdx.x] = o;
+    }
+}
+#ifdef SPH_LAB   // the form this one replaced, one particle per lane and its loads one behind the other: laboratory only (Options::boundary_chains = 0)
+__global__ __launch_bounds__(256) void k_solver_tail_serial(uint32_t n, SolveTail tail, float dt, float vfactor, const float4* __restrict__ pm, float4* __restrict__ pm_out,
                                                       float2* __restrict__ vel, const float4* __restrict__ pacc, const uint32_t* __restrict__ orig,
                                                       const uint8_t* __restrict__ owned, const SolverCtrl* __restrict__ ctrl, HeaderOut* __restrict__ hdr_partials,
                                                       DeviceStatus* status, const uint32_t* __restrict__ gate, SolverCtrl* __restrict__ handoff_host,
@@ -1986,6 +2096,7 @@ __global__ __launch_bounds__(256) void k_solver_tail(uint32_t n, SolveTail tail,
         hdr_partials[blockIdx.x] = o;
     }
 }
+#endif   // SPH_LAB (k_solver_tail_serial)
 
 // ------------------------------------------------------------------------------------------------
 // Op: relaxed-Jacobi pressure update (sweep B)
@@ -3608,10 +3719,24 @@ void launch_pack_and_totals(hipStream_t s, Profiler* prof, const SweepArgs& a, i
 void launch_solver_tail(hipStream_t s, Profiler* prof, const SweepArgs& a, SolveTail tail, float4* pm_out, SolverCtrl* handoff_host, uint32_t* gate_out)
 {
     ProfScope ps(prof, "solver_tail", s);
-    if (a.n && tail != TAIL_NONE)
-        hipLaunchKernelGGL(k_solver_tail, dim3((a.n + 255) / 256), dim3(256), 0, s, a.n, tail, a.sp.dt, a.sp.hyb_vfactor, a.pm, pm_out, a.vel, a.pacc, a.orig,
-                           a.owned, a.ctrl, tail >= TAIL_VX ? a.hdr_partials : nullptr, a.status, a.gate, handoff_host, gate_out,
-                           tail >= TAIL_VX ? a.inc : IncClassifyP{}, tail == TAIL_VEL && source_term_on_records(a) ? a.xv : nullptr);
+    if (!a.n || tail == TAIL_NONE) return;
+    HeaderOut* const hdr = tail >= TAIL_VX ? a.hdr_partials : nullptr;
+    const IncClassifyP inc = tail >= TAIL_VX ? a.inc : IncClassifyP{};
+    float4* const xv = tail == TAIL_VEL && source_term_on_records(a) ? a.xv : nullptr;
+#ifdef SPH_LAB
+    if (a.opt_boundary_chains == 0) {
+        hipLaunchKernelGGL(k_solver_tail_serial, dim3((a.n + 255) / 256), dim3(256), 0, s, a.n, tail, a.sp.dt, a.sp.hyb_vfactor, a.pm, pm_out, a.vel, a.pacc, a.orig,
+                           a.owned, a.ctrl, hdr, a.status, a.gate, handoff_host, gate_out, inc, xv);
+        return;
+    }
+#endif
+#define SPH_TAIL_LAUNCH(T, UU)                                                                                                                                  \
+    hipLaunchKernelGGL((k_solver_tail<T, UU>), dim3((a.n + 256u * UU - 1u) / (256u * UU)), dim3(256), 0, s, a.n, a.sp.dt, a.sp.hyb_vfactor, a.pm, pm_out, a.vel, \
+                       a.pacc, a.orig, a.owned, a.ctrl, hdr, a.status, a.gate, handoff_host, gate_out, inc, xv)
+    if (tail == TAIL_VEL) SPH_TAIL_LAUNCH(TAIL_VEL, SOLVER_TAIL_VEL_U);
+    else if (tail == TAIL_VX) SPH_TAIL_LAUNCH(TAIL_VX, SOLVER_TAIL_U);
+    else SPH_TAIL_LAUNCH(TAIL_HYBRID, SOLVER_TAIL_U);
+#undef SPH_TAIL_LAUNCH
 }
 
 // Chained solves (HybridDFSPH, one context): the host does not wait between the divergence solve and the density solve.  Behind
