@@ -12,6 +12,7 @@
 
 #include "sph_carry.hpp"
 #include "sph_internal.hpp"
+#include "sph_step_plan.hpp"   // AheadBuild
 
 struct sph_probe_set;   // include/sph_probe.h, sph_probe.hip
 
@@ -295,13 +296,7 @@ struct sph_ctx : Carry {   // (sph_carry.hpp: what a step leaves behind, its val
     DevBuf inc_local;   // the fused build (IncFusedP): the cell-range table in its two-level form
     uint32_t inc_epoch = 0;     // tag of the current call's list heads
     int inc_radix_streak = 0;   // ahead builds in a row that took the radix sort because the last known mover count was large
-    struct Ahead {   // the build queued while ahead_valid
-        GridP g{};
-        float h_max = 0.f, h_min = 0.f, rest_density = 0.f;
-        int tile_ts = 0, tile_tsx = 0, tile_tsy = 0;   // multi-resolution scenes: the tiles of the predicted grid
-        uint64_t n = 0;
-        bool xv_rec = false;   // its place launch left {x, y, v} in xvn (the step that adopts it may run OpFuseU; gone with ahead_valid)
-    } ahead;
+    AheadBuild ahead;   // the build queued while ahead_valid (sph_step_plan.hpp)
     DevBuf hdr_ahead_partials;   // per sweep block: next step's header terms from the integrating final sweep
     float hdr_ahead_rest_density = 0.f;   // (of the header computed ahead: hdr_ahead)
     DevBuf h2n[2];     // ParticleVec::h2_next (FromDistribution* support-length estimation), ping-pong across the reorder

@@ -285,6 +285,7 @@ int wait_all(Group& G)
 // ------------------------------------------------------------------------------------------------
 // collective error check at a wait point: returns the first error of this process, or (multi-rank) a generic
 // failure if another rank failed -- every rank must leave the step together or the next collective hangs
+static int other_rank_failed(sph_ctx* c, int status) { return c->fail(status, "another rank of the slab decomposition reported status %d", status); }
 int agree(Group& G, int local_rc)
 {
     if (!G.multi()) return local_rc;
@@ -292,7 +293,7 @@ int agree(Group& G, int local_rc)
     int rc = G.comm->allreduce_max_i32(G, v);
     if (rc) return rc;
     if (local_rc) return local_rc;
-    if (v[0]) return G.m[0]->fail(v[0], "another rank of the slab decomposition reported status %d", v[0]);
+    if (v[0]) return other_rank_failed(G.m[0], v[0]);
     return SPH_OK;
 }
 
@@ -382,9 +383,7 @@ struct SolveQ {
     int tot_slot = 0;   // slab decomposition: which totals buffer the solve all-reduces (1: the gated solve of a chained pair)
     uint32_t k = 1, upto = 2;
     bool header_in_build = false;   // the build the caller queues right behind this solve's integrating tail reduces the tail's header partials (the fused merge: no k_header_ahead)
-    void extend() { upto = k + std::max(1u, k / 4u); }   // a quarter more iterations per wait, at least one: a skipped
-                                                         // iteration costs two empty launches (~9 us), a wait the round trip to the host
-                                                         // (measured on the driver window, 5 runs each: k/4 1.279-1.295 ms per step, k/2 1.284-1.292, k 1.300-1.311)
+    void extend() { upto = solve_extend_upto(k); }   // the prediction fell short (sph_step_plan.hpp)
 };
 // one context: sweep A of iteration k -- a^p from pressure buffer k & 1, and the stop decision of iteration k - 1 by its block 0
 static void solve_sweep_a(std::vector<Member>& M, const SolveQ& q, uint32_t k)
@@ -485,6 +484,16 @@ static int solve_begin(Group& G, std::vector<Member>& M, SolveQ& q, uint32_t pre
     q.upto = predicted_iters > 2 ? predicted_iters : 2;
     return SPH_OK;
 }
+// iteration k: sweep B(k), and sweep A(k + 1) behind its exchange
+static int solve_iteration(Group& G, std::vector<Member>& M, const SolveQ& q, uint32_t k)
+{
+    for (auto& m : M) {
+        (void)hipSetDevice(m.c->device);
+        if (m.n) launch_jacobi_update(m.c->stream, &m.c->prof, m.a, (int)k, q.s.rule);
+    }
+    // (no exchange of a^p: the first ghost ring computes its own in sweep A)
+    return exchange_and_sweep_a(G, M, q, k + 1);
+}
 // iterations k .. upto, the (late) decision on the last one and the solve's tail
 // `handoff`: the solve is the first of a chained pair -- its tail (or, where no tail runs, k_solver_handoff) hands the control block
 // over and sets the second solve's gate.  `publish_next`: the caller waits right behind this (sync_ctrl): the header kernel of an
@@ -493,15 +502,8 @@ static int solve_queue(Group& G, std::vector<Member>& M, SolveQ& q, bool handoff
 {
     int rc;
     const SolveTail tail = q.s.tail;
-    for (; q.k <= q.upto && q.k <= q.s.rule.max_iters; q.k++) {
-        const uint32_t k = q.k;
-        for (auto& m : M) {
-            (void)hipSetDevice(m.c->device);
-            if (m.n) launch_jacobi_update(m.c->stream, &m.c->prof, m.a, (int)k, q.s.rule);
-        }
-        // (no exchange of a^p: the first ghost ring computes its own in sweep A)
-        if ((rc = exchange_and_sweep_a(G, M, q, k + 1))) return rc;
-    }
+    for (; q.k <= q.upto && q.k <= q.s.rule.max_iters; q.k++)
+        if ((rc = solve_iteration(G, M, q, q.k))) return rc;
     // (slab decomposition: the decision on the last queued iteration was taken behind its all-reduce, like every other -- by the last
     //  sweep A's block 0, or the launch that stands in for it: exchange_and_sweep_a)
     for (auto& m : M) {
@@ -543,23 +545,7 @@ static void solve_stats(Member& m, const SolveQ& q, const SolverCtrl& h)
 // iterations (the smaller of the last two counts) are queued without looking: a cushion against a host thread that is late once.
 // The tail is queued when the host has SEEN "stop": no gate, no re-queueing, and between the two solves of HybridDFSPH no wait.
 
-// Small scenes: an iteration of n particles takes ~46 us x n / 2^20 on the device, the host's answer to a decision ~10-20 us: the
-// lead grows as the sweeps shrink (1 from ~0.45M particles up), and the unpaced head is the smaller of the last two counts; large
-// scenes queue nothing unpaced (measured on configs[1]'s driver window: 1.148 ms/step, against 1.164 with the head and 1.201-1.207
-// with the predicted queue; profiles/r3_variants.md section 5).  SPH_PACE_LEAD / SPH_PACE_PRED override both.
-static uint32_t pace_lead(const sph_ctx* c, uint32_t n)
-{
-    if (c->opt.pace_lead > 0) return (uint32_t)c->opt.pace_lead;
-    return std::min(8u, std::max(1u, (450000u + n - 1u) / std::max(n, 1u)));
-}
-static uint32_t pace_prediction(const sph_ctx* c, uint32_t n, uint32_t last, uint32_t prev)
-{
-    const int mode = c->opt.pace_pred;   // 0: nothing unpaced; 1: min of the last two counts; 2: the last count
-    const int md = mode == 0xffff ? (n >= 450000u ? 0 : 1) : mode;
-    if (md == 0) return 2u;
-    if (md == 2 || prev == 0u) return last;
-    return std::min(last, prev);
-}
+// How the lead and the unpaced head follow the particle count: pace_lead, pace_prediction (sph_step_plan.hpp).
 // Slab decompositions pace the same way with lead 1 and no unpaced head beyond the two iterations every solve runs: block 0 of the
 // sweep A behind the iteration's exchange-and-all-reduce (or k_solver_progress) publishes what the stop rule makes of the ALL-REDUCED
 // totals (solver_decide_multi) -- the same word on every rank -- and iteration k + 1 is queued only once iteration k is known to
@@ -573,11 +559,11 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q)
     while (lead_member + 1 < M.size() && M[lead_member].n == 0) lead_member++;
     Member& m = M[lead_member];
     sph_ctx* c = m.c;
-    const uint32_t lead = multi ? 1u : pace_lead(c, m.n);
+    const uint32_t lead = multi ? 1u : pace_lead(m.n, c->opt.pace_lead);
     int rc;
     sph_ctx* c0 = M[0].c;
-    const uint32_t head = q.s.density_solver ? pace_prediction(c0, M[0].n, c0->last_dens_iters, c0->prev_dens_iters)
-                                             : pace_prediction(c0, M[0].n, c0->last_div_iters, c0->prev_div_iters);
+    const uint32_t head = q.s.density_solver ? pace_prediction(M[0].n, c0->opt.pace_pred, c0->last_dens_iters, c0->prev_dens_iters)
+                                             : pace_prediction(M[0].n, c0->opt.pace_pred, c0->last_div_iters, c0->prev_div_iters);
     // one epoch for the whole group (a member's word is only compared with the epoch its own launches carry)
     c0->solve_epoch = prog_next_epoch(c0->solve_epoch);
     const uint32_t epoch = c0->solve_epoch;
@@ -588,15 +574,8 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q)
     }
     if ((rc = solve_begin(G, M, q, multi ? 2u : head))) return rc;
     const uint32_t max_iters = q.s.rule.max_iters;
-    auto iteration = [&](uint32_t k) -> int {
-        for (auto& mm : M) {
-            (void)hipSetDevice(mm.c->device);
-            if (mm.n) launch_jacobi_update(mm.c->stream, &mm.c->prof, mm.a, (int)k, q.s.rule);
-        }
-        return exchange_and_sweep_a(G, M, q, k + 1);
-    };
     for (; q.k <= q.upto && q.k <= max_iters; q.k++)
-        if ((rc = iteration(q.k))) return rc;
+        if ((rc = solve_iteration(G, M, q, q.k))) return rc;
     auto t0 = std::chrono::steady_clock::now();
     int last_seen = -2;
     for (uint64_t spins = 0;; spins++) {
@@ -605,7 +584,7 @@ static int solve_paced(Group& G, std::vector<Member>& M, SolveQ& q)
         if (seen && prog_stopped(w)) break;
         const int decided = seen ? (int)prog_decided(w) : -1;   // iterations 0 .. decided are decided; A(q.k) is queued and decides q.k - 1
         if (q.k <= max_iters && (int)q.k - 1 - decided < (int)lead) {
-            if ((rc = iteration(q.k))) return rc;
+            if ((rc = solve_iteration(G, M, q, q.k))) return rc;
             q.k++;
             continue;
         }
@@ -765,12 +744,11 @@ static int level_setup(Member& m, const sph_params* p, bool after, LevelArgs& l)
     return SPH_OK;
 }
 
-// lists of the advected positions from the cells of the pre-step ones: a neighbour may now sit ceil((k h_max + slack) / tile side) tiles away
+// lists of the advected positions from the cells of the pre-step ones: the tiles' bounds re-dilated by slack_tile_reach (sph_step_plan.hpp)
 static void redilate_tiles_for_slack(sph_ctx* c, hipStream_t s, float k, float slack)
 {
-    const float tile_side = (float)c->tile_ts * c->fgrid.cs;
-    const int d = (int)ceilf((k * c->h_max_step + slack) / tile_side);
-    launch_tile_redilate(s, &c->prof, c->tile_tsx, c->tile_tsy, d < 1 ? 1 : d, c->tile_raw.as<uint32_t>(), c->tile_h_ext.as<uint32_t>());
+    launch_tile_redilate(s, &c->prof, c->tile_tsx, c->tile_tsy, slack_tile_reach(k, c->h_max_step, slack, c->tile_ts, c->fgrid.cs), c->tile_raw.as<uint32_t>(),
+                         c->tile_h_ext.as<uint32_t>());
 }
 
 // The propagation of one context: `while changed` (simulation.rs:740-800) as sweeps queued in batches; the host learns once per batch how
@@ -779,24 +757,49 @@ struct LevelBatches {
     uint32_t t = 1, effective = 0;   // the next sweep; sweeps that assigned something so far
     int B = 8;                       // length of the batch in flight
 };
+// The level estimation of one step (simulation.rs:2018-2046, 862-927; after advection: 2678-2707), from its detection to the smoothing
+// at the end of the step: one context or the ranks of a slab decomposition, entry i for member i.
+struct LevelState {
+    std::vector<LevelArgs> lv;
+    std::vector<SweepArgs> al;   // the sweep arguments the detection and the propagation run with (advected geometry after advection)
+    float slack = 0.f;           // after advection on the extended lists: 2 x the largest displacement (TileP::slack); else 0
+    LevelBatches batches;        // one context: the propagation in flight ...
+    bool pending = false;        // ... on the side stream, collected by level_estimation_finish()
+    bool stash_middle = false;   // fill_stash_with == SurfaceDistanceMiddle
+    LevelState(size_t members, const sph_params* p) : lv(members), al(members), stash_middle(p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_MIDDLE) {}
+};
+// adds its lifetime to sph_step_stats::ms_level_estimation of the members
+struct LevelClock {
+    std::vector<Member>& M;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit LevelClock(std::vector<Member>& members) : M(members) {}
+    ~LevelClock()
+    {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        for (auto& m : M) m.st.ms_level_estimation += ms;
+    }
+};
+
 // B sweeps from st.t on and the publish of their count.  The flags live in device memory (a store to mapped host memory from every
 // assigning lane made each sweep wait for PCIe at its end); their sum goes to the host once per batch.
-static void level_queue_batch(sph_ctx* c, hipStream_t ls, const SweepArgs& al, const LevelArgs& lv, bool stash_middle, LevelBatches& st)
+static void level_queue_batch(sph_ctx* c, hipStream_t ls, LevelState& L)
 {
+    LevelBatches& st = L.batches;
     uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
     (void)hipMemsetAsync(chg, 0, (size_t)st.B * sizeof(uint32_t), ls);
     for (int b = 0; b < st.B; b++, st.t++) {
-        launch_level_propagate(ls, &c->prof, al, lv, st.t, chg + b);
-        if (st.t == 1u && stash_middle) launch_fill_stash(ls, &c->prof, al, lv, c->stash.as<float>());   // num_iter == 1, simulation.rs:769-779
+        launch_level_propagate(ls, &c->prof, L.al[0], L.lv[0], st.t, chg + b);
+        if (st.t == 1u && L.stash_middle) launch_fill_stash(ls, &c->prof, L.al[0], L.lv[0], c->stash.as<float>());   // num_iter == 1, simulation.rs:769-779
     }
     c->level_seq++;
     if (c->level_seq == 0u) c->level_seq = 1u;
     hipLaunchKernelGGL(k_publish_count, dim3(1), dim3(64), 0, ls, chg, (uint32_t)st.B, c->lvl_changed_dev, 63u, c->level_seq);
 }
 // wait for the batch in flight; while every sweep of it assigned something, another batch of 8
-static int level_collect_batches(sph_ctx* c, hipStream_t ls, const SweepArgs& al, const LevelArgs& lv, bool stash_middle, LevelBatches& st)
+static int level_collect_batches(sph_ctx* c, hipStream_t ls, LevelState& L)
 {
-    for (;; level_queue_batch(c, ls, al, lv, stash_middle, st)) {
+    LevelBatches& st = L.batches;
+    for (;; level_queue_batch(c, ls, L)) {
         if (int rc = wait_word(c, (volatile uint32_t*)c->lvl_changed + 63, c->level_seq)) return rc;
         const uint32_t changed = c->lvl_changed[0];   // "nobody assigned anything" is final: the flags are ones, then zeros
         st.effective += changed;
@@ -805,6 +808,203 @@ static int level_collect_batches(sph_ctx* c, hipStream_t ls, const SweepArgs& al
     }
     c->last_level_sweeps = st.effective;
     return SPH_OK;
+}
+// One context: propagate until a sweep assigns nothing, in batches.  The first one is predicted from the previous step's propagation
+// (level_first_batch, sph_step_plan.hpp).  `side`: the batch stays in flight on the side stream.
+static int level_propagate_batches(Member& m, hipStream_t ls, bool side, LevelState& L)
+{
+    sph_ctx* c = m.c;
+    if (!m.n) return SPH_OK;
+    launch_level_propagate(ls, &c->prof, L.al[0], L.lv[0], 0u, c->lvl_changed_d.as<uint32_t>() + 1023);   // surface particles mark their neighbours
+    L.batches = LevelBatches{};
+    L.batches.B = level_first_batch(c->last_level_sweeps, c->opt.level_batch8 != 0);
+    level_queue_batch(c, ls, L);
+    if (side) {
+        L.pending = true;
+        return SPH_OK;
+    }
+    return level_collect_batches(c, ls, L);
+}
+// The same on a slab decomposition: ghost lanes idle, the ghosts' (level, when) refreshed from their owners after the detection and
+// after every sweep, fixed batches of 8, the stop decision all-reduced.
+static int level_propagate_slabs(Group& G, std::vector<Member>& M, LevelState& L)
+{
+    int rc;
+    if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level + when", -1, sel_lv_when))) return rc;   // (both fields in one exchange)
+    const bool frontier = L.lv[0].plain_propagate == 2;
+    if (frontier)   // sweep 0: the surface particles mark their unassigned neighbours (the candidates of sweep 1)
+        for (size_t i = 0; i < M.size(); i++) {
+            (void)hipSetDevice(M[i].c->device);
+            if (M[i].n) launch_level_propagate(M[i].c->stream, &M[i].c->prof, L.al[i], L.lv[i], 0u, M[i].c->lvl_changed_d.as<uint32_t>() + 1023);
+        }
+    const int B = 8;
+    uint32_t t = 1;
+    for (bool done = false; !done;) {
+        for (auto& m : M) {
+            (void)hipSetDevice(m.c->device);
+            (void)hipMemsetAsync(m.c->lvl_changed_d.p, 0, B * sizeof(uint32_t), m.c->stream);
+        }
+        for (int b = 0; b < B; b++, t++) {
+            for (size_t i = 0; i < M.size(); i++) {
+                Member& m = M[i];
+                sph_ctx* c = m.c;
+                (void)hipSetDevice(c->device);
+                if (!m.n) continue;
+                launch_level_propagate(c->stream, &c->prof, L.al[i], L.lv[i], t, c->lvl_changed_d.as<uint32_t>() + b);
+                if (t == 1u && L.stash_middle) launch_fill_stash(c->stream, &c->prof, L.al[i], L.lv[i], c->stash.as<float>());
+            }
+            if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level + when", -1, sel_lv_when))) return rc;
+        }
+        for (auto& m : M) {
+            (void)hipSetDevice(m.c->device);
+            HIPCHK(m.c, hipMemcpyAsync(m.c->lvl_changed, m.c->lvl_changed_d.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, m.c->stream));
+        }
+        if ((rc = agree(G, wait_all(G)))) return rc;
+        // "nobody assigned anything" is final once it happens: the flags of a batch are ones followed by zeros, on every rank
+        std::vector<int> last(M.size(), 0);
+        for (size_t i = 0; i < M.size(); i++)
+            for (int b = 0; b < B; b++)
+                if (M[i].c->lvl_changed[b]) last[i] = b + 1;
+        if ((rc = G.comm->allreduce_max_i32(G, last))) return rc;
+        done = last[0] < B;
+    }
+    return SPH_OK;
+}
+
+// Twice the largest displacement of the step over every member (a group: all-reduced): the slack of lists that are gathered at the
+// ADVECTED positions from the cells of the pre-step ones.  On a slab decomposition the ghost layer was widened for it at the start of
+// the step (slab_slack_k), which is checked here.
+static int level_measure_slack(Group& G, std::vector<Member>& M, float* slack)
+{
+    int rc;
+    sph_ctx* c0 = M[0].c;
+    for (auto& m : M) {
+        sph_ctx* c = m.c;
+        (void)hipSetDevice(c->device);
+        HIPCHK(c, c->lvl_changed_d.ensure(1024 * sizeof(uint32_t)));
+        uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
+        launch_max_disp(c->stream, &c->prof, m.n, c->pm[c->pcur].as<float4>(), c->pm[c->pcur ^ 1].as<float4>(), chg + 1022);
+        HIPCHK(c, hipMemcpyAsync(c->lvl_changed, chg + 1022, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = agree(G, wait_all(G)))) return rc;   // (one context: the wait alone)
+    std::vector<std::vector<float>> dm(M.size(), std::vector<float>(1));
+    for (size_t i = 0; i < M.size(); i++) {
+        float d;
+        memcpy(&d, (const void*)M[i].c->lvl_changed, 4);
+        dm[i][0] = std::isfinite(d) ? -d : -INFINITY;   // (NaN would stay NaN through fminf only by luck)
+    }
+    if (G.multi() && (rc = G.comm->allreduce_min_f32(G, dm))) return rc;
+    const float dmax = -dm[0][0];
+    if (!std::isfinite(dmax)) return c0->fail(SPH_ERR_POSITION_NOT_FINITE, "Assertion 'p_position[d].is_finite()' failed!");
+    *slack = 2.f * dmax;
+    if (!G.multi()) return SPH_OK;
+    for (auto& m : M) m.c->last_dmax = dmax;
+    // (all-reduced values only: every rank takes the same branch)
+    if (*slack > c0->slab_slack_w)
+        return c0->fail(SPH_ERR_UNSUPPORTED, "level estimation after advection on a slab decomposition: the particles moved %g in this step, the ghost layer "
+                        "was widened for %g (4 x the previous step's largest displacement, at least 2 h_max)", (double)dmax, (double)(0.5f * c0->slab_slack_w));
+    return SPH_OK;
+}
+
+// what the detection leaves alone, cleared in front of it; then the detection.  `every_flag`: a slab's flags / states of the ghost slots
+// are never read -- zero them so that downloads see defined bytes; one context clears what its detector does not write
+static void level_detect(sph_ctx* c, hipStream_t s, const sph_params* p, uint32_t n, const SweepArgs& al, const LevelArgs& l, bool every_flag)
+{
+    if (p->fill_stash_with == SPH_STASH_NONE) (void)hipMemsetAsync(c->stash.p, 0, (size_t)n * 4, s);
+    if (every_flag) (void)hipMemsetAsync(c->flag_surface.p, 0, n, s);
+    // (the CenterDiff detector leaves flag_insufficient_neighs alone: its default, false)
+    if (every_flag || l.center_diff) (void)hipMemsetAsync(c->flag_insufficient.p, 0, n, s);
+    launch_level_detect(s, &c->prof, al, l);
+}
+
+// Detection and propagation.  Before advection: on the positions the particles are sorted by.  `after`
+// (level_estimation_after_advection, simulation.rs:2678-2707): at the ADVECTED positions (pm[pcur ^ 1]; a slab's ghosts get theirs from
+// their owners first) -- on the step's own lists, or on extended lists gathered from the cells of the pre-step positions with every
+// search range widened by the slack.
+// One context before advection: detection and propagation are queued on the context's SECOND stream and the call returns without
+// waiting -- nothing of it is read until the smoothing at the end of the step, so the ~100 latency-bound propagation sweeps run under
+// the step's own sweeps; level_estimation_finish() collects it.  (Options::level_serial: measurement aid, everything on one stream)
+static int level_estimation(Group& G, std::vector<Member>& M, const sph_params* p, bool after, LevelState& L)
+{
+    int rc;
+    LevelClock clock(M);
+    const bool multi = G.multi();
+    const bool replay_step_lists = after && !p->use_extended_range_for_level_estimation;   // simulation.rs:2680: no rebuild
+    const bool side = !multi && !after && !M[0].c->opt.level_serial;
+    L.slack = 0.f;
+    if (after && multi) {
+        for (auto& m : M) m.lv_pmnew = (float*)m.c->pm[m.c->pcur ^ 1].as<float4>();
+        if ((rc = refresh_ghosts(G, M, sel_lv_pmnew, 4, "pm_new"))) return rc;
+    }
+    if (after && !replay_step_lists && (rc = level_measure_slack(G, M, &L.slack))) return rc;
+    hipStream_t ls = M[0].c->stream;
+    for (size_t i = 0; i < M.size(); i++) {
+        Member& m = M[i];
+        sph_ctx* c = m.c;
+        (void)hipSetDevice(c->device);
+        ls = side ? c->stream2 : c->stream;
+        if (side) {   // everything queued so far (sort, cell ranges, tile bounds) comes first
+            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+        }
+        LevelArgs& l = L.lv[i];
+        if ((rc = level_setup(m, p, after, l))) return rc;
+        l.pm_cell = after ? c->pm[c->pcur].as<float4>() : nullptr;
+        if (multi) {
+            // frontier form with probing halo members (OpLevelPropagate, mode 2); SPH_SLAB_LEVEL_PLAIN=1: every unassigned particle in
+            // every sweep (measurement / tests; parameters only: the same on every rank)
+            l.plain_propagate = M[0].c->opt.slab_level_plain ? 1 : 2;
+            l.edge = c->dist.edge.as<uint8_t>();
+        } else if (c->opt.level_queue && !l.replay_step_lists) {
+            // the propagation on a compacted frontier (explicit index lists: the extended-range lists; the step's own lists of a uniform
+            // scene are mask words, which the sweep forms replay)
+            uint32_t lg = 0;
+            while ((64ull << lg) < (m.n ? m.n : 1u)) lg++;
+            HIPCHK(c, c->lvl_queue.ensure((size_t)128 << lg));
+            l.fmap = c->lvl_queue.as<uint8_t>();
+            l.fmap_lg_s = lg;
+        }
+        SweepArgs& al = L.al[i];
+        al = m.a;
+        if (after) {
+            al.pm = c->pm[c->pcur ^ 1].as<float4>();
+            al.t_ext.slack = L.slack;
+            if (!replay_step_lists && c->tile_ts > 0) redilate_tiles_for_slack(c, ls, l.k, L.slack);
+        }
+        m.lv_level = (float*)l.level;
+        m.lv_when = (float*)l.when;
+        if (!m.n) continue;
+        // (lab, SPH_SIDE_CUS: the side stream owns a few CUs -- the heavy detection sweeps then run on the MAIN stream, and only the
+        //  propagation's ~100 small dependent launches go to the side stream, behind an event)
+        const bool masked_side = side && c->opt.side_cus > 0;
+        level_detect(c, masked_side ? c->stream : ls, p, m.n, al, l, multi);
+        if (masked_side) {
+            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+        }
+    }
+    if ((rc = multi ? level_propagate_slabs(G, M, L) : level_propagate_batches(M[0], ls, side, L))) return rc;
+    for (auto& m : M) m.c->have_level = true;
+    return SPH_OK;
+}
+// the rest of a propagation that was queued on the side stream: wait for its first batch, continue in batches of 8 if the prediction
+// fell short.  (The host saw the side stream's last publish: everything queued there has finished before the main stream goes on.)
+static int level_estimation_finish(std::vector<Member>& M, LevelState& L)
+{
+    if (!L.pending) return SPH_OK;
+    L.pending = false;
+    LevelClock clock(M);
+    return level_collect_batches(M[0].c, M[0].c->stream2, L);
+}
+// smooth_level_estimation_field (simulation.rs:2709-2722) of member i, at the advected positions; the smoothed field becomes the level field
+// (no classify_particles here: the reference's step never calls it -- sph_classify is the host's call)
+static void level_smooth_and_swap(Member& m, const LevelState& L, size_t i)
+{
+    sph_ctx* c = m.c;
+    SweepArgs as = m.a;   // (the step's geometry: the smoothing takes the advected records as its own argument)
+    as.t_ext.slack = L.slack;
+    launch_level_smooth(c->stream, &c->prof, as, L.lv[i], c->pm[c->pcur ^ 1].as<float4>(), c->lvl[c->cur].as<float>(), c->lvl_tmp.as<float>());
+    std::swap(c->lvl[c->cur], c->lvl_tmp);
 }
 
 static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs, bool* started)
@@ -868,13 +1068,10 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     std::vector<std::vector<float>> red(M.size(), std::vector<float>(8));
     int hdr_rc = SPH_OK, setup_rc = SPH_OK;
     bool slab_fused = false;   // the ghost layer is already in place (slab_refresh_fused)
-    // Ghost width in smoothing lengths of the largest particle: two rings of one support radius (2 h_max each), or the extended
-    // range of the level estimation.  Level estimation AFTER advection looks for neighbours at the advected positions among the
-    // ghosts selected BEFORE the step: the layer is widened by twice the largest displacement the step may produce -- 4 x the
-    // previous step's (all-reduced) largest displacement, at least 2 h_max -- and the step checks afterwards that it sufficed.
-    const float slab_slack_k = (level_on && p->level_estimation_after_advection && G.multi())
-                                   ? fmaxf(2.f, c0->h_max_step > 0.f ? 4.f * c0->last_dmax / c0->h_max_step : 0.f) : 0.f;
-    const float halo_base_k = fmaxf(4.f, level_on ? p->level_estimation_range / SPH_ETA : 0.f);
+    // Ghost width in smoothing lengths of the largest particle, and what level estimation AFTER advection adds to it (sph_step_plan.hpp)
+    const float range_k = p->level_estimation_range / SPH_ETA;   // simulation.rs:2036
+    const float ghost_slack_k = slab_slack_k(level_on, p->level_estimation_after_advection != 0, G.multi(), c0->last_dmax, c0->h_max_step);
+    const float ghost_base_k = halo_base_k(level_on, range_k);
     // The tail of the previous step's last solve already reduced this step's header into hdr_host (k_solver_tail,
     // k_header_ahead): nothing to launch, nothing to wait for -- unless the host touched the state or the smoothing lengths are
     // not the mass-derived ones.  On a slab the header describes the particles the rank owned at the END of that step; the ones
@@ -920,10 +1117,9 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const bool no_fused = c0->opt.slab_general != 0;   // measurement / test aid: always the general path
         const bool attempt = h_from_mass_mode && !rebalanced && !no_fused;     // (parameters and all-reduced values: the same on every rank)
         if (attempt) {
-            if ((rc = slab_refresh_fused(G, M, red, halo_base_k, slab_slack_k, &slab_fused))) return rc;
+            if ((rc = slab_refresh_fused(G, M, red, ghost_base_k, ghost_slack_k, &slab_fused))) return rc;
             if (!slab_fused && (hdr_rc || red[0][3] < 0.f)) {
-                if (hdr_rc) return hdr_rc;
-                return c0->fail((int)-red[0][3], "another rank of the slab decomposition reported status %d", (int)-red[0][3]);
+                return hdr_rc ? hdr_rc : other_rank_failed(c0, (int)-red[0][3]);
             }
         }
         std::vector<int> moved(M.size(), 0);
@@ -944,8 +1140,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     }
     g_trace.mark(0);
     if (hdr_rc) return hdr_rc;
-    if (red[0][3] < 0.f)
-        return c0->fail((int)-red[0][3], "another rank of the slab decomposition reported status %d", (int)-red[0][3]);
+    if (red[0][3] < 0.f) return other_rank_failed(c0, (int)-red[0][3]);
     const float h_max_g = -red[0][0], h_min_g = red[0][1], min_cfl_g = red[0][2];
     // (identical on every rank: all-reduced values only)
     if (!(h_max_g > 0.f) || !std::isfinite(h_max_g))
@@ -969,8 +1164,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // (the extended lists of the level estimation reach level_estimation_range / ETA smoothing lengths)
         // Two rings of one support radius (2 h_max) each: ghosts of the first ring compute their pressure acceleration here
         // (their neighbours are all inside the second), so a Jacobi iteration exchanges p / rho^2 only.
-        for (auto& m : M) m.c->slab_slack_w = slab_slack_k * h_max_g;
-        if (!slab_fused && (rc = build_ghost_layer(G, M, halo_base_k, slab_slack_k * h_max_g, h_max_g, status_in))) return rc;
+        for (auto& m : M) m.c->slab_slack_w = ghost_slack_k * h_max_g;
+        if (!slab_fused && (rc = build_ghost_layer(G, M, ghost_base_k, ghost_slack_k * h_max_g, h_max_g, status_in))) return rc;
         // bounding box of owned + ghosts from the cuts: an owned particle lies between them, a ghost within the cut's layer width beyond one
         for (size_t i = 0; i < M.size(); i++) {
             const auto& d = M[i].c->dist;
@@ -1044,27 +1239,18 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         const bool pre = c->dist.on && c->dist.pre;
         const uint32_t n_sort = pre ? m.n_sort : n;
         c->dist.pre = false;
-        // A slab rank behind its fused refresh: slots [0, n_prev) are last step's sorted array (some of them left the rank), the
-        // arrivals follow unsorted -- the stable sort is the merge of sph_sort.hip (incremental_cell_sort_perm) with the arrivals as
-        // movers, if they and the particles that changed cell last time are few; same keys, permutation and cell ranges as the radix sort.
+        // A slab rank behind its fused refresh: the stable sort as a merge (slab_merge_admitted, sph_step_plan.hpp); same keys,
+        // permutation and cell ranges as the radix sort.
         const uint32_t n_prev = pre ? c->dist.pre_cls_n : 0u;
-        bool merge = pre && c->opt.inc_sort && prev_valid && prev_grid.cs == g.cs && prev_grid.ncells > 0 && n_prev > 0 && n_prev <= n_sort && !c->exact &&
-                     inc_sort_fits(g.ncells, n_sort);
-        if (merge) {   // (the arrivals are movers of THIS build, whatever the last count was: too many of them do not touch the streak)
-            const uint32_t limit = inc_sort_mover_limit(n_sort, c->opt.inc_sort);
-            merge = n_sort - n_prev <= limit && inc_sort_worthwhile(c->inc_count_valid, *c->movers_host, limit, c->inc_radix_streak);
-        }
+        const bool merge = slab_merge_admitted(SlabSort{pre, c->opt.inc_sort, prev_valid, prev_grid.cs, prev_grid.ncells, g.cs, g.ncells, n_prev, n_sort, c->exact != 0,
+                                                        c->inc_count_valid, *c->movers_host},
+                                               c->inc_radix_streak);
         if (!merge) HIPCHK(c, c->cell_start.ensure(((size_t)g.ncells + 1) * sizeof(uint32_t)));
-        // the build the previous step queued ahead (queue_ahead_build): adopted if nothing touched the state since (the header that
-        // step left behind was still the one in force), the scene is what it predicted and the real bounding box fits its grid
+        // the build the previous step queued ahead (queue_ahead_build): adopted if nothing touched the state since, the scene is what it
+        // predicted and the real bounding box fits its grid (adopt_ahead_build, sph_step_plan.hpp)
         const GridP ag = c->ahead.g;
-        // (a multi-resolution scene: the same smoothing lengths, hence the same cell size and tile side; its tiles then lie on the
-        //  predicted grid -- another tiling bounds the neighbours' h as well, and the visiting order of a list does not depend on the
-        //  stencil width it was gathered with)
-        const bool adopt = ahead_usable && c->ahead_valid && !c->dist.on && c->ahead.n == c->n && n == (uint32_t)c->n && c->ahead.h_max == h_max_g &&
-                           c->ahead.h_min == h_min_g && c->ahead.rest_density == p->rest_density && (c->uniform_h ? c->tile_ts == 0 : c->tile_ts > 0) &&
-                           c->ahead.tile_ts == c->tile_ts && !c->exact && ag.cs == g.cs && g.minx >= ag.minx && g.miny >= ag.miny &&
-                           g.minx + g.sx <= ag.minx + ag.sx && g.miny + g.sy <= ag.miny + ag.sy;
+        const bool adopt = adopt_ahead_build(c->ahead, StepBuild{ahead_usable, c->ahead_valid, c->dist.on, c->exact != 0, c->uniform_h, (uint64_t)c->n, n, h_max_g, h_min_g,
+                                                                 p->rest_density, c->tile_ts, g});
         c->ahead_valid = false;
         if (adopt) {
             if (c->tile_ts > 0) {
@@ -1109,10 +1295,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         }
         if (c->tile_ts > 0) {
             const size_t nt = (size_t)c->tile_tsx * (size_t)c->tile_tsy;
-            // the extended-range lists reach k * h_max with k = level_estimation_range / ETA > 2: a larger particle may sit
-            // ceil(k / 2) tiles away (tile side >= 2 h_max)
             const bool want_ext = p->level_estimation_method != SPH_LEVEL_NONE;
-            const int d_ext = want_ext ? (int)ceilf(fmaxf(p->level_estimation_range / SPH_ETA, 2.f) * 0.5f) : 1;
+            const int d_ext = ext_tile_reach(want_ext, range_k);   // (how far a larger particle of the extended-range lists may sit)
             if (want_ext) HIPCHK(c, c->tile_h_ext.ensure(nt * 4));
             if (!adopt) {
                 HIPCHK(c, c->tile_raw.ensure(nt * 4));
@@ -1146,222 +1330,12 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     for (auto& m : M) dbg_sync(m.c, "neighbourhood (sort, reorder, cell ranges, maps)", 3);   // (slabs: the grid checks were taken on all-reduced numbers above, identically on every rank)
     g_trace.mark(2);
 
-    // ---- level estimation on the extended-range lists (simulation.rs:2018-2046, 862-927; after advection: 2678-2707) ------
-    LevelArgs lv{};
-    SweepArgs lv_args{};   // the arguments of a propagation queued on the side stream (level_estimation_finish)
-    float lv_slack = 0.f;
-    // `pm_old` == nullptr: the positions the particles are sorted by (before advection).  Else: `al.pm` holds the ADVECTED
-    // positions, pm_old the pre-step ones, and the extended lists are gathered from the cells of the pre-step positions with
-    // every search range widened by 2 x the largest displacement (TileP::slack).
-    // `side`: detection and propagation are queued on the context's SECOND stream and the call returns without waiting
-    // (level estimation BEFORE advection: nothing of it is read until the smoothing at the end of the step, so the ~100
-    // latency-bound propagation sweeps run under the step's own sweeps); level_estimation_finish() collects it.
-    LevelBatches lvb;
-    bool lv_pending = false;   // a batch is in flight on the side stream
-    const bool stash_middle = p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_MIDDLE;
-    auto level_estimation = [&](const float4* pm_geo, const float4* pm_old, bool side) -> int {
-        const auto t_lvl0 = std::chrono::steady_clock::now();
-        Member& m = M[0];
-        sph_ctx* c = m.c;
-        hipStream_t ls = side ? c->stream2 : c->stream;
-        if (side) {   // everything queued so far (sort, cell ranges, tile bounds) comes first
-            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        }
-        if ((rc = level_setup(m, p, pm_old != nullptr, lv))) return rc;
-        const size_t n = m.n ? m.n : 1;
-        uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
-        lv.pm_cell = pm_old;
-        // the propagation on a compacted frontier (explicit index lists: the extended-range lists; the step's own lists of a uniform
-        // scene are mask words, which the sweep forms replay)
-        if (c->opt.level_queue && !lv.replay_step_lists) {
-            uint32_t lg = 0;
-            while ((64ull << lg) < n) lg++;
-            HIPCHK(c, c->lvl_queue.ensure((size_t)128 << lg));
-            lv.fmap = c->lvl_queue.as<uint8_t>();
-            lv.fmap_lg_s = lg;
-        }
-        SweepArgs al = m.a;
-        lv_slack = 0.f;
-        if (pm_old && m.n && lv.replay_step_lists) al.pm = pm_geo;
-        if (pm_old && m.n && !lv.replay_step_lists) {
-            al.pm = pm_geo;
-            launch_max_disp(ls, &c->prof, m.n, pm_old, pm_geo, chg + 1022);
-            HIPCHK(c, hipMemcpyAsync(c->lvl_changed, chg + 1022, sizeof(uint32_t), hipMemcpyDeviceToHost, ls));
-            if ((rc = wait_stream(c))) return rc;
-            float dmax;
-            memcpy(&dmax, (const void*)c->lvl_changed, 4);
-            if (!std::isfinite(dmax)) return c->fail(SPH_ERR_POSITION_NOT_FINITE, "Assertion 'p_position[d].is_finite()' failed!");
-            lv_slack = 2.f * dmax;
-            al.t_ext.slack = lv_slack;
-            if (c->tile_ts > 0) redilate_tiles_for_slack(c, ls, lv.k, lv_slack);
-        }
-        if (m.n) {
-            // (lab, SPH_SIDE_CUS: the side stream owns a few CUs -- the heavy detection sweeps then run on the MAIN stream, and only the
-            //  propagation's ~100 small dependent launches go to the side stream, behind an event)
-            const bool masked_side = side && c->opt.side_cus > 0;
-            hipStream_t ds = masked_side ? c->stream : ls;
-            if (p->fill_stash_with == SPH_STASH_NONE) (void)hipMemsetAsync(c->stash.p, 0, n * 4, ds);
-            // (the CenterDiff detector leaves flag_insufficient_neighs alone: its default, false)
-            if (lv.center_diff) (void)hipMemsetAsync(c->flag_insufficient.p, 0, n, ds);
-            launch_level_detect(ds, &c->prof, al, lv);
-            if (masked_side) {
-                HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            }
-            // propagate until a sweep assigns nothing, in batches (LevelBatches).  The first batch is as long as the previous step's
-            // propagation + 1 -- the fluid's depth hardly changes from step to step -- so a step usually waits once instead of once per 8 sweeps.
-            launch_level_propagate(ls, &c->prof, al, lv, 0u, chg + 1023);   // surface particles mark their neighbours
-            lvb = LevelBatches{};
-            lvb.B = (int)std::min<uint32_t>(std::max<uint32_t>(c->last_level_sweeps + 1u, 8u), 1000u);
-            if (c->opt.level_batch8) lvb.B = 8;   // measurement aid: the fixed batches of 8
-            level_queue_batch(c, ls, al, lv, stash_middle, lvb);
-            if (side) {   // collected by level_estimation_finish()
-                lv_pending = true;
-                lv_args = al;
-            } else if ((rc = level_collect_batches(c, ls, al, lv, stash_middle, lvb))) {
-                return rc;
-            }
-        }
-        c->have_level = true;
-        m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
-        return SPH_OK;
-    };
-    // the rest of a propagation that was queued on the side stream: wait for its first batch, continue in batches of 8 if the
-    // prediction (the previous step's sweep count + 1) fell short
-    auto level_estimation_finish = [&]() -> int {
-        if (!lv_pending) return SPH_OK;
-        lv_pending = false;
-        const auto t_lvl0 = std::chrono::steady_clock::now();
-        if ((rc = level_collect_batches(c0, c0->stream2, lv_args, lv, stash_middle, lvb))) return rc;
-        // (the host saw the side stream's last publish: everything queued there has finished before the main stream goes on)
-        M[0].st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
-        return SPH_OK;
-    };
-    // the same on a slab decomposition (before advection): ghost lanes idle, the ghosts' (level, when) refreshed from their
-    // owners after the detection and after every sweep, propagation without frontier marks, the stop decision all-reduced
-    std::vector<LevelArgs> LV(M.size());
-    std::vector<SweepArgs> AL(M.size());   // the sweep arguments the level estimation runs with (advected geometry when `after`)
-    float slab_lv_slack = 0.f;
-    // `after` (level_estimation_after_advection, simulation.rs:2678-2707): detection and propagation on the lists of the ADVECTED
-    // positions -- the ghosts' advected records come from their owners first; the extended lists are gathered from the cells of
-    // the pre-step positions with every range widened by twice the largest displacement over ALL ranks, which the ghost layer
-    // was sized for at the start of the step (slab_slack_k) and which is checked here
-    auto level_estimation_slabs = [&](bool after) -> int {
-        const auto t_lvl0 = std::chrono::steady_clock::now();
-        const bool replay_step_lists = after && !p->use_extended_range_for_level_estimation;   // simulation.rs:2680: no rebuild
-        slab_lv_slack = 0.f;
-        if (after) {
-            for (auto& m : M) m.lv_pmnew = (float*)m.c->pm[m.c->pcur ^ 1].as<float4>();
-            if ((rc = refresh_ghosts(G, M, sel_lv_pmnew, 4, "pm_new"))) return rc;
-            if (!replay_step_lists) {
-                for (auto& m : M) {
-                    sph_ctx* c = m.c;
-                    (void)hipSetDevice(c->device);
-                    HIPCHK(c, c->lvl_changed_d.ensure(1024 * sizeof(uint32_t)));
-                    uint32_t* chg = c->lvl_changed_d.as<uint32_t>();
-                    (void)hipMemsetAsync(chg + 1022, 0, sizeof(uint32_t), c->stream);
-                    launch_max_disp(c->stream, &c->prof, m.n, c->pm[c->pcur].as<float4>(), c->pm[c->pcur ^ 1].as<float4>(), chg + 1022);
-                    HIPCHK(c, hipMemcpyAsync(c->lvl_changed, chg + 1022, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                }
-                if ((rc = agree(G, wait_all(G)))) return rc;
-                std::vector<std::vector<float>> dm(M.size(), std::vector<float>(1));
-                for (size_t i = 0; i < M.size(); i++) {
-                    float d;
-                    memcpy(&d, (const void*)M[i].c->lvl_changed, 4);
-                    dm[i][0] = -d;   // (NaN stays NaN through fminf only by luck: tested below on the local value too)
-                    if (!std::isfinite(d)) dm[i][0] = -INFINITY;
-                }
-                if ((rc = G.comm->allreduce_min_f32(G, dm))) return rc;
-                const float dmax = -dm[0][0];
-                if (!std::isfinite(dmax)) return c0->fail(SPH_ERR_POSITION_NOT_FINITE, "Assertion 'p_position[d].is_finite()' failed!");
-                for (auto& m : M) m.c->last_dmax = dmax;
-                slab_lv_slack = 2.f * dmax;
-                // (all-reduced values only: every rank takes the same branch)
-                if (slab_lv_slack > c0->slab_slack_w)
-                    return c0->fail(SPH_ERR_UNSUPPORTED, "level estimation after advection on a slab decomposition: the particles moved %g in this step, the ghost layer "
-                                    "was widened for %g (4 x the previous step's largest displacement, at least 2 h_max)", (double)dmax, (double)(0.5f * c0->slab_slack_w));
-            }
-        }
-        for (size_t i = 0; i < M.size(); i++) {
-            Member& m = M[i];
-            sph_ctx* c = m.c;
-            (void)hipSetDevice(c->device);
-            const size_t n = m.n ? m.n : 1;
-            LevelArgs& l = LV[i];
-            if ((rc = level_setup(m, p, after, l))) return rc;
-            // frontier form with probing halo members (OpLevelPropagate, mode 2); SPH_SLAB_LEVEL_PLAIN=1: every unassigned particle in
-            // every sweep (measurement / tests; parameters only: the same on every rank)
-            l.plain_propagate = c0->opt.slab_level_plain ? 1 : 2;
-            l.edge = c->dist.edge.as<uint8_t>();
-            l.pm_cell = after ? c->pm[c->pcur].as<float4>() : nullptr;
-            SweepArgs& al = AL[i];
-            al = m.a;
-            if (after) {
-                al.pm = c->pm[c->pcur ^ 1].as<float4>();
-                al.t_ext.slack = slab_lv_slack;
-                if (!replay_step_lists && c->tile_ts > 0) redilate_tiles_for_slack(c, c->stream, l.k, slab_lv_slack);
-            }
-            m.lv_level = (float*)l.level;
-            m.lv_when = (float*)l.when;
-            if (m.n) {
-                if (p->fill_stash_with == SPH_STASH_NONE) (void)hipMemsetAsync(c->stash.p, 0, n * 4, c->stream);
-                // (flags / states of the ghost slots are never read; zero them so that downloads see defined bytes)
-                (void)hipMemsetAsync(c->flag_surface.p, 0, n, c->stream);
-                (void)hipMemsetAsync(c->flag_insufficient.p, 0, n, c->stream);
-                launch_level_detect(c->stream, &c->prof, al, l);
-            }
-        }
-        if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level + when", -1, sel_lv_when))) return rc;   // (both fields in one exchange)
-        const bool frontier = LV[0].plain_propagate == 2;
-        if (frontier)   // sweep 0: the surface particles mark their unassigned neighbours (the candidates of sweep 1)
-            for (size_t i = 0; i < M.size(); i++) {
-                (void)hipSetDevice(M[i].c->device);
-                if (M[i].n) launch_level_propagate(M[i].c->stream, &M[i].c->prof, AL[i], LV[i], 0u, M[i].c->lvl_changed_d.as<uint32_t>() + 1023);
-            }
-        const int B = 8;
-        uint32_t t = 1;
-        for (bool done = false; !done;) {
-            for (auto& m : M) {
-                (void)hipSetDevice(m.c->device);
-                (void)hipMemsetAsync(m.c->lvl_changed_d.p, 0, B * sizeof(uint32_t), m.c->stream);
-            }
-            for (int b = 0; b < B; b++, t++) {
-                for (size_t i = 0; i < M.size(); i++) {
-                    Member& m = M[i];
-                    sph_ctx* c = m.c;
-                    (void)hipSetDevice(c->device);
-                    if (!m.n) continue;
-                    launch_level_propagate(c->stream, &c->prof, AL[i], LV[i], t, c->lvl_changed_d.as<uint32_t>() + b);
-                    if (t == 1u && p->fill_stash_with == SPH_STASH_SURFACE_DISTANCE_MIDDLE)
-                        launch_fill_stash(c->stream, &c->prof, AL[i], LV[i], c->stash.as<float>());
-                }
-                if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level + when", -1, sel_lv_when))) return rc;
-            }
-            for (auto& m : M) {
-                (void)hipSetDevice(m.c->device);
-                HIPCHK(m.c, hipMemcpyAsync(m.c->lvl_changed, m.c->lvl_changed_d.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, m.c->stream));
-            }
-            if ((rc = agree(G, wait_all(G)))) return rc;
-            // "nobody assigned anything" is final once it happens: the flags of a batch are ones followed by zeros, on every rank
-            std::vector<int> last(M.size(), 0);
-            for (size_t i = 0; i < M.size(); i++)
-                for (int b = 0; b < B; b++)
-                    if (M[i].c->lvl_changed[b]) last[i] = b + 1;
-            if ((rc = G.comm->allreduce_max_i32(G, last))) return rc;
-            done = last[0] < B;
-        }
-        for (auto& m : M) {
-            m.c->have_level = true;
-            m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
-        }
-        return SPH_OK;
-    };
-    if (level_on && G.multi() && !level_after) {
-        if ((rc = level_estimation_slabs(false))) return rc;
-        for (auto& m : M) dbg_sync(m.c, "level estimation (slabs)", 4);
-    } else if (level_on && !level_after) {
-        if ((rc = level_estimation(nullptr, nullptr, !c0->opt.level_serial))) return rc;   // (level_serial: measurement aid, everything on one stream)
+    // ---- level estimation on the extended-range lists (simulation.rs:2018-2046, 862-927), before advection -----------------------------
+    LevelState L(M.size(), p);
+    if (level_on && !level_after) {
+        if ((rc = level_estimation(G, M, p, false, L))) return rc;
+        if (G.multi())
+            for (auto& m : M) dbg_sync(m.c, "level estimation (slabs)", 4);
     } else if (!level_on) {
         for (auto& m : M) m.c->have_level = false;
     }
@@ -1527,10 +1501,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     auto plan_ahead_build = [&]() -> int {
         sph_ctx* c = c0;
         plan = AheadPlan{};
-        // (uniform scenes, and multi-resolution scenes sorted by their fine grid: tile_ts > 0; a narrow h distribution on the coarse
-        //  grid -- FromDistribution* -- is excluded with h_from_mass_mode)
-        if (G.multi() || !paced || !c->opt.ahead_build || !h_from_mass_mode || p->constrain_neighborhood_count || (!c->uniform_h && c->tile_ts <= 0) ||
-            (c->uniform_h && c->tile_ts != 0) || c->exact || M[0].n == 0)
+        if (!ahead_build_eligible(AheadWish{G.multi(), paced, c->opt.ahead_build != 0, h_from_mass_mode, p->constrain_neighborhood_count != 0, c->uniform_h, c->exact != 0,
+                                            c->tile_ts, M[0].n}))
             return SPH_OK;
         const uint32_t n = M[0].n;
         // the grid this step sorted by, moved to where the particles may be after it: the same cell size (the smoothing lengths are the
@@ -1568,7 +1540,7 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         // build waits for the smoothing -- takes the tail's header reduction into its count launch and the block-sum scan with it:
         // tail, count, place where there were tail, k_header_ahead, count, k_inc_scan, place (sph_sort.hip).  solve_queue() then
         // launches no k_header_ahead behind that tail (SolveQ::header_in_build), and queue_ahead_build() is the next thing queued.
-        plan.fused = c->opt.boundary_fused != 0 && !level_on && M[0].a.hdr_partials != nullptr;
+        plan.fused = ahead_build_fused(c->opt.boundary_fused != 0, level_on, M[0].a.hdr_partials != nullptr);
         if ((rc = ensure_inc_sort_scratch(c, g.ncells, plan.fused))) return rc;
         plan.incremental = true;
         plan.q = IncClassifyP{c->fgrid, g, c->cxy.as<uint32_t>(), c->akey[1].as<uint32_t>(), c->aval[1].as<uint8_t>(), c->inc_next.as<uint32_t>(),
@@ -1630,17 +1602,21 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         return SPH_OK;
     };
 
-    switch (p->pressure_solver_method) {
-    case SPH_SOLVER_IISPH: {  // simulation.rs:2389-2446
-        const SolveSpec solve = solve_iisph_density(p);
-        if ((rc = non_pressure())) return rc;
-        rec(4);
+    // One solve with a host wait of its own between the events e0 and e1, behind the non-pressure forces if they come here (`forces`).
+    // `ahead_behind_tail`: the next step's build is planned in front of it and rides behind its tail.
+    auto solve_alone = [&](const SolveSpec& solve, bool forces, int e0, int e1, bool final_solve, bool ahead_behind_tail) -> int {
+        if (forces && (rc = non_pressure())) return rc;
+        rec(e0);
         begin_solve(solve);
-        if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, solve, !level_on, &queue_ahead_build, plan.fused))) return rc;
-        rec(5);
+        if (ahead_behind_tail && (rc = plan_ahead_build())) return rc;
+        if ((rc = ahead_behind_tail ? pressure_iterations(G, M, solve, final_solve, &queue_ahead_build, plan.fused) : pressure_iterations(G, M, solve, final_solve))) return rc;
+        rec(e1);
+        return SPH_OK;
+    };
+    switch (p->pressure_solver_method) {
+    case SPH_SOLVER_IISPH:  // simulation.rs:2389-2446
+        if ((rc = solve_alone(solve_iisph_density(p), true, 4, 5, !level_on, true))) return rc;
         break;
-    }
     case SPH_SOLVER_IISPH2: {  // simulation.rs:2262-2387: omega rides in the source-term sweep; p /= sqrt(omega) before the last a^p
         const SolveSpec solve = solve_iisph2(p);
         if ((rc = non_pressure())) return rc;
@@ -1663,16 +1639,9 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         rec(5);
         break;
     }
-    case SPH_SOLVER_ONLY_DIVERGENCE: {  // simulation.rs:2448-2500
-        const SolveSpec solve = solve_divergence_only(p);
-        if ((rc = non_pressure())) return rc;
-        rec(2);
-        begin_solve(solve);
-        if ((rc = plan_ahead_build())) return rc;
-        if ((rc = pressure_iterations(G, M, solve, !level_on, &queue_ahead_build, plan.fused))) return rc;
-        rec(3);
+    case SPH_SOLVER_ONLY_DIVERGENCE:  // simulation.rs:2448-2500
+        if ((rc = solve_alone(solve_divergence_only(p), true, 2, 3, !level_on, true))) return rc;
         break;
-    }
     default: {  // HybridDFSPH, simulation.rs:2502-2670
         const SolveSpec divergence = solve_hybrid_divergence(p), density = solve_hybrid_density(p);
         const bool final_solve = !level_on;   // (of the density solve: the step's last unless the level estimation follows)
@@ -1717,8 +1686,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
             rec(5);
             break;
         }
-        const bool chain_wanted = c0->opt.chain >= 0 ? c0->opt.chain == 1 : c0->last_div_iters == c0->prev_div_iters;
-        const bool chain = (G.multi() || M[0].n > 0) && p->hybrid_dfsph_non_pressure_accel_before_divergence_free && chain_wanted;
+        const bool chain = (G.multi() || M[0].n > 0) && p->hybrid_dfsph_non_pressure_accel_before_divergence_free &&
+                           chain_wanted(c0->opt.chain, c0->last_div_iters, c0->prev_div_iters);
         if (chain) {
             SolveQ qd{divergence}, qs{density};
             qs.tot_slot = 1;
@@ -1767,13 +1736,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         g_trace.mark(4);
         rec(3);
         if ((rc = refresh_ghosts(G, M, sel_vel, 2, "vel"))) return rc;  // v += dt a^p happened in the final sweep
-        if (!p->hybrid_dfsph_non_pressure_accel_before_divergence_free)
-            if ((rc = non_pressure())) return rc;
-        rec(4);
-        begin_solve(density);
-        if ((rc = pressure_iterations(G, M, density, final_solve))) return rc;
+        if ((rc = solve_alone(density, !p->hybrid_dfsph_non_pressure_accel_before_divergence_free, 4, 5, final_solve, false))) return rc;
         g_trace.mark(5);
-        rec(5);
         break;
     }
     }
@@ -1781,52 +1745,31 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
     if (p->viscosity_type == SPH_VISC_XSPH)  // simulation.rs:2673-2676
         return c0->fail(SPH_ERR_XSPH_TODO, "not yet implemented (XSPH velocity smoothing)");
 
-    // ---- smooth_level_estimation_field (simulation.rs:2709-2722) ------------------------------------------------------------
-    if (level_on && G.multi()) {
-        if (level_after && (rc = level_estimation_slabs(true))) return rc;   // simulation.rs:2678-2707, at the advected positions
-        const auto t_lvl0 = std::chrono::steady_clock::now();
-        for (auto& m : M) {
-            m.lv_level = m.c->lvl[m.c->cur].as<float>();
-            m.lv_pmnew = (float*)m.c->pm[m.c->pcur ^ 1].as<float4>();
+    // ---- level estimation after advection (simulation.rs:2678-2707) and smooth_level_estimation_field (simulation.rs:2709-2722) --------
+    if (level_on) {
+        if (level_after && (rc = level_estimation(G, M, p, true, L))) return rc;
+        if ((rc = level_estimation_finish(M, L))) return rc;   // (before advection, one context: queued on the side stream at the start of the step)
+        {
+            LevelClock clock(M);
+            if (G.multi()) {   // the ghosts' level values and ADVECTED records (ghost lanes do not integrate) come from their owners
+                for (auto& m : M) {
+                    m.lv_level = m.c->lvl[m.c->cur].as<float>();
+                    m.lv_pmnew = (float*)m.c->pm[m.c->pcur ^ 1].as<float4>();
+                }
+                if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level"))) return rc;
+                if (!level_after && (rc = refresh_ghosts(G, M, sel_lv_pmnew, 4, "pm_new"))) return rc;
+            }
+            for (size_t i = 0; i < M.size(); i++) {
+                (void)hipSetDevice(M[i].c->device);
+                if (M[i].n) level_smooth_and_swap(M[i], L, i);
+            }
+            if (G.multi() && (rc = G.comm->agree_guards_queued(G))) return rc;
+            if ((rc = sync_ctrl(G, SYNC_FINAL))) return rc;   // (one context: SYNC_AGREE)
         }
-        // the ghosts' level values and ADVECTED records (ghost lanes do not integrate) come from their owners
-        if ((rc = refresh_ghosts(G, M, sel_lv_level, 1, "level"))) return rc;
-        if (!level_after && (rc = refresh_ghosts(G, M, sel_lv_pmnew, 4, "pm_new"))) return rc;
-        for (size_t i = 0; i < M.size(); i++) {
-            Member& m = M[i];
-            sph_ctx* c = m.c;
-            (void)hipSetDevice(c->device);
-            if (!m.n) continue;
-            SweepArgs as = level_after ? AL[i] : m.a;
-            as.pm = m.a.pm;   // (the smoothing takes the advected records as its own argument)
-            launch_level_smooth(c->stream, &c->prof, as, LV[i], c->pm[c->pcur ^ 1].as<float4>(), c->lvl[c->cur].as<float>(), c->lvl_tmp.as<float>());
-            std::swap(c->lvl[c->cur], c->lvl_tmp);
-            // (no classify_particles here: the reference's step never calls it -- sph_classify is the host's call)
+        if (!G.multi()) {   // the next step's neighbour build, behind the smoothed level values (the device works on it while the host leaves the step)
+            ahead_deferred = false;
+            if ((rc = queue_ahead_build())) return rc;
         }
-        if ((rc = G.comm->agree_guards_queued(G))) return rc;
-        if ((rc = sync_ctrl(G, SYNC_FINAL))) return rc;
-        for (auto& m : M) m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
-    }
-    if (level_after && !G.multi()) {   // simulation.rs:2678-2707: lists of the advected positions, then detection + propagation there
-        sph_ctx* c = M[0].c;
-        if ((rc = level_estimation(c->pm[c->pcur ^ 1].as<float4>(), c->pm[c->pcur].as<float4>(), false))) return rc;
-    }
-    if (level_on && !G.multi()) {
-        if ((rc = level_estimation_finish())) return rc;   // (before advection: queued on the side stream at the start of the step)
-        const auto t_lvl0 = std::chrono::steady_clock::now();
-        Member& m = M[0];
-        sph_ctx* c = m.c;
-        if (m.n) {
-            SweepArgs as = m.a;
-            as.t_ext.slack = lv_slack;
-            launch_level_smooth(c->stream, &c->prof, as, lv, c->pm[c->pcur ^ 1].as<float4>(), c->lvl[c->cur].as<float>(), c->lvl_tmp.as<float>());
-            std::swap(c->lvl[c->cur], c->lvl_tmp);
-        }
-        if ((rc = sync_ctrl(G))) return rc;
-        m.st.ms_level_estimation += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lvl0).count();
-        // the next step's neighbour build, behind the smoothed level values (the device works on it while the host leaves the step)
-        ahead_deferred = false;
-        if ((rc = queue_ahead_build())) return rc;
     }
 
     for (size_t i = 0; i < M.size(); i++) {
@@ -1834,8 +1777,8 @@ static int group_step_inner(Group& G, const sph_params* p, sph_step_stats* outs,
         sph_ctx* c = m.c;
         c->pcur ^= 1;  // integrated positions live in the other pm buffer; the old one keeps the pre-step snapshot
         c->lists_after = level_after && p->use_extended_range_for_level_estimation;
-        c->lists_after_k = G.multi() ? LV[i].k : lv.k;
-        c->lists_after_slack = G.multi() ? slab_lv_slack : lv_slack;
+        c->lists_after_k = L.lv[i].k;
+        c->lists_after_slack = L.slack;
         // every solver mode ends in an integrating final sweep, which left the next step's header in hdr_host
         // (constrain_neighborhood_count left reduced smoothing lengths in the records: the next step's k_header restores them)
         c->hdr_ahead = h_from_mass_mode && m.n > 0 && m.a.hdr_partials != nullptr && !p->constrain_neighborhood_count;
